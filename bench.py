@@ -8,6 +8,7 @@
   python bench.py --gpus N --steps K --warmup W          (no RANK in the environment: bench.py starts the N ranks itself, as
                                                           a CHILD `python -m torch.distributed.run`, before anything touches HIP)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR        (also writes the last timed step's outputs to DIR/*.npy)
 
 Every rank checks WORLD_SIZE == --gpus and refuses to run otherwise.
 
@@ -49,7 +50,7 @@ WORKLOADS = {
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="roundtrip",
                     help="roundtrip: BASELINE.json's metric (config 3: N=821 q=4096 encryptBits + decryptBits); encrypt_n701: config 4 "
@@ -90,7 +91,12 @@ def parse_args(argv=None):
                     help="LAST phase of the run: keep stepping for this long while socket power and shader clock are sampled "
                          "from sysfs (reported under `power`; 0 = skip).  Several seconds, so that a coarse external GPU-activity "
                          "sampler sees the GPU busy too")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last one computed (rank 0's shard) as DIR/<name>.npy in "
+                         "float32: a fixed seeded sample of rows, at most 60 MiB in all, for comparing two builds output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     w = WORKLOADS[args.workload]
     if args.total_batch_log2 is not None:
         if args.batch_log2 is not None:
@@ -182,6 +188,27 @@ def make_inputs(torch, dev, B, N, d, seed, ld=None):
         mp[:, :N] = m
         m = mp
     return r, m
+
+
+DUMP_BYTES = 60 << 20            # --dump-outputs: all arrays together
+DUMP_SEED = 20241               # --dump-outputs: which rows of the batch are written
+
+
+def dump_outputs(torch, out_dir, arrays, B, N):
+    """--dump-outputs: `arrays` (name -> device tensor, [B, >= N] or [B]) as out_dir/<name>.npy in float32 (every value is an
+    unsigned integer below 2^16, int16 tensors holding uint16 patterns: exact in float32).  The rows are the same seeded sample of
+    the batch on every run, as many as fit in DUMP_BYTES (the whole batch when it fits), in ascending order."""
+    row_bytes = 4 * sum(N if t.dim() == 2 else 1 for t in arrays.values())
+    n = min(B, DUMP_BYTES // row_bytes)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = (a[:, :N] if a.dim() == 2 else a).contiguous().cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+    return {"dir": out_dir, "arrays": sorted(arrays), "rows": int(n), "batch_rows": B, "row_seed": DUMP_SEED, "dtype": "float32"}
 
 
 def generate_key_pairs(torch, eng, dev, o, B, first_item, max_redraws=8, first_draw_minus=None):
@@ -488,6 +515,11 @@ def main():
                 if ev: ev[2].record(stream)
 
         gather_src = lambda: value if wl == "roundtrip" else e.view(torch.uint8)
+        # what a caller of the timed path receives (the reference's names)
+        results = {"e": e, "quotientE": quotE}
+        if wl == "roundtrip":
+            results.update(value=value, quotient1=quot1, remainder1=rem1, quotient2=quot2)
+        results = {k: t for k, t in results.items() if t is not None}
         unit_name = "round_trips" if wl == "roundtrip" else "encrypts"
 
         def cpu_unit_factory(n_cpu):
@@ -521,6 +553,7 @@ def main():
             if ev: ev[1].record(stream)
 
         gather_src = lambda: kouts[5].view(torch.uint8)            # remainderI of the h case
+        results = dict(zip(("quot_fq", "rem_fq", "quot_fp", "rem_fp", "quot_h", "rem_h"), kouts), flags=kflags)
         unit_name = "key_pairs"
 
         def cpu_unit_factory(n_cpu):
@@ -551,6 +584,8 @@ def main():
 
     elapsed, elapsed_local = sh.timed_region(run_steps, torch.cuda.synchronize, dist, red_dev, always=args.force_dist, return_local=True)
     seg_ms = [float(np.mean([ev[i].elapsed_time(ev[i + 1]) for ev in events])) for i in range(n_ev - 1)]
+    # before anything else runs on these buffers (the alternative-path and sustained phases below write them again)
+    dumped = dump_outputs(torch, args.dump_outputs, results, B, N) if args.dump_outputs and rank == 0 else None
 
     # ---- bit-exact check of a strided sample against the CPU oracle (outside the timed region): every output array ---
     n_chk = max(1, min(B, args.check_rows))
@@ -861,6 +896,8 @@ def main():
             out["dist"] = dist_info
         if gathered:
             out["gather"] = gathered
+        if dumped:
+            out["dump_outputs"] = dumped
         out.update(out_cpu)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

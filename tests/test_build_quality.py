@@ -11,14 +11,20 @@ import pytest
 KERNEL_TUS = ("valu_families", "matrix_encrypt", "matrix_decrypt", "matrix_rowimage", "matrix_peritem", "keygen_sampler_pack",
               "ntru_generic")
 # the shipped library, and the experiments build (kernel paths 6-10: most 16-byte result stores live there; it is tested for
-# bit-exactness too, so its kernels get the same gates): (ASMDIR, EXTRA, fewest wide stores the scan must see)
-BUILDS = {"default": ("/tmp/ntru_asm", "", 4), "experiments": ("/tmp/ntru_asm_exp", "-DNTRU_EXPERIMENTS", 60)}
+# bit-exactness too, so its kernels get the same gates): (EXTRA, fewest wide stores the scan must see)
+BUILDS = {"default": ("", 4), "experiments": ("-DNTRU_EXPERIMENTS", 60)}
 
 
-def _asm_usage(build):
-    """`make asm` (one .s + one .usage per kernel translation unit under ASMDIR, rebuilt when a source is newer); returns
+@pytest.fixture(scope="module")
+def asm_dirs(tmp_path_factory):
+    """ASMDIR of each build: fresh for this run, so that no ISA from another checkout or an earlier source is scanned."""
+    return {b: str(tmp_path_factory.mktemp("asm_" + b)) for b in BUILDS}
+
+
+def _asm_usage(build, asm_dir):
+    """`make asm` (one .s + one .usage per kernel translation unit under asm_dir, rebuilt when a source is newer); returns
     the concatenated resource-usage remarks."""
-    asm_dir, extra, _ = BUILDS[build]
+    extra, _ = BUILDS[build]
     src = os.path.join(ge.PKG_DIR, "csrc")
     cmd = ["make", "-C", src, "asm", "ASMDIR=" + asm_dir] + (["EXTRA=" + extra] if extra else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1800)
@@ -27,10 +33,10 @@ def _asm_usage(build):
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
-def test_no_kernel_spills_to_scratch(build):
+def test_no_kernel_spills_to_scratch(build, asm_dirs):
     """Register spills go to scratch memory = extra HBM traffic (round 1 measured 2.7-3.2x the algorithmic bytes
     before they were removed): every kernel must report ScratchSize 0."""
-    text = _asm_usage(build)
+    text = _asm_usage(build, asm_dirs[build])
     names = re.findall(r"Function Name: (\S+)", text)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)]
     assert len(names) == len(scratch) and len(names) >= 40, (len(names), len(scratch))
@@ -48,15 +54,15 @@ def test_no_kernel_spills_to_scratch(build):
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
-def test_no_wide_store_followed_by_a_write_of_its_data_registers(build):
+def test_no_wide_store_followed_by_a_write_of_its_data_registers(build, asm_dirs):
     """gfx950, measured (profiles/archive/r02_hazard_store_x4_soffset.txt): a buffer_store_dwordx4 whose data registers the very next
     instruction overwrites can store the NEW value of the first dword when the memory pipe is busy.  The compiler separates
     the two only when the store's soffset is not a register, so the kernels never pass a scalar offset to their 16-byte
     stores; this scans the generated ISA of every kernel translation unit for the pattern."""
-    _asm_usage(build)
+    _asm_usage(build, asm_dirs[build])
     lines = []
     for t in KERNEL_TUS:
-        lines += open(os.path.join(BUILDS[build][0], t + ".s")).read().split("\n")
+        lines += open(os.path.join(asm_dirs[build], t + ".s")).read().split("\n")
     kern, n, bad = None, 0, []
     for i, line in enumerate(lines):
         m = re.match(r"^(_Z\w+):", line)
@@ -76,5 +82,5 @@ def test_no_wide_store_followed_by_a_write_of_its_data_registers(build):
             a = int(w.group(1)); b = int(w.group(2) or a)
             if not (b < lo or a > hi):
                 bad.append((kern, line.strip(), nxt))
-    assert n >= BUILDS[build][2], n                       # the scan saw the wide stores of this build
+    assert n >= BUILDS[build][1], n                       # the scan saw the wide stores of this build
     assert not bad, bad[:5]

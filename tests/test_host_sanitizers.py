@@ -10,12 +10,13 @@ import subprocess
 import pytest
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
+HOSTCXX = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")     # tests/hostcheck/Makefile's compiler
 
 
 @pytest.mark.parametrize("kind", ["asan", "tsan"])
 def test_host_pipeline_under_sanitizers(kind):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
+    if not shutil.which(HOSTCXX):
+        pytest.skip("no ROCm clang++")
     build = subprocess.run(["make", "-C", HERE, kind], capture_output=True, text=True, timeout=600)
     assert build.returncode == 0, build.stderr[-3000:]
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66", ASAN_OPTIONS="detect_leaks=1")

@@ -203,3 +203,23 @@ def test_bench_four_ranks_report_each_rank():
     assert d["dist"]["straggler"]["ms_per_step_max"] <= d["ms_per_step"] * 1.0001
     assert d["gather"]["ranks"] == 4 and d["gather"]["rows"] == 4 << 14 and d["gather"]["every_shard_checksum_matches_its_owner"]
     assert abs(d["value"] - 4 * (1 << 14) / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+
+
+def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's witness arrays, a seeded row sample within the size cap, identical over two runs
+    with the same arguments (the inputs are seeded), and --steps is the number of timed steps the line reports."""
+    names = ["e", "quotient1", "quotient2", "quotientE", "remainder1", "value"]
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _run_bench(["--gpus", "1", "--steps", "3", "--batch-log2", "14", "--power-seconds", "0", "--dump-outputs", str(out)])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert d["dump_outputs"]["arrays"] == names and sorted(p.name for p in out.iterdir()) == [n + ".npy" for n in names]
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10 ** 6
+        runs.append({n: np.load(out / (n + ".npy")) for n in names})
+    rows = d["dump_outputs"]["rows"]
+    assert 0 < rows < 1 << 14
+    for n in names:
+        assert runs[0][n].dtype == np.float32 and runs[0][n].shape == (rows, 821), n
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+    assert runs[0]["e"].max() < 4096 and runs[0]["value"].max() <= 2 and runs[0]["e"].any()

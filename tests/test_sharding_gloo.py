@@ -133,6 +133,38 @@ def test_bench_total_batch_splits_over_the_ranks_and_says_strong_scaling():
         bench.parse_args(["--gpus", "2", "--total-batch-log2", "18", "--batch-log2", "17"])
 
 
+def test_bench_steps_must_be_positive():
+    assert bench.parse_args(["--steps", "7", "--warmup", "0"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--warmup", "-1"])
+
+
+def test_bench_dump_outputs_writes_a_seeded_row_sample_in_float32(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors shaped like the bench's buffers: pitched int16 rows holding uint16 patterns, uint8 rows, a
+    per-item flag.  The same rows every time, the whole batch when it fits, and never more than the size cap."""
+    assert bench.DUMP_BYTES < 64 * 10 ** 6 - 4096
+    B, N, LD = 64, 11, 16
+    g = torch.Generator().manual_seed(3)
+    arrays = {"e": torch.randint(0, 1 << 16, (B, LD), generator=g, dtype=torch.int32).to(torch.uint16).view(torch.int16),
+              "value": torch.randint(0, 3, (B, LD), generator=g, dtype=torch.uint8),
+              "flags": torch.randint(0, 2, (B,), generator=g, dtype=torch.uint8)}
+    info = bench.dump_outputs(torch, str(tmp_path / "all"), arrays, B, N)
+    assert info["rows"] == B and sorted(p.name for p in (tmp_path / "all").iterdir()) == ["e.npy", "flags.npy", "value.npy"]
+    e = np.load(tmp_path / "all" / "e.npy")
+    assert e.dtype == np.float32 and e.shape == (B, N)
+    assert np.array_equal(e, arrays["e"][:, :N].numpy().view(np.uint16).astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "all" / "flags.npy"), arrays["flags"].numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 400)  # room for 100 float32 rows of one column: 1000 rows are sampled
+    col = {"x": torch.arange(1000, dtype=torch.int16).view(1000, 1)}
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(torch, str(tmp_path / d), col, 1000, 1)
+        assert info["rows"] == 100 and np.load(tmp_path / d / "x.npy").shape == (100, 1)
+    a, b = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s2" / "x.npy")
+    assert np.array_equal(a, b) and np.all(np.diff(a[:, 0]) > 0)      # the same rows, ascending, each once
+
+
 def test_rank_reports_without_a_process_group():
     reports, s = sh.rank_reports({"rank": 0, "ms_per_step": 2.5})
     assert reports == [{"rank": 0, "ms_per_step": 2.5}] and s["slowest_rank"] == 0 and s["spread"] == 0.0
