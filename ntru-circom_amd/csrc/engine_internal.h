@@ -61,7 +61,7 @@ struct ntru_engine {
   hipStream_t stream;       // caller's stream for the *_dev entry points (never owned)
   int cus;
   int path;                 // ntru_engine_set_kernel_path: 0 auto, 1 MAC kernels, 2 add path, 3 add path without dot8, 4 matrix cores as two
-                            // workgroups per CU, 5 matrix cores with the lock-step decrypt; 6-9 only in -DNTRU_EXPERIMENTS builds
+                            // workgroups per CU, 5 matrix cores with the lock-step decrypt
   int max_blocks_per_cu;    // NTRU_MAX_BLOCKS_PER_CU read once at creation (tuning experiments); 0 = no cap
   int sampler_rounds;       // ntru_engine_set_sampler_rounds: 20 (RFC 8439, default), 12 or 8 rounds of the sampler's ChaCha block function
   char last_kernel[64];     // name of the kernel the last *_dev call launched (reporting only)
@@ -133,9 +133,8 @@ NTRU_HIDDEN int ntru_launch_decrypt_matrix(ntru_engine *eng, int N, int q, int p
 // decryptBits + packOutput(p - 1, N, value) in one kernel; d_value may be NULL (NTRU_NOT_TAKEN outside the matrix path's range)
 NTRU_HIDDEN int ntru_launch_decrypt_pack_matrix(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
                                                 const uint16_t *d_e, int64_t B, uint8_t *d_value, uint64_t *d_packed, int out_size);
-// the row-image variants (matrix_rowimage.hip): dense rows, one eight-wave workgroup per CU, results leave through LDS images
-NTRU_HIDDEN int ntru_launch_encrypt_rowimage(ntru_engine *eng, int N, int q, int ld, const uint16_t *d_h, const uint8_t *d_r,
-                                             const uint8_t *d_m, int64_t B, uint16_t *d_e, uint16_t *d_quotE);
+// encryptBits + packOutput on the row-image kernel (matrix_rowimage.hip): dense rows, one eight-wave workgroup per CU, results leave
+// through an LDS image
 NTRU_HIDDEN int ntru_launch_encrypt_pack_rowimage(ntru_engine *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint8_t *d_m,
                                                   int64_t B, uint64_t *d_packed, int os);
 // the same on the vector-ALU families (dense rows); never NTRU_NOT_TAKEN

@@ -19,9 +19,6 @@ int ntru_launch_encrypt_matrix(ntru_engine *eng, int N, int q, int ld, const uin
 int ntru_launch_decrypt_pack_matrix(ntru_engine *, int, int, int, const int8_t *, const uint8_t *, const uint16_t *, int64_t, uint8_t *, uint64_t *, int) {
   return NTRU_NOT_TAKEN;      // the host pipeline then runs decrypt + pack as two (fake) launches
 }
-int ntru_launch_encrypt_rowimage(ntru_engine *, int, int, int, const uint16_t *, const uint8_t *, const uint8_t *, int64_t, uint16_t *, uint16_t *) {
-  return NTRU_NOT_TAKEN;
-}
 int ntru_launch_encrypt_pack_rowimage(ntru_engine *, int, int, const uint16_t *, const uint8_t *, const uint8_t *, int64_t, uint64_t *, int) {
   return NTRU_NOT_TAKEN;      // the host pipeline then runs encrypt + pack as two (fake) launches
 }

@@ -10,9 +10,8 @@ import pytest
 
 KERNEL_TUS = ("valu_families", "matrix_encrypt", "matrix_decrypt", "matrix_rowimage", "matrix_peritem", "keygen_sampler_pack",
               "ntru_generic")
-# the shipped library, and the experiments build (kernel paths 6-10: most 16-byte result stores live there; it is tested for
-# bit-exactness too, so its kernels get the same gates): (EXTRA, fewest wide stores the scan must see)
-BUILDS = {"default": ("", 4), "experiments": ("-DNTRU_EXPERIMENTS", 60)}
+# the shipped library: (EXTRA, fewest wide stores the scan must see)
+BUILDS = {"default": ("", 4)}
 
 
 @pytest.fixture(scope="module")
@@ -40,17 +39,10 @@ def test_no_kernel_spills_to_scratch(build, asm_dirs):
     names = re.findall(r"Function Name: (\S+)", text)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)]
     assert len(names) == len(scratch) and len(names) >= 40, (len(names), len(scratch))
-    # (the two fp4 experiment kernels of path 11 keep a few loop-invariant addresses in scratch, 52-80 bytes per lane, outside
-    # their loops: measured slower than the int8 kernels anyway, profiles/r04_fp4_product2.txt -- not worth a register diet)
-    # (k_verify_keys_m16, the 16-row-tile experiment of path 12: 176 bytes per lane between its two walks, not inside them; measured slower)
-    bad = [(n, s) for n, s in zip(names, scratch)
-           if s and not (build == "experiments" and ((("k_decrypt_mq" in n or "k_decrypt_m8q" in n) and s <= 96) or ("k_verify_keys_m16" in n and s <= 208)))]
+    bad = [(n, s) for n, s in zip(names, scratch) if s]
     assert not bad, bad
     for must in ("k_encrypt_t", "k_decrypt_s", "k_encrypt", "k_decrypt", "k_verify_keys", "k_polymul_split", "k_encrypt_wp", "k_decrypt_mp"):
         assert any(must in n for n in names), must
-    if build == "experiments":
-        for must in ("k_encrypt_m2", "k_encrypt_mc", "k_encrypt_m8", "k_decrypt_m8d", "k_encrypt_w", "k_decrypt_m8q"):
-            assert any(must in n for n in names), must
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))

@@ -19,9 +19,6 @@ CONFIGS = [  # (N, q, d) -- the BASELINE.json parameter sets first
 ]
 
 
-from conftest import EXPERIMENT_PATHS, has_experiments, set_path_or_skip
-
-
 @pytest.fixture(scope="module")
 def eng():
     return pkg.Engine(0)
@@ -240,7 +237,7 @@ def test_kernel_families_agree(eng):
         f = ternary_rows(rng, 1, N, d, d - 1, two=-1)[0]
         r = ternary_rows(rng, 9, N, d, d); m = rng.integers(0, 2, (9, N))
         outs, names = [], []
-        for path in (1, 2, 3, 4, 5, 0) + ((6, 7, 8, 9) if has_experiments(eng) else ()):
+        for path in (1, 2, 3, 4, 5, 0):
             eng.set_kernel_path(path)
             e, quot = eng.encrypt_batch(N, q, h, r, m)
             names.append(eng.last_kernel() if False else None)
@@ -255,15 +252,15 @@ def test_kernel_families_agree(eng):
 @pytest.mark.parametrize("N,q,d", [(17, 32, 2), (31, 64, 5), (32, 128, 6), (33, 32, 7), (64, 8192, 20), (65, 4096, 21),
                                    (167, 128, 18), (509, 2048, 169), (701, 8192, 233), (821, 4096, 273),
                                    (1021, 4096, 300), (1022, 2048, 300), (1023, 8192, 300), (1024, 8192, 300)])
-@pytest.mark.parametrize("path", [4, 5] + EXPERIMENT_PATHS)
+@pytest.mark.parametrize("path", [4, 5])
 def test_matrix_core_path_equals_oracle(eng, N, q, d, path):
-    """Family 4 forced (ntru_engine_set_kernel_path 4: two workgroups per CU; 5: lock-step decrypt; 6-10: the variants of the experiments build), including sizes the
+    """Family 4 forced (ntru_engine_set_kernel_path 4: two workgroups per CU; 5: lock-step decrypt), including sizes the
     automatic choice leaves to other families, batches that do not fill a 32-row block, and h at the corners of the
     digit-plane range."""
     rng = np.random.default_rng(N * 31 + q)
     p = 3
-    set_path_or_skip(eng, path)
-    two_groups_fit = (N + 31) // 32 < 32                   # 32 column tiles: 160 KB of LDS do not hold two groups / two chunked workgroups
+    eng.set_kernel_path(path)
+    two_groups_fit = (N + 31) // 32 < 32                   # 32 column tiles: 160 KB of LDS do not hold two groups
     dma = ("k_encrypt_md",) if N + 3 <= 1024 else ("k_encrypt_md", "k_encrypt_m")   # direct-to-LDS loads: rows that fit one 1024-byte instruction
     try:
         for B in (1, 31, 33, 70):
@@ -274,9 +271,7 @@ def test_matrix_core_path_equals_oracle(eng, N, q, d, path):
             r = ternary_rows(rng, B, N, d, d)
             m = rng.integers(0, 256, (B, N))
             e, quot = eng.encrypt_batch(N, q, h, r, m)
-            assert eng.last_kernel() in {4: ("k_encrypt_m",), 5: dma, 6: ("k_encrypt_m2",),
-                                         7: ("k_encrypt_mc",) if two_groups_fit else dma, 8: dma,
-                                         9: ("k_encrypt_m8",), 10: ("k_encrypt_w",) + dma, 11: dma}[path]  # (two encrypt groups fit 160 KB at every N <= 1024)
+            assert eng.last_kernel() in {4: ("k_encrypt_m",), 5: dma}[path]
             e_o, quot_o = orc.encrypt_batch(N, q, h, r, m)
             assert np.array_equal(e, e_o) and np.array_equal(quot, quot_o), B
             e_only, _ = eng.encrypt_batch(N, q, h, r, m, want_quot=False)
@@ -285,10 +280,7 @@ def test_matrix_core_path_equals_oracle(eng, N, q, d, path):
             ein[-1] = rng.integers(0, q, N)
             ein[0, :4] = (q - 1, 0, q // 2, q // 2 + 1)
             got = eng.decrypt_batch(N, q, p, f, fp, ein)
-            assert eng.last_kernel() == ("k_decrypt_m8" if path in (5, 9) and two_groups_fit else
-                                         "k_decrypt_m8d" if path == 8 and two_groups_fit else
-                                         "k_decrypt_m8q" if path == 11 and two_groups_fit and N > 512 else
-                                         "k_decrypt_mq" if path == 11 else "k_decrypt_m")
+            assert eng.last_kernel() == ("k_decrypt_m8" if path == 5 and two_groups_fit else "k_decrypt_m")
             want = orc.decrypt_batch(N, q, p, f, fp, ein)
             for g_, w_, name in zip(got, want, ("value", "quotient1", "remainder1", "quotient2")):
                 assert np.array_equal(g_, w_), (B, name)
@@ -298,13 +290,13 @@ def test_matrix_core_path_equals_oracle(eng, N, q, d, path):
         eng.set_kernel_path(0)
 
 
-@pytest.mark.parametrize("path", [4, 5] + EXPERIMENT_PATHS)
+@pytest.mark.parametrize("path", [4, 5])
 def test_matrix_core_path_random_parameter_sweep(eng, path):
     """Differential sweep: 40 random (N, q, B) with N in [2, 1024] (odd and even, around the 32-tile boundaries), q any
     power of two up to 8192, ragged B; matrix-core family (forced) against the CPU oracle, all outputs."""
     rng = np.random.default_rng(20240)
     p = 3
-    set_path_or_skip(eng, path)
+    eng.set_kernel_path(path)
     try:
         for trial in range(40):
             N = int(rng.choice([rng.integers(2, 1025), 32 * rng.integers(1, 33) + rng.integers(-1, 2)]))
@@ -318,10 +310,7 @@ def test_matrix_core_path_random_parameter_sweep(eng, path):
             r = ternary_rows(rng, B, N, d, d)
             m = rng.integers(0, 256, (B, N))
             e, quot = eng.encrypt_batch(N, q, h, r, m)
-            assert eng.last_kernel() in {4: ("k_encrypt_m",), 5: ("k_encrypt_md", "k_encrypt_m"), 6: ("k_encrypt_m2",),
-                                         7: ("k_encrypt_mc", "k_encrypt_md", "k_encrypt_m"), 8: ("k_encrypt_md", "k_encrypt_m"),
-                                         9: ("k_encrypt_m8", "k_encrypt_md", "k_encrypt_m"),
-                                         10: ("k_encrypt_w", "k_encrypt_md", "k_encrypt_m"), 11: ("k_encrypt_md", "k_encrypt_m")}[path]
+            assert eng.last_kernel() in {4: ("k_encrypt_m",), 5: ("k_encrypt_md", "k_encrypt_m")}[path]
             e_o, quot_o = orc.encrypt_batch(N, q, h, r, m)
             assert np.array_equal(e, e_o) and np.array_equal(quot, quot_o), (N, q, B)
             ein = np.concatenate([e_o, rng.integers(0, q, (3, N))])
@@ -336,8 +325,8 @@ def test_matrix_core_path_random_parameter_sweep(eng, path):
 @pytest.mark.parametrize("N,q,B", [(167, 128, 32 * 256 * 3 + 5), (821, 4096, 32 * 256 * 2 + 33), (65, 64, 32 * 256 + 1),
                                    (65, 64, 32 * 256 * 5 + 9), (33, 32, 32 * 256 * 5 + 3)])   # waves WITHOUT a strip (NT < 4) on their second trip
 def test_role_split_kernels_many_row_blocks_per_workgroup(eng, N, q, B):
-    """Batches of more than two row blocks per CU: the persistent loop of the role-split kernels alternates its two
-    operand stages and drains every chunk one round late, the last one after the loop; ragged last row block."""
+    """Batches of more than two row blocks per CU: every trip of the persistent loops after the first (k_encrypt_md's rows
+    requested into LDS one trip ahead, k_decrypt_m8's two lock-step groups); ragged last row block."""
     rng = np.random.default_rng(N + B)
     p, d = 3, N // 3
     h = rng.integers(0, q, N); fp = rng.integers(0, p, N)
@@ -349,8 +338,6 @@ def test_role_split_kernels_many_row_blocks_per_workgroup(eng, N, q, B):
     e_o, quot_o = orc.encrypt_batch(N, q, h, r, m)
     want = orc.decrypt_batch(N, q, p, f, fp, e_o)
     variants = ((5, "k_encrypt_md", "k_decrypt_m8"),)       # every trip of k_encrypt_md but the first works on rows loaded straight into LDS
-    if has_experiments(eng):
-        variants += ((6, "k_encrypt_m2", "k_decrypt_m"), (8, "k_encrypt_md", "k_decrypt_m8d"), (9, "k_encrypt_m8", "k_decrypt_m8"))
     for path, ename, dname in variants:
         eng.set_kernel_path(path)
         try:
@@ -365,7 +352,7 @@ def test_role_split_kernels_many_row_blocks_per_workgroup(eng, N, q, B):
             assert np.array_equal(g_, w_), (path, name)
 
 
-@pytest.mark.parametrize("path", [0] + [x for x in EXPERIMENT_PATHS if x == 8])   # 8: decrypt's rows arrive by direct-to-LDS loads (dword-aligned pieces + a shift)
+@pytest.mark.parametrize("path", [0])
 @pytest.mark.parametrize("N,q", [(821, 4096), (167, 128), (701, 8192), (1021, 2048), (1022, 4096), (1023, 8192), (1024, 1024)])   # N >= 1022: a row + its byte phase exceeds one 1024-byte direct-to-LDS instruction
 def test_device_pointers_at_any_alignment(eng, N, q, path):
     """The *_dev entry points take any pointer: the matrix-core kernels read rows through aligned chunks + shifts and
@@ -378,7 +365,7 @@ def test_device_pointers_at_any_alignment(eng, N, q, path):
     r = ternary_rows(rng, B, N, d, d); m = rng.integers(0, 256, (B, N))
     e_o, quot_o = orc.encrypt_batch(N, q, h, r, m)
     want = orc.decrypt_batch(N, q, p, f, fp, e_o)
-    set_path_or_skip(eng, path)
+    eng.set_kernel_path(path)
     eng.set_stream(torch.cuda.current_stream().cuda_stream)
     try:
         for off in (1, 2, 3, 5, 14, 15):
@@ -416,7 +403,7 @@ def test_device_pointers_at_any_alignment(eng, N, q, path):
 
 @pytest.mark.parametrize("N,q,ld", [(821, 4096, 832), (821, 4096, 822), (821, 4096, 1024), (167, 128, 192), (701, 8192, 704),
                                     (509, 2048, 509), (64, 32, 80), (33, 8192, 47)])
-@pytest.mark.parametrize("path", [0] + [x for x in EXPERIMENT_PATHS if x == 8])
+@pytest.mark.parametrize("path", [0])
 def test_pitched_rows_equal_oracle(eng, N, q, ld, path):
     """ntru_*_batch_pitched_dev: rows at a pitch of ld >= N elements.  Pad elements of the inputs hold garbage and must
     not reach any result; pad elements of the outputs must stay untouched; a ragged batch (B % 32 != 0) must not write
@@ -447,7 +434,7 @@ def test_pitched_rows_equal_oracle(eng, N, q, ld, path):
     dfp = torch.from_numpy(fp.astype(np.uint8)).to(dev)
     dr = pitched(r, np.uint8, 256); dm = pitched(m, np.uint8, 256)
     de = outbuf(torch.int16, 0x5A5A); dq = outbuf(torch.int16, 0x5A5A)
-    set_path_or_skip(eng, path)
+    eng.set_kernel_path(path)
     eng.set_stream(torch.cuda.current_stream().cuda_stream)
     try:
         eng.encrypt_batch_dev(N, q, dh.data_ptr(), dr.data_ptr(), dm.data_ptr(), B, de.data_ptr(), dq.data_ptr(), ld=ld)
@@ -830,30 +817,6 @@ def test_verify_keys_h_comparison_boundaries_and_unreduced_fp(eng):
         assert (want["flags"][0::4][1:len(cuts)] & 4 == 0).all()            # the truncated copies are valid h (cut 0 = the zero
                                                                              # polynomial, which still compares index 0)
         assert np.array_equal(got["rem_fp"], base["rem_fp"])                 # unreduced fp = reduced fp
-
-
-def test_verify_keys_on_the_16_row_tile_experiment(eng):
-    """Kernel path 12 (experiments library only): verifyKeysInputs on v_mfma_i32_16x16x64_i8 -- two tile distances per instruction, two
-    row groups, rows moved two at a time inside 16-lane rows.  Bit-exact against the oracle and the default kernel; measured slower."""
-    set_path_or_skip(eng, 12)
-    try:
-        rng = np.random.default_rng(12)
-        p = 3
-        for N, q in ((821, 4096), (509, 2048), (512, 8192), (513, 64), (64, 4), (1024, 8192), (167, 128), (701, 8192), (95, 2048)):
-            B = int(rng.integers(1, 70)); d = N // 3
-            f = ternary_rows(rng, B, N, d, max(d - 1, 0), two=-1); g = ternary_rows(rng, B, N, d, d, two=-1)
-            fq = rng.integers(0, q, (B, N)); fp = rng.integers(0, p, (B, N)); h = rng.integers(0, q, (B, N))
-            if B > 2:
-                h[1, N // 3:] = 0; h[2] = 0
-                fq[0, :] = 0; fq[0, 0] = 1; f[0, :] = 0; f[0, 0] = 1
-            eng.set_kernel_path(12)
-            got = eng.verify_keys_batch(N, q, p, f, g, fq, fp, h)
-            assert eng.last_kernel() == "k_verify_keys_m16", (N, q, eng.last_kernel())
-            want = orc.verify_keys_batch(N, q, p, f, g, fq, fp, h)
-            for k in want:
-                assert np.array_equal(got[k], want[k]), (N, q, k)
-    finally:
-        eng.set_kernel_path(0)
 
 
 def test_verify_keys_device_pointers_at_any_alignment(eng):
@@ -1260,49 +1223,6 @@ def test_multi_device_host_api_shards_equal_oracle():
         pkg.MultiEngine([0, 99])                                               # no such device
 
 
-@pytest.mark.parametrize("N,q", [(821, 4096), (701, 8192), (509, 2048), (167, 128), (33, 64), (96, 256)] if EXPERIMENT_PATHS else [])
-def test_chunked_result_stores_at_every_base_alignment(eng, N, q):
-    """Kernel path 7 (k_encrypt_mc): results leave through per-wave LDS chunks as aligned 16-byte pieces plus 2-byte edges,
-    so the geometry depends on the byte phase of every row segment.  Output arrays at all eight 2-byte phases of a 16-byte
-    line (e and quotE at different ones), dense rows (N odd and even), ragged batches; guard elements before and behind the
-    arrays must stay untouched."""
-    import torch
-    dev = torch.device("cuda:0")
-    rng = np.random.default_rng(N + q)
-    d = N // 3
-    h = rng.integers(0, q, N)
-    dh = torch.from_numpy(h.astype(np.int16)).to(dev)
-    set_path_or_skip(eng, 7)
-    eng.set_stream(torch.cuda.current_stream().cuda_stream)
-    try:
-        for phase in range(8):
-            B = (1, 31, 45, 64, 77, 33, 96, 5)[phase]
-            r = ternary_rows(rng, B, N, d, d); m = rng.integers(0, 256, (B, N))
-            e_o, quot_o = orc.encrypt_batch(N, q, h, r, m)
-            dr = torch.from_numpy(r.astype(np.uint8)).to(dev); dm = torch.from_numpy(m.astype(np.uint8)).to(dev)
-            G = 64                                            # guard elements on both sides
-            pe, pq = phase, (phase * 3 + 1) % 8
-            be = torch.full((G + pe + B * N + G,), 0x5A5A, dtype=torch.int16, device=dev)
-            bq = torch.full((G + pq + B * N + G,), 0x5A5A, dtype=torch.int16, device=dev)
-            assert be.data_ptr() % 16 == 0 and bq.data_ptr() % 16 == 0
-            e_ptr, q_ptr = be.data_ptr() + 2 * (G + pe), bq.data_ptr() + 2 * (G + pq)
-            eng.encrypt_batch_dev(N, q, dh.data_ptr(), dr.data_ptr(), dm.data_ptr(), B, e_ptr, q_ptr)
-            torch.cuda.synchronize()
-            assert eng.last_kernel() == "k_encrypt_mc"
-            for buf, ph, want, name in ((be, pe, e_o, "e"), (bq, pq, quot_o, "quotE")):
-                a = buf.cpu().numpy().astype(np.int64) & 0xFFFF
-                assert np.array_equal(a[G + ph:G + ph + B * N].reshape(B, N), want), (name, phase, B)
-                assert (a[:G + ph] == 0x5A5A).all() and (a[G + ph + B * N:] == 0x5A5A).all(), (name, phase, "wrote outside")
-            # value-only mode (no quotient array)
-            be.fill_(0x5A5A)
-            eng.encrypt_batch_dev(N, q, dh.data_ptr(), dr.data_ptr(), dm.data_ptr(), B, e_ptr, None)
-            torch.cuda.synchronize()
-            a = be.cpu().numpy().astype(np.int64) & 0xFFFF
-            assert np.array_equal(a[G + pe:G + pe + B * N].reshape(B, N), e_o), ("e only", phase)
-            assert (a[:G + pe] == 0x5A5A).all() and (a[G + pe + B * N:] == 0x5A5A).all()
-    finally:
-        eng.set_kernel_path(0)
-        eng.set_stream(None)
 
 
 @pytest.mark.parametrize("N,q,d,B", [(167, 128, 18, 9001), (821, 4096, 273, 300), (509, 2048, 169, 1)])

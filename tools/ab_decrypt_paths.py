@@ -14,7 +14,7 @@ for N, q in ((509, 2048), (701, 8192), (821, 4096), (167, 128)):
     fp = torch.randint(0, 3, (N,), dtype=torch.uint8, device=dev, generator=g)
     ref = None; out = {}
     for rnd in range(2):
-        for path in (4, 5, 8):
+        for path in (4, 5):
             eng.set_kernel_path(path)
             v = torch.empty((B, N), dtype=torch.uint8, device=dev); q2 = torch.empty_like(v)
             q1 = torch.empty((B, N), dtype=torch.int16, device=dev); r1 = torch.empty_like(q1)

@@ -72,9 +72,3 @@ lab8 = [(0, 1, "wait b1"), (1, 2, "stage"), (2, 3, "wait b2"), (3, 4, "P1 loops 
         (12, 13, "(barrier) P2 loops s2"), (13, 14, "P2 (barrier) epi s2")]
 report("k_decrypt_m8 group 0", st, lab8, 256, slice(0, 4))
 report("k_decrypt_m8 group 1", st, lab8, 256, slice(4, 8))
-eng.set_kernel_path(8)      # needs EXTRA="-DNTRU_STAMPS -DNTRU_EXPERIMENTS"
-for _ in range(2):
-    eng.decrypt_batch_dev(N, q, 3, f.data_ptr(), fp.data_ptr(), e.data_ptr(), B, v.data_ptr(), q1.data_ptr(), r1.data_ptr(), q2.data_ptr())
-st = read("dec")
-report("k_decrypt_m8d group 0 (rows by direct-to-LDS loads)", st, lab8, 256, slice(0, 4))
-report("k_decrypt_m8d group 1", st, lab8, 256, slice(4, 8))

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 OUT=gpurun_out/r03_power_kernel_paths.txt
 : > $OUT
-for kp in ${PATHS:-0 4 7 6 5}; do
+for kp in ${PATHS:-0 4 5}; do
   echo "# kernel path $kp" >> $OUT
   timeout -k 10 100 python3 tools/clock_power.py --seconds 2.5 --no-smi --loads encrypt,decrypt --kernel-path $kp 2>/dev/null | python3 -c '
 import sys, json
