@@ -47,7 +47,7 @@ int ntru_blocks_per_cu(ntru_engine *eng, const void *fn, int threads, size_t lds
   // The query over-reports LDS-bound residency: a CU hands out its 160 KB in pieces of 1280 bytes per WORKGROUP (bench_micro/wg_residency:
   // twelve workgroups of 13312 bytes are reported, eleven are resident; twenty of 8192, eighteen).  A persistent grid sized by the
   // reported figure runs its surplus workgroups as a second round on a nearly empty chip.
-  if (lds > 0 && getenv("NTRU_TRUST_OCCUPANCY_QUERY") == nullptr) {
+  if (lds > 0) {
     const size_t piece = 1280, per_wg = (lds + piece - 1) / piece * piece;
     const int fit = (int)((size_t)160 * 1024 / per_wg);
     if (fit < n) n = fit;
@@ -120,11 +120,6 @@ extern "C" int ntru_engine_create(int device, ntru_engine_t **out) {
   eng->scratch_stream = nullptr;
   eng->scratch_event = nullptr;
   eng->scratch_used = false;
-  eng->max_blocks_per_cu = 0;
-  if (const char *cap = getenv("NTRU_MAX_BLOCKS_PER_CU")) {      // tuning experiments only; read once
-    const int c = atoi(cap);
-    if (c >= 1) eng->max_blocks_per_cu = c;
-  }
   *out = eng;
   return NTRU_OK;
 }
@@ -251,10 +246,8 @@ extern "C" int ntru_decrypt_pack_batch_dev(ntru_engine_t *eng, int N, int q, int
   if (B == 0) return NTRU_OK;
   if (!d_f || !d_fp || !d_e || !d_packed) return fail(NTRU_ERR_ARG, "ntru_decrypt_pack_batch: NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
-  if (eng->path == 0 || eng->path >= 4) {
-    const int rc = ntru_launch_decrypt_pack_matrix(eng, N, q, p, d_f, d_fp, d_e, B, d_value, d_packed, os);
-    if (rc != NTRU_NOT_TAKEN) return rc;
-  }
+  const int rc = ntru_launch_decrypt_pack_matrix(eng, N, q, p, d_f, d_fp, d_e, B, d_value, d_packed, os);
+  if (rc != NTRU_NOT_TAKEN) return rc;
   if (!d_value) return fail(NTRU_ERR_ARG, "ntru_decrypt_pack_batch: outside the fused kernel's range d_value is needed as the intermediate");
   if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_e, B, d_value, nullptr, nullptr, nullptr)) return rc;
   return ntru_pack_bytes_batch_dev(eng, p - 1, N, d_value, B, d_packed);
@@ -271,7 +264,7 @@ extern "C" int ntru_encrypt_pack_batch_dev(ntru_engine_t *eng, int N, int q, con
   if (B == 0) return NTRU_OK;
   if (!d_h || !d_r || !d_m || !d_packed) return fail(NTRU_ERR_ARG, "ntru_encrypt_pack_batch: NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
-  if (!d_e && (eng->path == 0 || eng->path >= 4)) {
+  if (!d_e) {
     const int rc = ntru_launch_encrypt_pack_rowimage(eng, N, q, d_h, d_r, d_m, B, d_packed, os);
     if (rc != NTRU_NOT_TAKEN) return rc;
   }

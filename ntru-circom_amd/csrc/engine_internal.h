@@ -62,7 +62,6 @@ struct ntru_engine {
   int cus;
   int path;                 // ntru_engine_set_kernel_path: 0 auto, 1 MAC kernels, 2 add path, 3 add path without dot8, 4 matrix cores as two
                             // workgroups per CU, 5 matrix cores with the lock-step decrypt
-  int max_blocks_per_cu;    // NTRU_MAX_BLOCKS_PER_CU read once at creation (tuning experiments); 0 = no cap
   int sampler_rounds;       // ntru_engine_set_sampler_rounds: 20 (RFC 8439, default), 12 or 8 rounds of the sampler's ChaCha block function
   char last_kernel[64];     // name of the kernel the last *_dev call launched (reporting only)
   HostSlot slot[NTRU_HOST_SLOTS];
@@ -113,10 +112,9 @@ static inline int fail(int code, const std::string &msg) { return ntru_fail(code
 static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // Workgroups of 256 for an elementwise kernel.  Kernels that move 16 bytes per lane and access (streaming = true) get TWO per CU: more
 // resident waves lower the HBM rate (the add of two ciphertext batches: 5.0 TB/s with 8 per CU, 5.9 with 2, 4.8 with 1:
-// profiles/archive/r03_ab_elementwise_grid.txt); element-per-lane kernels keep 8.  NTRU_EW_PER_CU overrides the streaming figure (experiments).
+// profiles/archive/r03_ab_elementwise_grid.txt); element-per-lane kernels keep 8.
 static inline dim3 elementwise_grid(const ntru_engine *eng, long total, bool streaming = false) {
-  static const int ew_env = getenv("NTRU_EW_PER_CU") ? atoi(getenv("NTRU_EW_PER_CU")) : 0;
-  const int per_cu = streaming ? (ew_env > 0 ? ew_env : 2) : 8;
+  const int per_cu = streaming ? 2 : 8;
   long blocks = (total + 255) / 256, cap = (long)eng->cus * per_cu;
   return dim3((unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks)));
 }

@@ -1,5 +1,5 @@
 // kernels_common.h -- what the kernel translation units of libntru_engine.so share: scalar types, the workgroup shape, small device
-// helpers, and the host-side launch helpers (persistent grid from the occupancy query).
+// helpers, and the host-side launch helpers (persistent launch with the grid from the occupancy query).
 #ifndef NTRU_KERNELS_COMMON_H
 #define NTRU_KERNELS_COMMON_H
 
@@ -33,17 +33,16 @@ static __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// Persistent grid: as many workgroups as are co-resident (occupancy query for this kernel and LDS size) x CUs, capped
-// by the work available.  A grid larger than residency would run its tail at a fraction of the chip.  The dynamic-LDS limit of
-// a kernel is raised at its first use, inside ntru_blocks_per_cu.
-template <class Kern>
-static int resident_grid(const ntru_engine *eng, Kern kern, size_t lds, long work_blocks, dim3 *grid, int threads = BLOCK_THREADS) {
+// Launches a persistent kernel on eng->stream: as many workgroups as are co-resident (occupancy query for this kernel, block size
+// and LDS size) x CUs, capped by the work available (work_blocks >= 1).  A grid larger than residency would run its tail at a
+// fraction of the chip.  The dynamic-LDS limit of a kernel is raised at its first use, inside ntru_blocks_per_cu.
+template <class Kern, class... Args>
+static int launch_resident(ntru_engine *eng, Kern kern, long work_blocks, int threads, size_t lds, Args... args) {
   int per_cu = 0;
-  if (int rc = ntru_blocks_per_cu(const_cast<ntru_engine *>(eng), (const void *)kern, threads, lds, &per_cu)) return rc;
-  if (eng->max_blocks_per_cu && eng->max_blocks_per_cu < per_cu) per_cu = eng->max_blocks_per_cu;
-  long blocks = (long)eng->cus * per_cu;
-  if (blocks > work_blocks) blocks = work_blocks;
-  *grid = dim3((unsigned)(blocks < 1 ? 1 : blocks));
+  if (int rc = ntru_blocks_per_cu(eng, (const void *)kern, threads, lds, &per_cu)) return rc;
+  const long resident = (long)eng->cus * per_cu;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(work_blocks < resident ? work_blocks : resident)), dim3(threads), lds, eng->stream, args...);
+  HIP_TRY(hipGetLastError());
   return NTRU_OK;
 }
 

@@ -658,14 +658,7 @@ static int launch_invert_nw(ntru_engine *eng, int N, const int8_t *d_f, long B, 
   // planes in LDS (NWC = 0), or only the transposition buffer of the results: [plane][word][lane]
   const size_t lds = NWC ? (size_t)(P == 2 ? 1 : 2) * NWC * 64 * 4 : (size_t)(P == 2 ? 4 : 8) * ((N + 32) / 32) * 64 * 4;
   if (lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "N too large for the inversion kernel's LDS planes");
-  int per_cu = 0;
-  if (int rc = ntru_blocks_per_cu(eng, (const void *)k_invert_key<P, NWC>, 64, lds, &per_cu)) return rc;
-  long blocks = (B + 63) / 64, cap = (long)eng->cus * (per_cu < 1 ? 1 : per_cu);
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL((k_invert_key<P, NWC>), dim3((unsigned)blocks), dim3(64), lds, eng->stream, N, d_f, B, (u16 *)d16, d8,
-                     d_flags, (u32)bit);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_invert_key<P, NWC>, (B + 63) / 64, 64, lds, N, d_f, B, (u16 *)d16, d8, d_flags, (u32)bit);
 }
 
 // Register-resident planes for the word counts below (N + 1 bits rounded up to the next size), LDS planes otherwise.
@@ -792,17 +785,9 @@ static int launch_sampler(ntru_engine *eng, int N, int n1, int n2, int other, co
   const int NW = (N + 15) / 16;                          // dwords of 16 symbols per row
   const size_t lds = WAVES * ((size_t)64 * NW * 4 + (BIGN ? (size_t)((N + 2) & ~1) * 4 : 0));
   if (lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "N too large for the sampler's LDS rows");
-  const void *fn = (const void *)k_sample_ternary<BIGN, WAVES, DR>;
-  int per_cu = 0;
-  if (int rc = ntru_blocks_per_cu(eng, fn, WAVES * 64, lds, &per_cu)) return rc;
-  if (eng->max_blocks_per_cu && eng->max_blocks_per_cu < per_cu) per_cu = eng->max_blocks_per_cu;     // NTRU_MAX_BLOCKS_PER_CU (experiments)
-  long blocks = (B + WAVES * 64 - 1) / (WAVES * 64), cap = (long)eng->cus * (per_cu < 1 ? 1 : per_cu);
-  if (blocks > cap) blocks = cap;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sample_ternary");
-  hipLaunchKernelGGL((k_sample_ternary<BIGN, WAVES, DR>), dim3((unsigned)blocks), dim3(WAVES * 64), lds, eng->stream, N, n1, n2, (u32)other, ck,
-                     (unsigned long long)first_item, (long)B, d_out, NW);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_sample_ternary<BIGN, WAVES, DR>, (B + WAVES * 64 - 1) / (WAVES * 64), WAVES * 64, lds, N, n1, n2, (u32)other,
+                         ck, (unsigned long long)first_item, (long)B, d_out, NW);
 }
 
 extern "C" int ntru_sample_ternary_dev(ntru_engine_t *eng, int N, int n1, int n2, int other, const uint32_t *key,

@@ -22,9 +22,7 @@
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned int v2u __attribute__((__vector_size__(2 * sizeof(unsigned int))));
-#ifndef ST_AUX
-#define ST_AUX 0     // cache policy bits of the result stores (0 measured best; 2 = non-temporal is 1.6x slower)
-#endif
+constexpr int ST_AUX = 0;   // cache policy bits of the result stores (0 measured best; 2 = non-temporal is 1.6x slower)
 
 struct MGeom {
   int N;        // ring size
@@ -318,9 +316,12 @@ static __device__ __forceinline__ v4i col_mask16(int c16, int N) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
+// Family 4 may run: kernel path 0 (auto) or a forced matrix-core path (4, 5); paths 1-3 force the vector-ALU families.
+static inline bool matrix_path_allowed(const ntru_engine *eng) { return eng->path == 0 || eng->path >= 4; }
+
 // Matrix-core path (family 4): shared key, q a power of two <= 8192 (two int8 digit planes), LDS for a 32-row block.
 static inline bool make_mgeom(const ntru_engine *eng, int N, int q, int ld, MGeom *g) {
-  if (eng->path != 0 && eng->path < 4) return false;
+  if (!matrix_path_allowed(eng)) return false;
   if (q > 8192 || N > 1024 || ld > 1024 || N < (eng->path >= 4 || ld != N ? 2 : 64)) return false;   // staging: lane = 16-byte chunk of a row
   g->N = N;
   g->ld = ld;
@@ -329,8 +330,5 @@ static inline bool make_mgeom(const ntru_engine *eng, int N, int q, int ld, MGeo
   g->tpitch = ((16 * g->NT + 31) / 32) * 32 + 8;
   return true;
 }
-
-
-static const char *const kMatrixLdsLimitNote = "160 KB of LDS per CU";
 
 #endif

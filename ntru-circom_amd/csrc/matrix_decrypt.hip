@@ -80,10 +80,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
   build_toeplitz_array(TF, g, [&](int i) { return (int)f[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   build_toeplitz_array(TP, g, [&](int i) { return (int)fp[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)mod_small(2 * x > q ? x + 1 : x, p);
-#ifndef NTRU_PHASE_MASK
-#define NTRU_PHASE_MASK 15       // which boundaries of the lock-step schedule are barriers (tuning experiments): 1 = product 1 loop | epilogue,
-#endif                           // 2 = product 1 epilogue | next loop, 4 / 8 = the same for product 2
-  auto phase = [&](int kind) { if (GROUPS == 2 && (NTRU_PHASE_MASK & kind)) __syncthreads(); };
+  auto phase = [&]() { if (GROUPS == 2) __syncthreads(); };   // a boundary of the lock-step schedule
   if (GROUPS == 2 && group == 1) __syncthreads();                   // group 1 runs one phase behind group 0
   const bool want_q1 = quot1 != nullptr, want_r1 = rem1 != nullptr, want_q2 = quot2 != nullptr;
   const long nrb = (B + 31) >> 5;
@@ -167,7 +164,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     for_each_strip<4>(g.NT, GROUPS == 2 ? wave ^ (2 * group) ^ (2 * blockIdx.x >= gridDim.x ? 2 : 0) : wave, [&](int kb0, int nt) {
       auto epi = [&](auto &lo, auto &hi) {
         constexpr int NTS = sizeof(lo) / sizeof(lo[0]);
-        phase(1);                                        // matrix loop | epilogue
+        phase();                                         // matrix loop | epilogue
         // descriptors are made here, from a re-materialised row-block base, so that they live in scalar registers only
         // while they are used (held across the matrix loops they are spilled to VGPRs and every store becomes a
         // waterfall loop)
@@ -215,14 +212,14 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
         else out(std::false_type{}, std::false_type{});
       };
       switch (nt) {
-        case 0: phase(1); break;                         // (the strip list hands out empty strips only to keep the phases in step)
+        case 0: phase(); break;                          // (the strip list hands out empty strips only to keep the phases in step)
         case 1: toeplitz_strip<M_DEC1, 1>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
         case 2: toeplitz_strip<M_DEC1, 2>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
         case 3: toeplitz_strip<M_DEC1, 3>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
         default: toeplitz_strip<M_DEC1, 4>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
       }
       sidx++;
-      if (sidx < rounds) phase(2);                       // epilogue | next matrix loop (after the last strip: the barrier below)
+      if (sidx < rounds) phase();                        // epilogue | next matrix loop (after the last strip: the barrier below)
     }, GROUPS == 2);
     __syncthreads();                                 // every wave is done with the e stages; packed image complete
     STAMP(8);
@@ -259,7 +256,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     for_each_strip<4>(g.NT, GROUPS == 2 ? wave ^ (2 * group) ^ (2 * blockIdx.x >= gridDim.x ? 2 : 0) : wave, [&](int kb0, int nt) {
       auto epi = [&](auto &lo, auto &hi) {
         constexpr int NTS = sizeof(lo) / sizeof(lo[0]);
-        phase(4);                                        // matrix loop | epilogue
+        phase();                                         // matrix loop | epilogue
         long bb = b0;                                    // see product 1
         asm volatile("" : "+s"(bb));
         const long lf = (B - bb) * LD;
@@ -304,14 +301,14 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
         if (want_q2) out(std::true_type{}); else out(std::false_type{});
       };
       switch (nt) {
-        case 0: phase(4); break;                         // no strip this round: keep the phases in step
+        case 0: phase(); break;                          // no strip this round: keep the phases in step
         case 1: toeplitz_strip<M_DEC2, 1>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
         case 2: toeplitz_strip<M_DEC2, 2>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
         case 3: toeplitz_strip<M_DEC2, 3>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
         default: toeplitz_strip<M_DEC2, 4>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
       }
       sidx++;
-      if (sidx < rounds) phase(8);
+      if (sidx < rounds) phase();                        // epilogue | next matrix loop
     }, GROUPS == 2);
   }
   if (GROUPS == 2 && group == 0) __syncthreads();     // group 1's last phase
@@ -358,14 +355,9 @@ int ntru_launch_decrypt_pack_matrix(ntru_engine *eng, int N, int q, int p, const
   // the 2-bit image of the values lives in the e_hi stage behind the mod-p tables
   const size_t m3_end = ((((size_t)4 * N + 4) & ~(size_t)3) + (size_t)4 * N + 1 + 15) & ~(size_t)15, img = ((size_t)8 * (126 * out_size + 16) + 15) & ~(size_t)15;
   if (lds > 160 * 1024 || m3_end + img > (size_t)32 * mg.pitchA || 126 * out_size + 16 < 32 * mg.NT) return NTRU_NOT_TAKEN;
-  const long nrb = (long)((B + 31) / 32);
-  dim3 grid;
-  if (int rc = resident_grid(eng, k_decrypt_mp, lds, nrb, &grid)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_mp");
-  hipLaunchKernelGGL(k_decrypt_mp, grid, dim3(BLOCK_THREADS), lds, eng->stream, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
-                     (unsigned long long *)d_packed, out_size);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_decrypt_mp, (long)((B + 31) / 32), BLOCK_THREADS, lds, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
+                         (unsigned long long *)d_packed, out_size);
 }
 
 // Kernel paths: 4 -> k_decrypt_m (two free-running workgroups per CU); 5 -> k_decrypt_m8 (one workgroup of two lock-step groups)
@@ -378,23 +370,16 @@ int ntru_launch_decrypt_matrix(ntru_engine *eng, int N, int q, int p, int ld, co
   if (p != 3 || !make_mgeom(eng, N, q, ld, &mg)) return NTRU_NOT_TAKEN;
   const size_t lds = (size_t)32 * mg.tpitch + (size_t)64 * mg.pitchA + (size_t)256 * mg.NT + (((size_t)q + 15) & ~(size_t)15);
   const long nrb = (long)((B + 31) / 32);
-  dim3 grid;
   if (eng->path == 5 || (eng->path == 0 && mg.NT > 16 && d_quot1 && d_rem1 && d_quot2)) {
     const size_t lds8 = 2 * ((size_t)64 * mg.pitchA + (size_t)256 * mg.NT) + (size_t)32 * mg.tpitch + (((size_t)q + 15) & ~(size_t)15);
     if (lds8 <= 160 * 1024) {
-      if (int rc = resident_grid(eng, k_decrypt_m8, lds8, (nrb + 1) / 2, &grid, 2 * BLOCK_THREADS)) return rc;
       snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m8");
-      hipLaunchKernelGGL(k_decrypt_m8, grid, dim3(2 * BLOCK_THREADS), lds8, eng->stream, mg, (u32)q, (u32)p, d_f, d_fp, d_e,
-                         (long)B, d_value, d_quot1, d_rem1, d_quot2);
-      HIP_TRY(hipGetLastError());
-      return NTRU_OK;
+      return launch_resident(eng, k_decrypt_m8, (nrb + 1) / 2, 2 * BLOCK_THREADS, lds8, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B,
+                             d_value, d_quot1, d_rem1, d_quot2);
     }
   }
   if (lds > 160 * 1024) return NTRU_NOT_TAKEN;
-  if (int rc = resident_grid(eng, k_decrypt_m, lds, nrb, &grid)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m");
-  hipLaunchKernelGGL(k_decrypt_m, grid, dim3(BLOCK_THREADS), lds, eng->stream, mg, (u32)q, (u32)p, d_f, d_fp, d_e,
-                     (long)B, d_value, d_quot1, d_rem1, d_quot2);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_decrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value, d_quot1,
+                         d_rem1, d_quot2);
 }

@@ -292,7 +292,6 @@ int ntru_launch_encrypt_matrix(ntru_engine *eng, int N, int q, int ld, const uin
   if (!make_mgeom(eng, N, q, ld, &mg)) return NTRU_NOT_TAKEN;
   const size_t lds = (size_t)32 * mg.tpitch + (size_t)32 * mg.pitchA + (((size_t)32 * ld + 15) & ~(size_t)15) + 16;
   const long nrb = (long)((B + 31) / 32);
-  dim3 grid;
   if (lds > 160 * 1024) return NTRU_NOT_TAKEN;
   // The default: the operands reach LDS by direct-to-LDS loads, r of the next row block ahead of the last epilogue's stores:
   // 1.49-1.51 ms against 1.57-1.62 ms per 2^20 at N = 821 on the same device (profiles/archive/r02_ab_direct_to_lds_rows.txt).
@@ -302,16 +301,7 @@ int ntru_launch_encrypt_matrix(ntru_engine *eng, int N, int q, int ld, const uin
   // staging fetches the extra dword.
   const bool rows_dword_aligned = (ld & 3) == 0 && ((uintptr_t)d_r & 3) == 0, img_dword_aligned = (ld & 3) == 0 && ((uintptr_t)d_m & 3) == 0;
   const bool dma_fits = (N + 3 <= 1024 || (rows_dword_aligned && N <= 1024)) && (32 * ld + 3 <= 32768 || (img_dword_aligned && 32 * ld <= 32768));
-  if (eng->path != 4 && dma_fits) {
-    if (int rc = resident_grid(eng, k_encrypt_md, lds, nrb, &grid)) return rc;
-    snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_encrypt_md");
-    hipLaunchKernelGGL(k_encrypt_md, grid, dim3(BLOCK_THREADS), lds, eng->stream, mg, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
-  }
-  if (int rc = resident_grid(eng, k_encrypt_m, lds, nrb, &grid)) return rc;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_encrypt_m");
-  hipLaunchKernelGGL(k_encrypt_m, grid, dim3(BLOCK_THREADS), lds, eng->stream, mg, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  const bool md = eng->path != 4 && dma_fits;
+  snprintf(eng->last_kernel, sizeof eng->last_kernel, md ? "k_encrypt_md" : "k_encrypt_m");
+  return launch_resident(eng, md ? k_encrypt_md : k_encrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
 }

@@ -925,32 +925,17 @@ static PGeom make_pgeom(int N) {
 }
 // The per-item matrix kernels: modulus a power of two <= 8192 (two int8 digit planes), 64 <= N <= 1024; automatic from N = 128.
 static bool peritem_applies(const ntru_engine *eng, int N, int q) {
-  return (eng->path == 0 || eng->path >= 4) && is_pow2(q) && q <= 8192 && N <= 1024 && N >= (eng->path >= 4 ? 64 : 128);
-}
-template <class Kern>
-static int peritem_grid(ntru_engine *eng, Kern kern, size_t lds, long B, dim3 *grid) {
-  int per_cu = 0;
-  if (int rc = ntru_blocks_per_cu(eng, (const void *)kern, 64 * PI_WAVES, lds, &per_cu)) return rc;
-  if (eng->max_blocks_per_cu && eng->max_blocks_per_cu < per_cu) per_cu = eng->max_blocks_per_cu;     // NTRU_MAX_BLOCKS_PER_CU (experiments)
-  long blocks = (long)eng->cus * (per_cu < 1 ? 1 : per_cu), work = (B + PI_WAVES - 1) / PI_WAVES;
-  if (blocks > work) blocks = work;
-  *grid = dim3((unsigned)blocks);
-  return NTRU_OK;
+  return matrix_path_allowed(eng) && is_pow2(q) && q <= 8192 && N <= 1024 && N >= (eng->path >= 4 ? 64 : 128);
 }
 
 int ntru_launch_polymul_matrix(ntru_engine *eng, int N, int mod, const uint16_t *d_a, const uint16_t *d_b, int64_t B, uint16_t *d_quot,
                                uint16_t *d_rem) {
   if (!peritem_applies(eng, N, mod)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
-  dim3 grid;
-  auto go = [&](auto kern, size_t lds) -> int {
-    if (int rc = peritem_grid(eng, kern, lds, (long)B, &grid)) return rc;
-    snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_polymul_m");
-    hipLaunchKernelGGL(kern, grid, dim3(64 * PI_WAVES), lds, eng->stream, pg, (u32)mod, d_a, d_b, (long)B, d_quot, d_rem);
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
-  };
-  return mod <= 256 ? go(k_polymul_m<true>, PI_WAVES * pi_reg_wave_bytes(pg)) : go(k_polymul_m<false>, PI_WAVES * pi_reg_wave_bytes2(pg));
+  const bool one = mod <= 256;
+  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_polymul_m");
+  return launch_resident(eng, one ? k_polymul_m<true> : k_polymul_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
+                         PI_WAVES * (one ? pi_reg_wave_bytes(pg) : pi_reg_wave_bytes2(pg)), pg, (u32)mod, d_a, d_b, (long)B, d_quot, d_rem);
 }
 
 bool ntru_product_tern_matrix_applies(const ntru_engine *eng, int N, int q) { return peritem_applies(eng, N, q); }
@@ -958,14 +943,8 @@ bool ntru_product_tern_matrix_applies(const ntru_engine *eng, int N, int q) { re
 int ntru_launch_product_tern_matrix(ntru_engine *eng, int N, int q, uint32_t mul, const uint16_t *d_a, const int8_t *d_s, long B,
                                     uint16_t *d_rem) {
   const PGeom pg = make_pgeom(N);
-  dim3 grid;
-  auto go = [&](auto kern, size_t lds) -> int {
-    if (int rc = peritem_grid(eng, kern, lds, B, &grid)) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * PI_WAVES), lds, eng->stream, pg, (u32)q, (u32)mul, d_a, d_s, B, d_rem);
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
-  };
-  return q <= 256 ? go(k_product_tern_m<true>, PI_WAVES * pi_reg_wave_bytes(pg)) : go(k_product_tern_m<false>, PI_WAVES * pi_reg_wave_bytes(pg));
+  return launch_resident(eng, q <= 256 ? k_product_tern_m<true> : k_product_tern_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
+                         PI_WAVES * pi_reg_wave_bytes(pg), pg, (u32)q, (u32)mul, d_a, d_s, B, d_rem);
 }
 
 int ntru_launch_verify_keys_matrix(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, const int8_t *d_g, const uint16_t *d_fq,
@@ -973,14 +952,9 @@ int ntru_launch_verify_keys_matrix(ntru_engine *eng, int N, int q, int p, const 
                                    uint8_t *d_quot_fp, uint8_t *d_rem_fp, uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags) {
   if (p != 3 || !peritem_applies(eng, N, q)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
-  const size_t lds = PI_WAVES * pi_verify_wave_bytes(pg);
-  dim3 grid;
-  if (int rc = peritem_grid(eng, k_verify_keys_m, lds, (long)B, &grid)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_verify_keys_m");
-  hipLaunchKernelGGL(k_verify_keys_m, grid, dim3(64 * PI_WAVES), lds, eng->stream, pg, (u32)q, d_f, d_g, d_fq, d_fp, d_h, (long)B,
-                     d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_verify_keys_m, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES, PI_WAVES * pi_verify_wave_bytes(pg), pg,
+                         (u32)q, d_f, d_g, d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
 }
 
 
@@ -991,12 +965,8 @@ bool ntru_newton_round_matrix_applies(const ntru_engine *eng, int N, int kb, int
 int ntru_launch_newton_round_matrix(ntru_engine *eng, int N, int kb, int m, const int8_t *d_f, uint16_t *d_v, long B) {
   if (!ntru_newton_round_matrix_applies(eng, N, kb, m)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
-  const size_t lds = PI_WAVES * pi_reg_wave_bytes(pg);
-  dim3 grid;
-  if (int rc = peritem_grid(eng, k_newton_round_m, lds, B, &grid)) return rc;
-  hipLaunchKernelGGL(k_newton_round_m, grid, dim3(64 * PI_WAVES), lds, eng->stream, pg, (u32)kb, (u32)m, d_f, d_v, B);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
+  return launch_resident(eng, k_newton_round_m, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES, PI_WAVES * pi_reg_wave_bytes(pg), pg, (u32)kb,
+                         (u32)m, d_f, d_v, B);
 }
 
 #ifdef NTRU_STAMPS

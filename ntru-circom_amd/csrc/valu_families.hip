@@ -1463,7 +1463,7 @@ static Geom make_geom(int N, int K) {
   return g;
 }
 
-struct Launch { Geom g; int K; dim3 grid; size_t lds; };
+struct Launch { Geom g; int K; long blocks; size_t lds; };   // blocks: work blocks, capped to residency by launch_resident()
 
 // shared_eo: number of EO arrays shared by the workgroup; per_item_eo: whether each item also needs its own EO array.
 static int plan(const ntru_engine *eng, int N, long B, int shared_eo, bool per_item_eo, Launch *L) {
@@ -1475,10 +1475,8 @@ static int plan(const ntru_engine *eng, int N, long B, int shared_eo, bool per_i
   size_t per_wave = (size_t)L->g.G * ((size_t)L->g.a_len * 4 + (per_item_eo ? (size_t)L->g.eo_len * 8 + raw_len * 2 : 0));
   L->lds = (size_t)shared_eo * L->g.eo_len * 8 + WAVES_PER_BLOCK * per_wave;
   if (L->lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "parameter set needs more than 160 KiB of LDS");
-  long ngroups = (B + L->g.G - 1) / L->g.G;
-  long blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-  if (blocks < 1) blocks = 1;                   // work blocks; capped to residency by resident_grid()
-  L->grid = dim3((unsigned)blocks);
+  const long ngroups = (B + L->g.G - 1) / L->g.G;
+  L->blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
   return NTRU_OK;
 }
 
@@ -1501,9 +1499,7 @@ static int plan_add(const ntru_engine *eng, int N, long B, size_t shared_bytes, 
   L->g = make_geom(N, L->K);
   L->lds = shared_bytes + WAVES_PER_BLOCK * per_wave_bytes;
   if (L->lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "parameter set needs more than 160 KiB of LDS");
-  long blocks = (B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-  if (blocks < 1) blocks = 1;
-  L->grid = dim3((unsigned)blocks);
+  L->blocks = (B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
   return NTRU_OK;
 }
 
@@ -1546,10 +1542,6 @@ static int shared_path_K(const ntru_engine *eng, int N, int q, int p, int *me) {
     default: return fail(NTRU_ERR_UNSUPPORTED, "no add-path kernel for this (K, mask interval)");   \
   }
 
-// The dynamic-LDS limit of a kernel is raised at its first use, inside ntru_blocks_per_cu (resident_grid).
-template <class Kern>
-static int allow_lds(Kern, size_t) { return NTRU_OK; }
-
 #define DISPATCH_K(Kv, ...)                                                                       \
   switch (Kv) {                                                                                     \
     case 1: { constexpr int KK = 1; __VA_ARGS__; } break;                                                  \
@@ -1570,25 +1562,15 @@ int ntru_launch_encrypt_valu(ntru_engine *eng, int N, int q, const uint16_t *d_h
     Geom g0 = make_geom(N, pick_K(N));
     if (int rc = plan_add(eng, N, B, (size_t)g0.eo_len * 8, (size_t)g0.nl * 4, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
-      if (int rc = allow_lds(k_encrypt_t<KK, MM>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_encrypt_t<KK, MM>, L.lds, (long)L.grid.x, &L.grid)) return rc;
       note_kernel(eng, "k_encrypt_t", KK, MM);
-      hipLaunchKernelGGL((k_encrypt_t<KK, MM>), L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q,
-                         d_h, d_r, d_m, (long)B, d_e, d_quotE);
+      return launch_resident(eng, k_encrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
     });
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
   }
   if (int rc = plan(eng, N, B, 1, false, &L)) return rc;
   DISPATCH_K(L.K, {
-    if (int rc = allow_lds(k_encrypt<KK>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_encrypt<KK>, L.lds, (long)L.grid.x, &L.grid)) return rc;
     note_kernel(eng, "k_encrypt", KK, -1);
-    hipLaunchKernelGGL(k_encrypt<KK>, L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, d_h, d_r, d_m,
-                       (long)B, d_e, d_quotE);
+    return launch_resident(eng, k_encrypt<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
   });
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
 }
 
 int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp, const uint16_t *d_e,
@@ -1605,17 +1587,12 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
       // product 2 on v_dot8 needs the 32-lane item layout (and is skipped when the MAC/add families are forced apart)
       const int d8 = (L.g.nl == 32 && eng->path != 3) ? 1 : 0;
       const long ngroups = (B + L.g.G - 1) / L.g.G;
-      long blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-      L.grid = dim3((unsigned)(blocks < 1 ? 1 : blocks));
+      L.blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
       DISPATCH_K_SHARED(KS, me, d8, {
-        if (int rc = allow_lds(k_decrypt_s<KK, MM, DD>, L.lds)) return rc;
-        if (int rc = resident_grid(eng, k_decrypt_s<KK, MM, DD>, L.lds, (long)L.grid.x, &L.grid)) return rc;
         note_kernel(eng, DD ? "k_decrypt_s+dot8" : "k_decrypt_s", KK, MM);
-        hipLaunchKernelGGL((k_decrypt_s<KK, MM, DD>), L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, (u32)p,
-                           d_f, d_fp, d_e, (long)B, d_value, d_quot1, d_rem1, d_quot2);
+        return launch_resident(eng, k_decrypt_s<KK, MM, DD>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B,
+                               d_value, d_quot1, d_rem1, d_quot2);
       });
-      HIP_TRY(hipGetLastError());
-      return NTRU_OK;
     }
   }
   if (const int me = (p == 3 && eng->path == 2) ? add_path_me(eng, N, q) : 0) {   // per-item stepping: only when forced
@@ -1623,25 +1600,17 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
     if (int rc = plan_add(eng, N, B, (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4,
                           (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
-      if (int rc = allow_lds(k_decrypt_t<KK, MM>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_decrypt_t<KK, MM>, L.lds, (long)L.grid.x, &L.grid)) return rc;
       note_kernel(eng, "k_decrypt_t", KK, MM);
-      hipLaunchKernelGGL((k_decrypt_t<KK, MM>), L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, (u32)p,
-                         d_f, d_fp, d_e, (long)B, d_value, d_quot1, d_rem1, d_quot2);
+      return launch_resident(eng, k_decrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
+                             d_quot1, d_rem1, d_quot2);
     });
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
   }
   if (int rc = plan(eng, N, B, 2, false, &L)) return rc;
   DISPATCH_K(L.K, {
-    if (int rc = allow_lds(k_decrypt<KK>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_decrypt<KK>, L.lds, (long)L.grid.x, &L.grid)) return rc;
     note_kernel(eng, "k_decrypt", KK, -1);
-    hipLaunchKernelGGL(k_decrypt<KK>, L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, (u32)p, d_f, d_fp,
-                       d_e, (long)B, d_value, d_quot1, d_rem1, d_quot2);
+    return launch_resident(eng, k_decrypt<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value, d_quot1,
+                           d_rem1, d_quot2);
   });
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
 }
 
 int ntru_launch_polymul_valu(ntru_engine *eng, int N, int mod, const uint16_t *d_a, const uint16_t *d_b, int64_t B, uint16_t *d_quot,
@@ -1649,14 +1618,10 @@ int ntru_launch_polymul_valu(ntru_engine *eng, int N, int mod, const uint16_t *d
   Launch L;
   if (int rc = plan(eng, N, B, 0, true, &L)) return rc;
   DISPATCH_K(L.K, {
-    if (int rc = allow_lds(k_polymul_split<KK>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_polymul_split<KK>, L.lds, (long)L.grid.x, &L.grid)) return rc;
     note_kernel(eng, "k_polymul_split", KK, -1);
-    hipLaunchKernelGGL(k_polymul_split<KK>, L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)mod,
-                       (int)is_pow2(mod), d_a, d_b, (long)B, d_quot, d_rem);
+    return launch_resident(eng, k_polymul_split<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)mod, (int)is_pow2(mod), d_a, d_b, (long)B,
+                           d_quot, d_rem, 1u);
   });
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
 }
 
 int ntru_launch_public_key_valu(ntru_engine *eng, int N, int q, int p, const uint16_t *d_fq, const int8_t *d_g, int64_t B,
@@ -1664,14 +1629,10 @@ int ntru_launch_public_key_valu(ntru_engine *eng, int N, int q, int p, const uin
   Launch L;
   if (int rc = plan(eng, N, B, 0, true, &L)) return rc;
   DISPATCH_K(L.K, {
-    if (int rc = allow_lds((k_polymul_split<KK, true>), L.lds)) return rc;
-    if (int rc = resident_grid(eng, (k_polymul_split<KK, true>), L.lds, (long)L.grid.x, &L.grid)) return rc;
     note_kernel(eng, "k_public_key", KK, -1);
-    hipLaunchKernelGGL((k_polymul_split<KK, true>), L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, 1,
-                       (const u16 *)d_g, d_fq, (long)B, (u16 *)nullptr, d_h, (u32)p);
+    return launch_resident(eng, k_polymul_split<KK, true>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, 1, (const u16 *)d_g, d_fq, (long)B,
+                           (u16 *)nullptr, d_h, (u32)p);
   });
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
 }
 
 int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, const int8_t *d_g, const uint16_t *d_fq,
@@ -1679,31 +1640,20 @@ int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int p, const in
                                  uint8_t *d_quot_fp, uint8_t *d_rem_fp, uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags) {
   Launch L;
   if (const int me = p == 3 ? add_path_me(eng, N, q) : 0) {
-    L.K = pick_K(N);
-    L.g = make_geom(N, L.K);
+    Geom g0 = make_geom(N, pick_K(N));
     const size_t raw_len = ((size_t)N + 1) & ~(size_t)1;
-    L.lds = WAVES_PER_BLOCK * ((size_t)L.g.eo_len * 8 + (size_t)L.g.nl * 4 + raw_len * 2);
-    L.grid = dim3((unsigned)((B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK));
+    if (int rc = plan_add(eng, N, B, 0, (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4 + raw_len * 2, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
-      if (int rc = allow_lds(k_verify_keys_t<KK, MM>, L.lds)) return rc;
-      if (int rc = resident_grid(eng, k_verify_keys_t<KK, MM>, L.lds, (long)L.grid.x, &L.grid)) return rc;
       note_kernel(eng, "k_verify_keys_t", KK, MM);
-      hipLaunchKernelGGL((k_verify_keys_t<KK, MM>), L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, (u32)p,
-                         d_f, d_g, d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h,
-                         d_flags);
+      return launch_resident(eng, k_verify_keys_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_g, d_fq, d_fp, d_h,
+                             (long)B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
     });
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
   }
   if (int rc = plan(eng, N, B, 0, true, &L)) return rc;
   DISPATCH_K(L.K, {
-    if (int rc = allow_lds(k_verify_keys<KK>, L.lds)) return rc;
-    if (int rc = resident_grid(eng, k_verify_keys<KK>, L.lds, (long)L.grid.x, &L.grid)) return rc;
     note_kernel(eng, "k_verify_keys", KK, -1);
-    hipLaunchKernelGGL(k_verify_keys<KK>, L.grid, dim3(BLOCK_THREADS), L.lds, eng->stream, L.g, (u32)q, (u32)p, d_f, d_g,
-                       d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
+    return launch_resident(eng, k_verify_keys<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_g, d_fq, d_fp, d_h, (long)B,
+                           d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
   });
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
 }
 

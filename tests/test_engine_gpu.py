@@ -236,11 +236,10 @@ def test_kernel_families_agree(eng):
         h = rng.integers(0, q, N); fp = rng.integers(0, 3, N)
         f = ternary_rows(rng, 1, N, d, d - 1, two=-1)[0]
         r = ternary_rows(rng, 9, N, d, d); m = rng.integers(0, 2, (9, N))
-        outs, names = [], []
+        outs = []
         for path in (1, 2, 3, 4, 5, 0):
             eng.set_kernel_path(path)
             e, quot = eng.encrypt_batch(N, q, h, r, m)
-            names.append(eng.last_kernel() if False else None)
             dec = eng.decrypt_batch(N, q, 3, f, fp, e)
             outs.append((e, quot) + dec)
         eng.set_kernel_path(0)
