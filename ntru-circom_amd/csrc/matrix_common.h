@@ -32,7 +32,9 @@ struct MGeom {
   int ld;       // row pitch of every batch array in ELEMENTS (>= N; N for the dense layout of the plain entry points)
 };
 
-enum { M_ENC = 0, M_DEC1 = 1, M_DEC2 = 2 };
+// M_DEC1: product 1 of decrypt, the 64 f plane derived from the f fragment; M_DEC1T: the same product with the 64 f plane read
+// from a reversed key array of its own (tb1), as M_ENC reads its second plane.
+enum { M_ENC = 0, M_DEC1 = 1, M_DEC2 = 2, M_DEC1T = 3 };
 
 // -DNTRU_STAMPS: diagnostic build that records s_memtime at the phase boundaries of the matrix-core kernels for the
 // first row blocks of each workgroup (tools/phase_stamps.py reads them back); no stamp executes in the shipped library.
@@ -105,7 +107,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
   auto load_w = [&](int d, v4i &w0, v4i &w1) {
     const u32 *p = tb0 - 8 * d;
     w0 = (v4i){(int)p[0], (int)p[1], (int)p[2], (int)p[3]};
-    if (MODE == M_ENC) {
+    if (MODE == M_ENC || MODE == M_DEC1T) {
       const u32 *p1 = tb1 - 8 * d;
       w1 = (v4i){(int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
     } else if (MODE == M_DEC1) {                       // 64 f from f in {-1,0,1} (0xFF, 0, 1): the two low bits of every
@@ -120,7 +122,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
     if (MODE == M_ENC) {                               // 32 r: r <= 3, no carry between bytes
 #pragma unroll
       for (int c = 0; c < 4; c++) a1[c] = (int)((u32)a0[c] << 5);
-    } else if (MODE == M_DEC1) {
+    } else if (MODE == M_DEC1 || MODE == M_DEC1T) {
       a1 = *(const v4i *)(st1 + 32 * ib);
     } else {
       a1 = a0;

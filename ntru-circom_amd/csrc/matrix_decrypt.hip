@@ -10,7 +10,7 @@
 // LDS image [column][8 bytes] and one expansion pass.
 // GROUPS = 1: one workgroup = four waves = one row block at a time, two workgroups per CU (k_decrypt_m).
 // GROUPS = 2 (k_decrypt_m8): ONE workgroup of eight waves per CU = two groups of four, each with its own row blocks, stages and
-// packed image, sharing the key arrays and the lift table.  Every matrix loop and every epilogue is a PHASE between two
+// packed image, sharing the key arrays, the lift table and the mod-p tables.  Every matrix loop and every epilogue is a PHASE between two
 // workgroup barriers, and group 1 runs one phase behind group 0: while one group's waves are in their matrix loops, the
 // other group's waves (their partners on the SIMDs) are in an epilogue / staging phase, by construction instead of by
 // luck.  Phases per row block: stage, then (loop, epilogue) per strip and product, with the image expansion between the
@@ -32,15 +32,22 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
                                                       unsigned long long *__restrict__ packed = nullptr, int pack_os = 0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int group = GROUPS == 2 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;
-  // LDS layout: per group [e_hi stage][e_lo stage][packed image], then the shared key arrays and the lift table.  Group 0's
-  // e_hi stage is at LDS address 0: the mod-p tables of product 2 are overlaid on it and their lookups need no base add.
+  // LDS layout: per group [e_hi stage][e_lo stage][packed image], then the shared key arrays and the lift table.  The mod-p
+  // tables of product 2 are at LDS address 0, so that their lookups need no base add: GROUPS = 1 overlays them on the e_hi
+  // stage and rebuilds them per row block; GROUPS = 2 builds them once, in a region of their own in front of the groups'.
   static_assert(!PACK || GROUPS == 1, "fused packOutput is built on the plain four-wave kernel");
+  // mod-p tables of product 2: (-x) mod p at LDS address x, so that the quotient lookup's address IS the `high` accumulator;
+  // x mod p at M3V + x, the base folded into the low + high add
+  const int M3V = __builtin_amdgcn_readfirstlane(((int)((p - 1) * (p - 1)) * g.N + 4) & ~3);
+  const int m3_bytes = GROUPS == 2 ? (M3V + (int)((p - 1) * (p - 1)) * g.N + 1 + 15) & ~15 : 0;
   const int gbytes = 64 * g.pitchA + 256 * g.NT;
-  unsigned char *stHi = lds + group * gbytes;
+  // (one wave-uniform offset: as two adds, this base costs the lock-step kernel six more SGPR spills)
+  unsigned char *stHi = lds + (GROUPS == 2 ? __builtin_amdgcn_readfirstlane(m3_bytes + group * gbytes) : 0);
   unsigned char *stLo = stHi + 32 * g.pitchA;
   unsigned char *blp = stLo + 32 * g.pitchA;             // [8 row groups][32 NT columns]: 4 rows x 2 bits per byte
-  u32 *TF = (u32 *)(lds + GROUPS * gbytes), *TP = TF + 4 * g.tpitch;
-  unsigned char *lift_lut = (unsigned char *)(TP + 4 * g.tpitch);   // [q]: centred lift followed by mod p, index.js:117 verbatim
+  // GROUPS = 2 keeps a third key array, TF64 = the 64 f plane of product 1 (the four-wave kernels derive it from f in the loop)
+  u32 *TF = (u32 *)(lds + m3_bytes + GROUPS * gbytes), *TP = TF + 4 * g.tpitch, *TF64 = TP + 4 * g.tpitch;
+  unsigned char *lift_lut = (unsigned char *)(TP + 4 * g.tpitch * GROUPS);   // [q]: centred lift followed by mod p, index.js:117 verbatim
   // PACK: 2-bit image of product 2's values, [8 row groups][pcols] bytes, pcols = 126 pack_os + 16 >= 32 NT (zero beyond N).  It lives
   // in the e_hi stage behind the mod-p tables (dead between product 1's last loop and the next trip's staging: no LDS of its own --
   // 7 KB more would cost the second workgroup of the CU); it is turned into packed dwords at the top of the next trip, and a barrier
@@ -72,14 +79,21 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
   auto pack_wipe = [&]() {                               // the staging of product 1 has been here since: columns >= N must read zero again
     for (int x = (int)threadIdx.x; x < pimg_bytes / 16; x += BLOCK_THREADS) *(uint4 *)(pimg + 16 * x) = make_uint4(0u, 0u, 0u, 0u);
   };
-  // mod-p tables of product 2, rebuilt per row block once the e stages are dead: (-x) mod p at LDS address x, so that
-  // the quotient lookup's address IS the `high` accumulator; x mod p at M3V + x, the base folded into the low + high add
-  const int M3V = __builtin_amdgcn_readfirstlane(((int)((p - 1) * (p - 1)) * g.N + 4) & ~3);   // both tables inside the e_hi stage
-  unsigned char *m3_lut = stHi;
+  unsigned char *m3_lut = lds;
+  auto build_m3 = [&](int tid, int nthr, int n) {
+    for (int x = tid; x <= (int)((p - 1) * (p - 1)) * n; x += nthr) {
+      const u32 rm = mod_small((u32)x, p);
+      m3_lut[x] = (unsigned char)(rm ? p - rm : 0u);
+      m3_lut[M3V + x] = (unsigned char)rm;
+    }
+  };
   const int tid0 = threadIdx.x & (BLOCK_THREADS - 1), lane0 = tid0 & 63, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   build_toeplitz_array(TF, g, [&](int i) { return (int)f[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   build_toeplitz_array(TP, g, [&](int i) { return (int)fp[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
+  if (GROUPS == 2)   // 64 f: the two low bits of every digit of f in bits 6-7 (f in {-1,0,1}: 0xC0, 0, 0x40)
+    build_toeplitz_array(TF64, g, [&](int i) { return (int)(((u32)f[i] << 6) & 0xC0u); }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)mod_small(2 * x > q ? x + 1 : x, p);
+  if (GROUPS == 2) build_m3((int)threadIdx.x, GROUPS * BLOCK_THREADS, g.N);
   auto phase = [&]() { if (GROUPS == 2) __syncthreads(); };   // a boundary of the lock-step schedule
   if (GROUPS == 2 && group == 1) __syncthreads();                   // group 1 runs one phase behind group 0
   const bool want_q1 = quot1 != nullptr, want_r1 = rem1 != nullptr, want_q2 = quot2 != nullptr;
@@ -99,6 +113,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     int lane = lane0, N = g.N, LD = g.ld;                // see k_encrypt_m
     asm volatile("" : "+v"(lane), "+s"(N), "+s"(LD));
     const u32 *tbf = frag_lane_base(TF, g, lane), *tbp = frag_lane_base(TP, g, lane);
+    const u32 *tbf64 = GROUPS == 2 ? frag_lane_base(TF64, g, lane) : tbf;
 
     const unsigned char *st0 = stLo + (lane & 31) * g.pitchA + 16 * (lane >> 5);
     const unsigned char *st1 = stHi + (lane & 31) * g.pitchA + 16 * (lane >> 5);
@@ -161,6 +176,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     const int lane_off = (lane >> 5) * 4 * LD + (lane & 31);
     // ---- product 1: a = f * e mod q; witness stores; lifted message -> packed image
     sidx = 0;
+    constexpr int P1 = GROUPS == 2 ? M_DEC1T : M_DEC1;
     for_each_strip<4>(g.NT, GROUPS == 2 ? wave ^ (2 * group) ^ (2 * blockIdx.x >= gridDim.x ? 2 : 0) : wave, [&](int kb0, int nt) {
       auto epi = [&](auto &lo, auto &hi) {
         constexpr int NTS = sizeof(lo) / sizeof(lo[0]);
@@ -213,10 +229,10 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
       };
       switch (nt) {
         case 0: phase(); break;                          // (the strip list hands out empty strips only to keep the phases in step)
-        case 1: toeplitz_strip<M_DEC1, 1>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
-        case 2: toeplitz_strip<M_DEC1, 2>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
-        case 3: toeplitz_strip<M_DEC1, 3>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
-        default: toeplitz_strip<M_DEC1, 4>(st0, st1, tbf, tbf, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
+        case 1: toeplitz_strip<P1, 1>(st0, st1, tbf, tbf64, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
+        case 2: toeplitz_strip<P1, 2>(st0, st1, tbf, tbf64, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
+        case 3: toeplitz_strip<P1, 3>(st0, st1, tbf, tbf64, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
+        default: toeplitz_strip<P1, 4>(st0, st1, tbf, tbf64, g, kb0, mlow, epi, stamp_iter, 4 + 2 * sidx); break;
       }
       sidx++;
       if (sidx < rounds) phase();                        // epilogue | next matrix loop (after the last strip: the barrier below)
@@ -224,11 +240,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     __syncthreads();                                 // every wave is done with the e stages; packed image complete
     STAMP(8);
     if (PACK) pack_wipe();
-    for (int x = tid0; x <= (int)((p - 1) * (p - 1)) * N; x += BLOCK_THREADS) {
-      const u32 rm = mod_small((u32)x, p);
-      m3_lut[x] = (unsigned char)(rm ? p - rm : 0u);
-      m3_lut[M3V + x] = (unsigned char)rm;
-    }
+    if (GROUPS == 1) build_m3(tid0, BLOCK_THREADS, N);     // the e stages are dead: the tables go over the e_hi stage
     {   // packed image -> byte stage: all of a wave's reads in flight before the first write (as a read-write loop this
         // pass was one LDS round trip per dword: 7 k cycles per row block in the phase stamps)
       constexpr int RPW = 32 / WAVES_PER_BLOCK;
@@ -371,7 +383,9 @@ int ntru_launch_decrypt_matrix(ntru_engine *eng, int N, int q, int p, int ld, co
   const size_t lds = (size_t)32 * mg.tpitch + (size_t)64 * mg.pitchA + (size_t)256 * mg.NT + (((size_t)q + 15) & ~(size_t)15);
   const long nrb = (long)((B + 31) / 32);
   if (eng->path == 5 || (eng->path == 0 && mg.NT > 16 && d_quot1 && d_rem1 && d_quot2)) {
-    const size_t lds8 = 2 * ((size_t)64 * mg.pitchA + (size_t)256 * mg.NT) + (size_t)32 * mg.tpitch + (((size_t)q + 15) & ~(size_t)15);
+    // two groups' stages and images, the mod-p tables of product 2, three key arrays (f, fp, 64 f), the lift table
+    const size_t m3 = ((((size_t)4 * N + 4) & ~(size_t)3) + (size_t)4 * N + 1 + 15) & ~(size_t)15;
+    const size_t lds8 = 2 * ((size_t)64 * mg.pitchA + (size_t)256 * mg.NT) + m3 + (size_t)48 * mg.tpitch + (((size_t)q + 15) & ~(size_t)15);
     if (lds8 <= 160 * 1024) {
       snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m8");
       return launch_resident(eng, k_decrypt_m8, (nrb + 1) / 2, 2 * BLOCK_THREADS, lds8, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B,
