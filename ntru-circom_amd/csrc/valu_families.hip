@@ -650,10 +650,13 @@ static __device__ __forceinline__ void tern_core(const uint2 *__restrict__ eo, c
 }
 
 // T = S1 + c*S2 per 16-bit field, as a u16 pair (mod 2^16 from here on).  NEG: c = -1 (mod q), else c = 2.
+// c = 2 adds as u16 pairs: at q = 32768 a field's S1 + 2 S2 reaches 3 (q - 1) > 65535, and a 32-bit add would carry
+// into the odd coefficient's field.  S1 + q - S2 <= 2q - 1 never does.
 template <bool NEG>
 static __device__ __forceinline__ u16x2 tern_combine(u32 s1, u32 s2, u32 fmask, u32 qq) {
   s1 &= fmask; s2 &= fmask;
-  return as_pair(NEG ? s1 + (qq - s2) : s1 + (s2 << 1));
+  if constexpr (NEG) return as_pair(s1 + (qq - s2));
+  else return as_pair(s1) + as_pair(s2) + as_pair(s2);
 }
 
 // Finish one ternary-stepped product: remainder / quotient pairs like product_split.
@@ -1584,8 +1587,9 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
       const size_t per_wave = (size_t)L.g.G * (L.g.eo_len + 2) * 4;
       const int nblk8 = ((N + 31) >> 5) << 2;
       L.lds = (size_t)L.g.nl * 16 + (size_t)L.g.nl * KS * 8 + (size_t)nblk8 * 4 + WAVES_PER_BLOCK * per_wave;
-      // product 2 on v_dot8 needs the 32-lane item layout (and is skipped when the MAC/add families are forced apart)
-      const int d8 = (L.g.nl == 32 && eng->path != 3) ? 1 : 0;
+      // product 2 on v_dot8 needs the 32-lane item layout (and is skipped when the MAC/add families are forced apart); it is
+      // instantiated for K >= 11 only, so K = 9 at nl == 32 (odd N 559..575) keeps the plain second product
+      const int d8 = (L.g.nl == 32 && KS >= 11 && eng->path != 3) ? 1 : 0;
       const long ngroups = (B + L.g.G - 1) / L.g.G;
       L.blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
       DISPATCH_K_SHARED(KS, me, d8, {

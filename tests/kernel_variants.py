@@ -1,0 +1,166 @@
+"""Every kernel instantiation the library compiles, with a call that launches it.
+
+Plain data, imported by tests/test_build_quality.py (every compiled instantiation has a row and every row names one) and by
+tests/test_kernel_variants_gpu.py (each row's calls against the oracle, and the dispatch sweep).  Not a test module.
+
+A row:
+  kernel  the demangled instantiation as `c++filt` prints it, return type and argument list dropped ("k_decrypt_s<11, 11, true>")
+  entry   the C-ABI entry point whose launcher selects it (the name without the ntru_ prefix and the _batch[_dev] suffix)
+  shapes  calls that select it: dicts of N, q, p, path (ntru_engine_set_kernel_path) and B.  The first has the smallest N that
+          selects the kernel; a second, larger N follows where the selection rule spans a wide range.  For the entry points
+          without a scheme modulus, q is the modulus (add, split_by_I, polymul_split), the largest value (pack, pack_bytes, unpack)
+          or 2^20 (generic_multiply); p is the sampler's rounds (sample_ternary) and 0 elsewhere.
+  last    what ntru_engine_last_kernel() returns after the call
+  rule    where the launcher writes a coarse name or none: the selection rule the shapes satisfy (nw = (N + 32) / 32 etc.)
+  unreachable  set instead of shapes when no call the ABI accepts selects the instantiation, with the reason
+"""
+
+ROWS = []
+
+
+def _row(kernel, entry, shapes, last=None, rule=None, unreachable=None):
+    ROWS.append({"kernel": kernel, "entry": entry,
+                 "shapes": [dict(N=N, q=q, p=p, path=path, B=B) for (N, q, p, path, B) in shapes],
+                 "last": last, "rule": rule, "unreachable": unreachable})
+
+
+# K of the vector-ALU families: the smallest odd K with ceil(N / 2K) <= 64
+K_RANGES = {1: (2, 128), 3: (129, 384), 5: (385, 640), 7: (641, 896), 9: (897, 1152), 11: (1153, 1408), 13: (1409, 1664),
+            15: (1665, 1920)}
+
+# ---- encrypt -------------------------------------------------------------------------------------------------------------------
+_row("k_encrypt_md", "encrypt", [(64, 2048, 0, 0, 33), (821, 4096, 0, 0, 95)], "k_encrypt_md")
+_row("k_encrypt_m", "encrypt", [(2, 2048, 0, 4, 33), (1024, 8192, 0, 4, 31)], "k_encrypt_m")
+# the ternary add path: K <= 7, one item per wave (ceil(N / 2K) > 32), K values below q on a masked 16-bit field (ME = 2K or K);
+# at path 0 only where the matrix path does not apply (q > 8192)
+_row("k_encrypt_t<1, 2>", "encrypt", [(65, 16384, 0, 0, 5), (128, 2048, 0, 2, 5)], "k_encrypt_t<1,2>")
+_row("k_encrypt_t<1, 1>", "encrypt", [(65, 32768, 0, 0, 5), (128, 32768, 0, 2, 5)], "k_encrypt_t<1,1>")
+_row("k_encrypt_t<3, 6>", "encrypt", [(193, 2048, 0, 2, 5), (384, 8192, 0, 2, 5)], "k_encrypt_t<3,6>")
+_row("k_encrypt_t<3, 3>", "encrypt", [(193, 16384, 0, 0, 5), (384, 16384, 0, 0, 5)], "k_encrypt_t<3,3>")
+_row("k_encrypt_t<5, 10>", "encrypt", [(385, 2048, 0, 2, 5), (640, 4096, 0, 2, 5)], "k_encrypt_t<5,10>")
+_row("k_encrypt_t<5, 5>", "encrypt", [(385, 8192, 0, 2, 5), (640, 8192, 0, 3, 5)], "k_encrypt_t<5,5>")
+_row("k_encrypt_t<7, 14>", "encrypt", [(641, 2048, 0, 2, 5), (896, 4096, 0, 2, 5)], "k_encrypt_t<7,14>")
+_row("k_encrypt_t<7, 7>", "encrypt", [(641, 8192, 0, 2, 5), (896, 8192, 0, 2, 5)], "k_encrypt_t<7,7>")
+# the multiply-accumulate kernels: everything else (q = 65536 leaves no field budget for the add path)
+_row("k_encrypt<1>", "encrypt", [(2, 2048, 0, 0, 1), (128, 65536, 0, 0, 3)], "k_encrypt<1>")
+_row("k_encrypt<3>", "encrypt", [(129, 65536, 0, 0, 3), (384, 2048, 0, 1, 3)], "k_encrypt<3>")
+_row("k_encrypt<5>", "encrypt", [(385, 65536, 0, 0, 3), (640, 2048, 0, 1, 3)], "k_encrypt<5>")
+_row("k_encrypt<7>", "encrypt", [(641, 65536, 0, 0, 3), (896, 2048, 0, 1, 3)], "k_encrypt<7>")
+_row("k_encrypt<9>", "encrypt", [(1025, 2048, 0, 0, 3), (1152, 65536, 0, 0, 3)], "k_encrypt<9>")
+_row("k_encrypt<11>", "encrypt", [(1153, 2048, 0, 0, 3), (1408, 8192, 0, 0, 3)], "k_encrypt<11>")
+_row("k_encrypt<13>", "encrypt", [(1409, 4096, 0, 0, 3), (1664, 65536, 0, 0, 3)], "k_encrypt<13>")
+_row("k_encrypt<15>", "encrypt", [(1665, 2048, 0, 0, 3), (1920, 2048, 0, 0, 3)], "k_encrypt<15>")
+
+# ---- decrypt (p = 3 unless stated) ----------------------------------------------------------------------------------------------
+_row("k_decrypt_m8", "decrypt", [(513, 2048, 3, 0, 95), (864, 4096, 3, 0, 97)], "k_decrypt_m8")
+_row("k_decrypt_m", "decrypt", [(2, 2048, 3, 4, 33), (1024, 8192, 3, 0, 95)], "k_decrypt_m")
+# shared stepping: paths 2 and 3, odd N, K = ceil(N / 64) made odd in 9..13; ME = K for q <= 4096, 7 at q = 8192 (not for K = 13);
+# the dot8 second product where the item takes 32 lanes (ceil(N / 2K) == 32), K >= 11 and path != 3
+_row("k_decrypt_s<9, 9, false>", "decrypt", [(449, 2048, 3, 2, 3), (575, 4096, 3, 2, 3)], "k_decrypt_s<9,9>")
+_row("k_decrypt_s<9, 7, false>", "decrypt", [(449, 8192, 3, 2, 3), (575, 8192, 3, 2, 3)], "k_decrypt_s<9,7>")
+_row("k_decrypt_s<11, 11, false>", "decrypt", [(577, 2048, 3, 2, 3), (703, 4096, 3, 3, 3)], "k_decrypt_s<11,11>")
+_row("k_decrypt_s<11, 11, true>", "decrypt", [(683, 2048, 3, 2, 3), (703, 4096, 3, 2, 3)], "k_decrypt_s+dot8<11,11>")
+_row("k_decrypt_s<11, 7, false>", "decrypt", [(577, 8192, 3, 2, 3), (703, 8192, 3, 3, 3)], "k_decrypt_s<11,7>")
+_row("k_decrypt_s<11, 7, true>", "decrypt", [(683, 8192, 3, 2, 3), (703, 8192, 3, 2, 3)], "k_decrypt_s+dot8<11,7>")
+_row("k_decrypt_s<13, 13, false>", "decrypt", [(705, 2048, 3, 2, 3), (831, 4096, 3, 3, 3)], "k_decrypt_s<13,13>")
+_row("k_decrypt_s<13, 13, true>", "decrypt", [(807, 2048, 3, 2, 3), (831, 4096, 3, 2, 3)], "k_decrypt_s+dot8<13,13>")
+# per-item stepping: path 2 only, the add path's rule (even N where the shared stepping would take odd N)
+_row("k_decrypt_t<1, 2>", "decrypt", [(65, 2048, 3, 2, 5), (128, 16384, 3, 2, 5)], "k_decrypt_t<1,2>")
+_row("k_decrypt_t<1, 1>", "decrypt", [(65, 32768, 3, 2, 5), (128, 32768, 3, 2, 5)], "k_decrypt_t<1,1>")
+_row("k_decrypt_t<3, 6>", "decrypt", [(193, 2048, 3, 2, 5), (384, 8192, 3, 2, 5)], "k_decrypt_t<3,6>")
+_row("k_decrypt_t<3, 3>", "decrypt", [(193, 16384, 3, 2, 5), (384, 16384, 3, 2, 5)], "k_decrypt_t<3,3>")
+_row("k_decrypt_t<5, 10>", "decrypt", [(385, 2048, 3, 2, 5), (640, 4096, 3, 2, 5)], "k_decrypt_t<5,10>")
+_row("k_decrypt_t<5, 5>", "decrypt", [(385, 8192, 3, 2, 5), (640, 8192, 3, 2, 5)], "k_decrypt_t<5,5>")
+_row("k_decrypt_t<7, 14>", "decrypt", [(642, 2048, 3, 2, 5), (896, 4096, 3, 2, 5)], "k_decrypt_t<7,14>")
+_row("k_decrypt_t<7, 7>", "decrypt", [(642, 8192, 3, 2, 5), (896, 8192, 3, 2, 5)], "k_decrypt_t<7,7>")
+_row("k_decrypt<1>", "decrypt", [(2, 2048, 3, 0, 1), (128, 65536, 5, 0, 3)], "k_decrypt<1>")
+_row("k_decrypt<3>", "decrypt", [(129, 65536, 3, 0, 3), (384, 2048, 7, 0, 3)], "k_decrypt<3>")
+_row("k_decrypt<5>", "decrypt", [(385, 65536, 3, 0, 3), (640, 8192, 11, 0, 3)], "k_decrypt<5>")
+_row("k_decrypt<7>", "decrypt", [(641, 65536, 3, 0, 3), (896, 2048, 3, 1, 3)], "k_decrypt<7>")
+_row("k_decrypt<9>", "decrypt", [(1025, 2048, 3, 0, 3), (1152, 8192, 5, 0, 3)], "k_decrypt<9>")
+_row("k_decrypt<11>", "decrypt", [(1153, 2048, 3, 0, 3), (1408, 65536, 7, 0, 3)], "k_decrypt<11>")
+_row("k_decrypt<13>", "decrypt", [(1409, 4096, 3, 0, 3), (1664, 2048, 5, 0, 3)], "k_decrypt<13>")
+_row("k_decrypt<15>", "decrypt", [(1665, 2048, 3, 0, 3), (1920, 8192, 5, 0, 3)], "k_decrypt<15>")
+
+# ---- fused and packed forms -----------------------------------------------------------------------------------------------------
+_row("k_decrypt_mp", "decrypt_pack", [(97, 2048, 3, 0, 33), (821, 4096, 3, 0, 95)], "k_decrypt_mp")
+_row("k_encrypt_wp<11>", "encrypt_pack", [(64, 2048, 0, 0, 33), (509, 2048, 0, 0, 95)], None,
+     "q == 2048, d_e NULL, the row-image kernel's range")
+_row("k_encrypt_wp<12>", "encrypt_pack", [(64, 4096, 0, 0, 33), (821, 4096, 0, 0, 95)], None,
+     "q == 4096, d_e NULL, the row-image kernel's range")
+_row("k_encrypt_wp<13>", "encrypt_pack", [(64, 8192, 0, 0, 33), (701, 8192, 0, 0, 95)], None,
+     "q == 8192, d_e NULL, the row-image kernel's range")
+_row("k_pack_bytes2", "pack_bytes", [(1, 2, 0, 0, 1), (821, 3, 0, 0, 7)], None, "bits == 2 (max_val 2 or 3)")
+_row("k_pack<unsigned char>", "pack_bytes", [(1, 4, 0, 0, 1), (821, 255, 0, 0, 7)], None, "bits != 2")
+_row("k_pack<unsigned short>", "pack", [(1, 1, 0, 0, 1), (821, 4095, 0, 0, 7)], None, "every ntru_pack_batch_dev call")
+_row("k_unpack", "unpack", [(3, 1, 0, 0, 1), (7, 4095, 0, 0, 7)], None,
+     "every ntru_unpack_batch_dev call (N = packed_size, packed_bits 252)")
+
+# ---- verify_keys ----------------------------------------------------------------------------------------------------------------
+_row("k_verify_keys_m", "verify_keys", [(128, 2048, 3, 0, 3), (1024, 8192, 3, 0, 3)], "k_verify_keys_m")
+_row("k_verify_keys_t<1, 2>", "verify_keys", [(65, 2048, 3, 0, 5), (128, 16384, 3, 0, 5)], "k_verify_keys_t<1,2>")
+_row("k_verify_keys_t<1, 1>", "verify_keys", [], "k_verify_keys_t<1,1>",
+     unreachable="ME = 1 at K = 1 needs q = 32768, and verify_keys refuses p (q - 1) > 65535; it is instantiated by the "
+                 "shared add-path dispatch")
+_row("k_verify_keys_t<3, 6>", "verify_keys", [(193, 2048, 3, 2, 5), (384, 8192, 3, 2, 5)], "k_verify_keys_t<3,6>")
+_row("k_verify_keys_t<3, 3>", "verify_keys", [(193, 16384, 3, 0, 5), (384, 16384, 3, 0, 5)], "k_verify_keys_t<3,3>")
+_row("k_verify_keys_t<5, 10>", "verify_keys", [(385, 2048, 3, 2, 5), (640, 4096, 3, 2, 5)], "k_verify_keys_t<5,10>")
+_row("k_verify_keys_t<5, 5>", "verify_keys", [(385, 8192, 3, 2, 5), (640, 8192, 3, 3, 5)], "k_verify_keys_t<5,5>")
+_row("k_verify_keys_t<7, 14>", "verify_keys", [(641, 2048, 3, 2, 5), (896, 4096, 3, 2, 5)], "k_verify_keys_t<7,14>")
+_row("k_verify_keys_t<7, 7>", "verify_keys", [(641, 8192, 3, 2, 5), (896, 8192, 3, 2, 5)], "k_verify_keys_t<7,7>")
+_row("k_verify_keys<1>", "verify_keys", [(2, 2048, 3, 0, 1), (128, 2048, 3, 1, 3)], "k_verify_keys<1>")
+_row("k_verify_keys<3>", "verify_keys", [(129, 2048, 3, 1, 3), (384, 8192, 5, 0, 3)], "k_verify_keys<3>")
+_row("k_verify_keys<5>", "verify_keys", [(385, 2048, 3, 1, 3), (640, 4096, 11, 0, 3)], "k_verify_keys<5>")
+_row("k_verify_keys<7>", "verify_keys", [(641, 2048, 3, 1, 3), (896, 8192, 7, 0, 3)], "k_verify_keys<7>")
+_row("k_verify_keys<9>", "verify_keys", [(1025, 2048, 3, 0, 3), (1152, 8192, 5, 0, 3)], "k_verify_keys<9>")
+_row("k_verify_keys<11>", "verify_keys", [(1153, 2048, 3, 0, 3), (1408, 8192, 7, 0, 3)], "k_verify_keys<11>")
+_row("k_verify_keys<13>", "verify_keys", [(1409, 4096, 3, 0, 3), (1664, 2048, 5, 0, 3)], "k_verify_keys<13>")
+_row("k_verify_keys<15>", "verify_keys", [(1665, 2048, 3, 0, 3), (1920, 8192, 5, 0, 3)], "k_verify_keys<15>")
+
+# ---- polymul_split and the public key ---------------------------------------------------------------------------------------
+_row("k_polymul_m<true>", "polymul_split", [(64, 256, 0, 4, 3), (1024, 2, 0, 0, 3)], "k_polymul_m")
+_row("k_polymul_m<false>", "polymul_split", [(128, 512, 0, 0, 3), (1024, 8192, 0, 0, 3)], "k_polymul_m")
+for _K, (_lo, _hi) in K_RANGES.items():
+    _row("k_polymul_split<%d, false>" % _K, "polymul_split", [(_lo, 65536, 0, 0, 3), (_hi, 3, 0, 1, 3)],
+         "k_polymul_split<%d>" % _K)
+_row("k_product_tern_m<true>", "public_key", [(64, 256, 3, 4, 3), (1024, 2, 1, 0, 3)], "k_public_key_m")
+_row("k_product_tern_m<false>", "public_key", [(128, 512, 3, 0, 3), (1024, 8192, 8, 0, 3)], "k_public_key_m")
+for _K, (_lo, _hi) in K_RANGES.items():
+    _row("k_polymul_split<%d, true>" % _K, "public_key", [(_lo, 16384, 3, 0, 3), (_hi, 8192, 5, 1, 3)], "k_public_key<%d>" % _K)
+
+# ---- key inversion (q = 2048, p = 3) --------------------------------------------------------------------------------------------
+# register-resident planes for nw = (N + 32) / 32 words up to NWC, planes in LDS (NWC = 0) above the largest case
+_INV = {2: (2, 63), 6: (64, 191), 12: (192, 383), 16: (384, 511), 22: (512, 703), 26: (704, 831)}
+for _P in (2, 3):
+    for _W, (_lo, _hi) in _INV.items():
+        _row("k_invert_key<%d, %d>" % (_P, _W), "invert_key", [(_lo, 2048, 3, 0, 3), (_hi, 2048, 3, 0, 3)], None,
+             "nw = (N + 32) / 32 <= %d, above the next smaller case" % _W)
+_row("k_invert_key<2, 32>", "invert_key", [(832, 2048, 3, 0, 3), (1023, 2048, 3, 0, 3)], None, "27 <= nw = (N + 32) / 32 <= 32")
+_row("k_invert_key<2, 0>", "invert_key", [(1024, 2048, 3, 0, 3), (1100, 2048, 3, 0, 3)], None, "nw = (N + 32) / 32 > 32")
+_row("k_invert_key<3, 0>", "invert_key", [(832, 2048, 3, 0, 3), (1023, 2048, 3, 0, 3)], None, "nw = (N + 32) / 32 > 26")
+_row("k_newton_round_m", "invert_key", [(128, 2048, 3, 0, 3), (1024, 8192, 3, 0, 3)], None,
+     "every Newton round on the per-item matrix kernels: 128 <= N <= 1024, q <= 8192")
+_row("k_signed_to_u16", "invert_key", [(17, 32, 3, 0, 3), (101, 2048, 3, 0, 3)], None,
+     "a Newton round outside the matrix range (N < 128 at path 0)")
+_row("k_newton_combine_vec", "invert_key", [(17, 32, 3, 0, 3), (101, 2048, 3, 0, 3)], None,
+     "a Newton round outside the matrix range on 16-byte aligned rows, B N >= 8")
+_row("k_newton_combine", "invert_key", [(17, 32, 3, 0, 3), (101, 2048, 3, 0, 1)], None,
+     "a Newton round outside the matrix range, B N not a multiple of 8")
+_row("k_or_bytes", "invert_key", [(17, 32, 3, 0, 3), (821, 4096, 3, 0, 3)], None, "fq and fp both asked for")
+
+# ---- sampler, elementwise, generic ----------------------------------------------------------------------------------------------
+for _DR, _R in ((10, 20), (6, 12), (4, 8)):
+    _row("k_sample_ternary<false, 4, %d>" % _DR, "sample_ternary", [(2, 0, _R, 0, 1), (1920, 0, _R, 0, 257)], None,
+         "N + 1 < 2048, %d rounds" % _R)
+    _row("k_sample_ternary<true, 1, %d>" % _DR, "sample_ternary", [(2047, 0, _R, 0, 3), (2500, 0, _R, 0, 3)], None,
+         "N + 1 >= 2048, %d rounds" % _R)
+_row("k_add_mod_vec<true>", "add", [(8, 2048, 0, 0, 1), (821, 65536, 0, 0, 9)], None, "power-of-two mod, 16-byte aligned, B N >= 8")
+_row("k_add_mod_vec<false>", "add", [(8, 3, 0, 0, 1), (821, 5, 0, 0, 9)], None, "other mod, 16-byte aligned, B N >= 8")
+_row("k_add_mod", "add", [(1, 2, 0, 0, 1), (821, 2048, 0, 0, 9)], None, "B N not a multiple of 8 (or unaligned)")
+_row("k_split_by_I", "split_by_I", [(1, 2, 0, 0, 1), (821, 4096, 0, 0, 9)], None, "every ntru_split_by_I_dev call")
+_row("(anonymous namespace)::k_generic", "generic_multiply", [(1, 1 << 20, 0, 0, 1), (300, 1 << 20, 0, 0, 5)], "k_generic")
+
+BY_KERNEL = {r["kernel"]: r for r in ROWS}
+assert len(BY_KERNEL) == len(ROWS), "duplicate row"
+# every string ntru_engine_last_kernel() may return after a call of the scheme entry points
+LAST_KERNELS = {r["last"] for r in ROWS if r["last"]} | {"k_invert_key", "k_sample_ternary", "k_encrypt_wp"}

@@ -76,3 +76,33 @@ def test_no_wide_store_followed_by_a_write_of_its_data_registers(build, asm_dirs
                 bad.append((kern, line.strip(), nxt))
     assert n >= BUILDS[build][1], n                       # the scan saw the wide stores of this build
     assert not bad, bad[:5]
+
+
+def _instantiation(demangled):
+    """`void k_decrypt_s<11, 11, true>(Geom, ...)` -> `k_decrypt_s<11, 11, true>`: return type and argument list dropped."""
+    depth = 0
+    for i in range(len(demangled) - 1, -1, -1):
+        depth += {")": 1, "(": -1}.get(demangled[i], 0)
+        if demangled[i] == "(" and depth == 0:
+            demangled = demangled[:i]
+            break
+    return demangled[5:] if demangled.startswith("void ") else demangled
+
+
+@pytest.mark.parametrize("build", sorted(BUILDS))
+def test_every_kernel_instantiation_has_a_variant_row(build, asm_dirs):
+    """tests/kernel_variants.py has one row per compiled kernel instantiation, and names no other: a template case added to a
+    dispatch without a test row that launches it fails here, on the CPU."""
+    import kernel_variants as kv
+    mangled = sorted(set(re.findall(r"Function Name: (\S+)", _asm_usage(build, asm_dirs[build]))))
+    out = subprocess.run(["/usr/bin/c++filt"], input="\n".join(mangled), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    compiled = {_instantiation(d) for d in out.stdout.split("\n") if d.strip()}
+    assert len(compiled) >= 100, len(compiled)
+    rows = [r["kernel"] for r in kv.ROWS]
+    assert len(rows) == len(set(rows)), "duplicate rows"
+    assert not compiled - set(rows), ("compiled without a row", sorted(compiled - set(rows)))
+    assert not set(rows) - compiled, ("row without a compiled instantiation", sorted(set(rows) - compiled))
+    for r in kv.ROWS:
+        assert bool(r["shapes"]) != bool(r["unreachable"]), r["kernel"]          # a call that launches it, or why there is none
+        assert r["last"] or r["rule"], r["kernel"]

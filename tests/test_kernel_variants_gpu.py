@@ -1,0 +1,474 @@
+"""Every compiled kernel instantiation (tests/kernel_variants.py) launched through its entry point and compared bit for bit with the
+CPU oracle, on the operand values and batch sizes where kernels go wrong; p != 3 on every kernel that takes p; and a dispatch sweep
+over every N of kernel paths 0-3, so that a launcher cannot ask for an instantiation that does not exist."""
+import numpy as np
+import pytest
+
+import __graft_entry__ as ge
+import kernel_variants as kv
+from oracle import ntru_keygen as kg
+from oracle import ntru_oracle as orc
+
+pytestmark = pytest.mark.gpu
+pkg = ge.load_package()
+
+WAVES_PER_BLOCK = 4
+P3_ONLY = ("k_decrypt_s", "k_decrypt_t", "k_decrypt_m", "k_verify_keys_t", "k_verify_keys_m")
+FILL = 0xA5                      # output buffers start as this byte: an element the kernel should write and does not shows up
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = pkg.Engine(0)
+    yield e
+    e.close()
+
+
+class Dev:
+    """Device buffers of one call, freed on exit."""
+
+    def __init__(self, eng):
+        self.eng, self.ptrs = eng, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.eng.synchronize()
+        for p in self.ptrs:
+            self.eng.dev_free(p)
+
+    def up(self, arr):
+        arr = np.ascontiguousarray(arr)
+        p = self.eng.dev_alloc(max(arr.nbytes, 16))
+        self.ptrs.append(p)
+        if arr.nbytes:
+            self.eng.dev_upload(p, arr)
+        return p
+
+    def out(self, shape, dtype):
+        return self.up(np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, FILL, np.uint8))
+
+    def get(self, p, shape, dtype):
+        return self.eng.dev_download(p, shape, dtype)
+
+
+def ternary(rng, shape, lo=-1):
+    return rng.integers(lo, lo + 3, shape)
+
+
+def items_per_group(kernel, N):
+    """Items one wave holds at a time (G) for the vector-ALU families: 64 / ceil(N / 2K)."""
+    if "<" not in kernel or kernel.startswith(("k_invert_key", "k_sample", "k_pack", "k_add", "k_polymul_m", "k_product", "k_encrypt_wp")):
+        return None
+    K = int(kernel.split("<")[1].split(",")[0].rstrip(">"))
+    if kernel.startswith(("k_encrypt_t", "k_decrypt_t", "k_verify_keys_t")):
+        return 1
+    return 64 // (-(-N // (2 * K)))
+
+
+def batch_sizes(kernel, shape):
+    """B = 1, the row's own B, and the sizes that leave a partial last group / row block."""
+    N, B = shape["N"], shape["B"]
+    out = {1, B}
+    G = items_per_group(kernel, N)
+    if G:
+        out |= {max(G - 1, 1), G + 1, WAVES_PER_BLOCK * G + 1}
+    if kernel in ("k_encrypt_m", "k_encrypt_md", "k_decrypt_m", "k_decrypt_mp") or kernel.startswith("k_encrypt_wp"):
+        out |= {31, 33}
+    if kernel == "k_decrypt_m8":
+        out |= {31, 95}                              # 1 and 3 row blocks: the second group of the last workgroup idles
+    if kernel in ("k_polymul_m<true>", "k_polymul_m<false>", "k_verify_keys_m") or kernel.startswith("k_product_tern_m"):
+        out |= {3, 33}
+    if N >= 1024:
+        out = {b for b in out if b <= 33}
+    return sorted(out)
+
+
+def rows_cycle(B, makers):
+    return np.stack([makers[b % len(makers)](b) for b in range(B)])
+
+
+# ---- one call of each entry point, compared with the oracle -----------------------------------------------------------------------
+
+def run_encrypt(eng, N, q, B, rng, variant, witness=True):
+    h = [np.full(N, q - 1), rng.integers(0, q, N), np.zeros(N, np.int64)][variant % 3].astype(np.uint16)
+    r = rows_cycle(B, [lambda b: np.ones(N), lambda b: np.full(N, 2), lambda b: ternary(rng, N, 0),
+                       lambda b: np.zeros(N)]).astype(np.uint8)
+    m = rows_cycle(B, [lambda b: np.full(N, 2), lambda b: rng.integers(0, 2, N), lambda b: rng.integers(0, 3, N)]).astype(np.uint8)
+    with Dev(eng) as d:
+        de, dq = d.out((B, N), np.uint16), (d.out((B, N), np.uint16) if witness else None)
+        eng.encrypt_batch_dev(N, q, d.up(h), d.up(r), d.up(m), B, de, dq)
+        got = [d.get(de, (B, N), np.uint16)] + ([d.get(dq, (B, N), np.uint16)] if witness else [])
+    e, quot = orc.encrypt_batch(N, q, h, r, m)
+    return got, [e] + ([quot] if witness else [])
+
+
+def e_rows(rng, N, q, B):
+    return rows_cycle(B, [lambda b: np.full(N, q - 1), lambda b: np.zeros(N), lambda b: np.full(N, q // 2),
+                          lambda b: np.full(N, q // 2 + 1), lambda b: rng.integers(0, q, N),
+                          lambda b: rng.choice([0, q - 1, q // 2, q // 2 + 1], N)]).astype(np.uint16)
+
+
+def decrypt_key(rng, N, p, variant):
+    f = [np.full(N, -1), np.ones(N), ternary(rng, N)][variant % 3].astype(np.int8)
+    fp = (np.full(N, p - 1) if variant % 3 < 2 else rng.integers(0, p, N)).astype(np.uint8)
+    return f, fp
+
+
+def run_decrypt(eng, N, q, p, B, rng, variant, witness=True):
+    f, fp = decrypt_key(rng, N, p, variant)
+    e = e_rows(rng, N, q, B)
+    with Dev(eng) as d:
+        outs = [d.out((B, N), dt) for dt in (np.uint8, np.uint16, np.uint16, np.uint8)]
+        if not witness:
+            outs[1:] = [None] * 3
+        eng.decrypt_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, *outs)
+        got = [d.get(o, (B, N), dt) for o, dt in zip(outs, (np.uint8, np.uint16, np.uint16, np.uint8)) if o]
+    want = orc.decrypt_batch(N, q, p, f, fp, e, want_witness=witness)
+    return got, [w for w in want if w is not None]
+
+
+def run_decrypt_pack(eng, N, q, p, B, rng, variant, fused=True):
+    f, fp = decrypt_key(rng, N, p, variant)
+    e = e_rows(rng, N, q, B)
+    os_ = orc.pack_params(p - 1, N)["outputSize"]
+    with Dev(eng) as d:
+        dv = None if fused else d.out((B, N), np.uint8)
+        dp = d.out((B, os_, 4), np.uint64)
+        eng.decrypt_pack_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, dv, dp)
+        got = [d.get(dp, (B, os_, 4), np.uint64)] + ([] if fused else [d.get(dv, (B, N), np.uint8)])
+    value = orc.decrypt_batch(N, q, p, f, fp, e, want_witness=False)[0]
+    return got, [orc.pack_batch(p - 1, N, value)] + ([] if fused else [value])
+
+
+def run_encrypt_pack(eng, N, q, B, rng, variant):
+    h = [np.full(N, q - 1), rng.integers(0, q, N)][variant % 2].astype(np.uint16)
+    r = rows_cycle(B, [lambda b: np.full(N, 2), lambda b: np.ones(N), lambda b: ternary(rng, N, 0)]).astype(np.uint8)
+    m = rows_cycle(B, [lambda b: np.ones(N), lambda b: rng.integers(0, 2, N)]).astype(np.uint8)
+    os_ = orc.pack_params(q - 1, N)["outputSize"]
+    with Dev(eng) as d:
+        dp = d.out((B, os_, 4), np.uint64)
+        eng.encrypt_pack_batch_dev(N, q, d.up(h), d.up(r), d.up(m), B, None, dp)
+        got = [d.get(dp, (B, os_, 4), np.uint64)]
+    return got, [orc.pack_batch(q - 1, N, orc.encrypt_batch(N, q, h, r, m, want_quot=False)[0])]
+
+
+def key_pairs(rng, N, q, p, B):
+    """Rows of true key pairs (f = +-x^k: fq, fp its inverses, h = p fq g), the same with fq, fp, h or all three corrupted, and the
+    shared extremes (f all -1, g all 1, fq and h all q-1, fp all p-1)."""
+    f = np.zeros((B, N), np.int64); g = ternary(rng, (B, N)); fq = np.zeros((B, N), np.int64); fp = np.zeros((B, N), np.int64)
+    for b in range(B):
+        k, s = (3 * b) % N, (1 if b % 2 else -1)
+        f[b, k] = s
+        fq[b, (N - k) % N] = s % q
+        fp[b, (N - k) % N] = s % p
+    h = orc.public_key_batch(N, q, p, fq, g).astype(np.int64)
+    kind = np.arange(B) % 7
+    fq[kind == 1] = (fq[kind == 1] + 1) % q
+    fp[kind == 2] = (fp[kind == 2] + 1) % p
+    h[kind == 3] = (h[kind == 3] + 1) % q
+    for arr, mod in ((fq, q), (fp, p), (h, q)):
+        arr[kind == 4] = (arr[kind == 4] + 1) % mod
+    f[kind == 5], g[kind == 5], fq[kind == 5], fp[kind == 5], h[kind == 5] = -1, 1, q - 1, p - 1, q - 1
+    f[kind == 6], g[kind == 6] = ternary(rng, (np.sum(kind == 6), N)), -1
+    fq[kind == 6], fp[kind == 6], h[kind == 6] = (rng.integers(0, q, (np.sum(kind == 6), N)), rng.integers(0, p, (np.sum(kind == 6), N)),
+                                                  rng.integers(0, q, (np.sum(kind == 6), N)))
+    return (f.astype(np.int8), g.astype(np.int8), fq.astype(np.uint16), fp.astype(np.uint8), h.astype(np.uint16))
+
+
+VK_OUT = (("quot_fq", np.uint16), ("rem_fq", np.uint16), ("quot_fp", np.uint8), ("rem_fp", np.uint8), ("quot_h", np.uint16),
+          ("rem_h", np.uint16))
+
+
+def run_verify_keys(eng, N, q, p, B, rng, variant):
+    ins = key_pairs(rng, N, q, p, B)
+    with Dev(eng) as d:
+        outs = [d.out((B, N), dt) for _, dt in VK_OUT] + [d.out((B,), np.uint8)]
+        eng.verify_keys_batch_dev(N, q, p, *[d.up(x) for x in ins], B, *outs)
+        got = [d.get(o, (B, N), dt) for o, (_, dt) in zip(outs, VK_OUT)] + [d.get(outs[-1], (B,), np.uint8)]
+    want = orc.verify_keys_batch(N, q, p, *ins)
+    if B >= 7:
+        flags = want["flags"]
+        assert flags[0] == 0 and flags[1] & 1 and flags[2] & 2 and flags[3] & 4 and flags[4] == 7, flags[:7]
+    return got, [want[k] for k, _ in VK_OUT] + [want["flags"]]
+
+
+def run_polymul_split(eng, N, mod, B, rng, variant):
+    a = rows_cycle(B, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(0, mod, N)]).astype(np.uint16)
+    b_ = rows_cycle(B, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(0, mod, N), lambda b: np.ones(N)]).astype(np.uint16)
+    if variant % 2:
+        a, b_ = b_, a
+    with Dev(eng) as d:
+        dq, dr = d.out((B, N), np.uint16), d.out((B, N), np.uint16)
+        eng.polymul_split_dev(N, mod, d.up(a), d.up(b_), B, dq, dr)
+        got = [d.get(dq, (B, N), np.uint16), d.get(dr, (B, N), np.uint16)]
+    return got, list(orc.polymul_split_batch(N, mod, a, b_))
+
+
+def run_public_key(eng, N, q, p, B, rng, variant):
+    fq = rows_cycle(B, [lambda b: np.full(N, q - 1), lambda b: rng.integers(0, q, N)]).astype(np.uint16)
+    g = rows_cycle(B, [lambda b: [np.ones(N), np.full(N, -1), ternary(rng, N)][(b + variant) % 3]]).astype(np.int8)
+    with Dev(eng) as d:
+        dh = d.out((B, N), np.uint16)
+        eng.public_key_batch_dev(N, q, p, d.up(fq), d.up(g), B, dh)
+        got = [d.get(dh, (B, N), np.uint16)]
+    return got, [orc.public_key_batch(N, q, p, fq, g)]
+
+
+def run_invert_key(eng, N, q, p, B, rng, variant):
+    """Inverses are unique: a unit's row must satisfy fq f = 1 (mod q) and fp f = 1 (mod 3); a flagged row must be a non-unit and
+    zero."""
+    f = rows_cycle(B, [lambda b: ternary(rng, N), lambda b: np.ones(N), lambda b: np.eye(1, N, b % N)[0]]).astype(np.int8)
+    with Dev(eng) as d:
+        dq, dp, dfl = d.out((B, N), np.uint16), d.out((B, N), np.uint8), d.out((B,), np.uint8)
+        eng.invert_key_batch_dev(N, q, p, d.up(f), B, dq, dp, dfl)
+        fq, fp, flags = d.get(dq, (B, N), np.uint16), d.get(dp, (B, N), np.uint8), d.get(dfl, (B,), np.uint8)
+    one = np.eye(1, N, 0, dtype=np.uint16)[0]
+    for b in range(B):
+        assert int(flags[b]) & ~24 == 0, flags[b]
+        if b % 3 == 1:                                        # f = 1 + x + ... + x^(N-1) is a zero divisor modulo 2 and 3
+            assert flags[b] == 24 and not fq[b].any() and not fp[b].any(), (b, flags[b])
+            continue
+        for bit, inv, mod, prime in ((8, fq[b], q, 2), (16, fp[b], p, p)):
+            if flags[b] & bit:
+                assert not inv.any() and not kg.is_unit(f[b], N, prime), (b, bit)
+            else:
+                rem = orc.polymul_split_batch(N, mod, inv.astype(np.uint16), (f[b].astype(np.int64) % mod).astype(np.uint16))[1][0]
+                assert np.array_equal(rem, one), (b, mod)
+    return [], []
+
+
+def run_sample_ternary(eng, N, rounds, B, rng, variant):
+    key = rng.integers(0, 1 << 32, 8, dtype=np.uint64).astype(np.uint32)
+    n1, n2 = [(N // 3, N // 3), (N, 0), (0, N)][variant % 3]
+    eng.set_sampler_rounds(rounds)
+    try:
+        with Dev(eng) as d:
+            do = d.out((B, N), np.uint8)
+            eng.sample_ternary_dev(N, n1, n2, 2, key, 5 + variant, B, do)
+            got = [d.get(do, (B, N), np.uint8)]
+    finally:
+        eng.set_sampler_rounds(20)
+    return got, [orc.sample_ternary_batch(N, n1, n2, 2, key, 5 + variant, B, rounds)]
+
+
+def run_pack(eng, N, max_val, B, rng, variant, dtype):
+    data = rows_cycle(B, [lambda b: np.full(N, max_val), lambda b: rng.integers(0, max_val + 1, N)]).astype(dtype)
+    os_ = orc.pack_params(max_val, N)["outputSize"]
+    with Dev(eng) as d:
+        dp = d.out((B, os_, 4), np.uint64)
+        fn = eng._lib.ntru_pack_bytes_batch_dev if dtype == np.uint8 else eng._lib.ntru_pack_batch_dev
+        eng._chk(fn(eng._h, max_val, N, eng._dp(d.up(data)), B, eng._dp(dp)))
+        got = [d.get(dp, (B, os_, 4), np.uint64)]
+    return got, [orc.pack_batch(max_val, N, data)]
+
+
+def run_unpack(eng, S, max_val, B, rng, variant):
+    bits = max_val.bit_length()
+    per = 252 // bits
+    vals = rows_cycle(B, [lambda b: np.full(S * per, max_val), lambda b: rng.integers(0, max_val + 1, S * per)])
+    limbs = orc.pack_batch(max_val, S * per, vals)[:, :S]
+    with Dev(eng) as d:
+        do = d.out((B, S * per), np.uint16)
+        eng._chk(eng._lib.ntru_unpack_batch_dev(eng._h, max_val, 252, eng._dp(d.up(limbs)), S, B, eng._dp(do)))
+        got = [d.get(do, (B, S * per), np.uint16)]
+    return got, [orc.unpack_batch(max_val, 252, limbs)]
+
+
+def run_add(eng, N, mod, B, rng, variant):
+    a = rows_cycle(B, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(0, mod, N)]).astype(np.uint16)
+    b_ = rows_cycle(B, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(0, mod, N)]).astype(np.uint16)
+    with Dev(eng) as d:
+        do = d.out((B, N), np.uint16)
+        eng.add_batch_dev(N, mod, d.up(a), d.up(b_), B, do)
+        got = [d.get(do, (B, N), np.uint16)]
+    return got, [((a.astype(np.int64) + b_) % mod).astype(np.uint16)]
+
+
+def run_split_by_I(eng, N, mod, B, rng, variant):
+    a = rows_cycle(B, [lambda b: np.full(2 * N, mod - 1), lambda b: rng.integers(0, mod, 2 * N)]).astype(np.uint16)
+    with Dev(eng) as d:
+        dq, dr = d.out((B, N), np.uint16), d.out((B, N), np.uint16)
+        eng.split_by_I_dev(N, mod, d.up(a), B, dq, dr)
+        got = [d.get(dq, (B, N), np.uint16), d.get(dr, (B, N), np.uint16)]
+    lo, hi = a[:, :N].astype(np.int64), a[:, N:].astype(np.int64)
+    return got, [((mod - hi) % mod).astype(np.uint16), ((lo + hi) % mod).astype(np.uint16)]
+
+
+def run_generic_multiply(eng, N, mod, B, rng, variant):
+    a = rows_cycle(B, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(-(1 << 26), 1 << 26, N)])
+    b_ = rows_cycle(B, [lambda b: np.full(N, -(1 << 26)), lambda b: rng.integers(0, mod, N)])
+    got = eng.generic_multiply(a, b_, mod)
+    return [got], [[kg._multiply(a[i], b_[i], mod).tolist() for i in range(B)]]
+
+
+def run_shape(eng, entry, s, B, rng, variant):
+    N, q, p = s["N"], s["q"], s["p"]
+    if entry == "encrypt":
+        return run_encrypt(eng, N, q, B, rng, variant, witness=variant != 1)
+    if entry == "decrypt":
+        return run_decrypt(eng, N, q, p, B, rng, variant, witness=variant != 1)
+    if entry == "decrypt_pack":
+        return run_decrypt_pack(eng, N, q, p, B, rng, variant, fused=variant != 1)
+    if entry == "encrypt_pack":
+        return run_encrypt_pack(eng, N, q, B, rng, variant)
+    if entry == "verify_keys":
+        return run_verify_keys(eng, N, q, p, B, rng, variant)
+    if entry == "polymul_split":
+        return run_polymul_split(eng, N, q, B, rng, variant)
+    if entry == "public_key":
+        return run_public_key(eng, N, q, p, B, rng, variant)
+    if entry == "invert_key":
+        return run_invert_key(eng, N, q, p, B, rng, variant)
+    if entry == "sample_ternary":
+        return run_sample_ternary(eng, N, p, B, rng, variant)
+    if entry in ("pack", "pack_bytes"):
+        return run_pack(eng, N, q, B, rng, variant, np.uint8 if entry == "pack_bytes" else np.uint16)
+    if entry == "unpack":
+        return run_unpack(eng, N, q, B, rng, variant)
+    if entry == "add":
+        return run_add(eng, N, q, B, rng, variant)
+    if entry == "split_by_I":
+        return run_split_by_I(eng, N, q, B, rng, variant)
+    if entry == "generic_multiply":
+        return run_generic_multiply(eng, N, q, B, rng, variant)
+    raise AssertionError("no runner for " + entry)
+
+
+def assert_equal(got, want, ctx):
+    assert len(got) == len(want), ctx
+    for i, (g, w) in enumerate(zip(got, want)):
+        if isinstance(w, list):
+            assert g == w, (ctx, i)
+            continue
+        bad = np.argwhere(np.asarray(g) != np.asarray(w))
+        assert bad.size == 0, (ctx, "output %d" % i, "first differing index", bad[0].tolist(), np.asarray(g)[tuple(bad[0])],
+                               np.asarray(w)[tuple(bad[0])], "differing", len(bad))
+
+
+REACHABLE = [r for r in kv.ROWS if r["shapes"]]
+
+
+@pytest.mark.parametrize("row", REACHABLE, ids=[r["kernel"] for r in REACHABLE])
+def test_variant_row_equals_oracle(eng, row):
+    rng = np.random.default_rng(sum(map(ord, row["kernel"])))
+    try:
+        for s in row["shapes"]:
+            eng.set_kernel_path(s["path"])
+            for B in batch_sizes(row["kernel"], s):
+                for variant in range(3):
+                    got, want = run_shape(eng, row["entry"], s, B, rng, variant)
+                    ctx = (row["kernel"], s, B, variant)
+                    if row["last"]:
+                        # the lock-step decrypt runs only with every witness array; value-only calls take k_decrypt_m
+                        expect = "k_decrypt_m" if row["kernel"] == "k_decrypt_m8" and variant == 1 else row["last"]
+                        assert eng.last_kernel() == expect, (ctx, eng.last_kernel())
+                    if row["entry"] == "encrypt_pack":
+                        assert eng.last_kernel() == "k_encrypt_wp", ctx
+                    assert_equal(got, want, ctx)
+    finally:
+        eng.set_kernel_path(0)
+
+
+# ---- p != 3 ------------------------------------------------------------------------------------------------------------------------
+P_MAX_N = {5: 1920, 7: 1820, 11: 655, 13: 455}          # the largest N with N (p - 1)^2 < 65536 (and N <= 1920)
+
+
+def _not_p3_only(eng, ctx):
+    assert not eng.last_kernel().startswith(P3_ONLY), (ctx, eng.last_kernel())
+    assert eng.last_kernel() in kv.LAST_KERNELS, (ctx, eng.last_kernel())
+
+
+@pytest.mark.parametrize("p", sorted(P_MAX_N))
+def test_decrypt_and_verify_keys_p_sweep(eng, p):
+    rng = np.random.default_rng(p)
+    for N in (17, P_MAX_N[p]):
+        for q in (2048, 8192, 65536):
+            for variant in range(3):
+                got, want = run_decrypt(eng, N, q, p, 3, rng, variant, witness=variant != 1)
+                _not_p3_only(eng, ("decrypt", N, q, p))
+                assert_equal(got, want, ("decrypt", N, q, p, variant))
+        for q in sorted({2048, max(2 ** k for k in range(1, 17) if p * (2 ** k - 1) <= 65535)}):
+            got, want = run_verify_keys(eng, N, q, p, 7, rng, 0)
+            _not_p3_only(eng, ("verify_keys", N, q, p))
+            assert_equal(got, want, ("verify_keys", N, q, p))
+
+
+@pytest.mark.parametrize("p", [1, 2, 4, 5, 7, 8])
+def test_public_key_p_sweep(eng, p):
+    rng = np.random.default_rng(100 + p)
+    q = 8192
+    try:
+        for path, N, kernel in ((0, 509, "k_public_key_m"), (4, 64, "k_public_key_m"), (1, 509, "k_public_key<5>"),
+                                (0, 101, "k_public_key<1>"), (0, 1920, "k_public_key<15>")):
+            eng.set_kernel_path(path)
+            for variant in range(3):
+                got, want = run_public_key(eng, N, q, p, 3, rng, variant)
+                assert eng.last_kernel() == kernel, (N, p, path, eng.last_kernel())
+                assert_equal(got, want, ("public_key", N, q, p, path, variant))
+    finally:
+        eng.set_kernel_path(0)
+
+
+def test_decrypt_pack_p5(eng):
+    """packOutput with max 4 (3 bits per value) behind the vector-ALU decrypt: not the fused p == 3 kernel."""
+    rng = np.random.default_rng(5)
+    for N, q in ((17, 2048), (821, 4096), (1920, 8192)):
+        for variant in range(3):
+            got, want = run_decrypt_pack(eng, N, q, 5, 3, rng, variant, fused=False)
+            _not_p3_only(eng, ("decrypt_pack", N, q))
+            assert_equal(got, want, ("decrypt_pack", N, q, 5, variant))
+
+
+# ---- dispatch sweep -------------------------------------------------------------------------------------------------------------
+SWEEP_Q = (2048, 4096, 8192, 16384, 32768)
+MAXN = 1920
+
+
+def documented_refusal(entry, N, q, p):
+    """Calls the ABI refuses by its documented rules: verify_keys needs p (q - 1) <= 65535."""
+    return entry == "verify_keys" and p * (q - 1) > 65535
+
+
+@pytest.mark.parametrize("entry", ["encrypt", "decrypt", "verify_keys", "polymul_split"])
+def test_dispatch_sweep_every_n(eng, entry):
+    """Every N from 2 to 1920 at kernel paths 0-3 and q 2048..32768, B = 1 or 2, device buffers sized for N = 1920: each call the ABI
+    accepts returns NTRU_OK and launches a kernel of the variant table.  Outputs are checked by the per-row cases."""
+    B = 2
+    z16, z8 = np.zeros(B * MAXN, np.uint16), np.zeros(B * MAXN, np.uint8)
+    failed, unknown = [], set()
+    with Dev(eng) as d:
+        u16 = [d.up(z16) for _ in range(6)]
+        u8 = [d.up(z8) for _ in range(6)]
+        try:
+            for N in range(2, MAXN + 1):
+                b = 1 + N % 2
+                for path in range(4):
+                    eng.set_kernel_path(path)
+                    for q in SWEEP_Q:
+                        try:
+                            if entry == "encrypt":
+                                eng.encrypt_batch_dev(N, q, u16[0], u8[0], u8[1], b, u16[1], u16[2])
+                            elif entry == "decrypt":
+                                eng.decrypt_batch_dev(N, q, 3, u8[0], u8[1], u16[0], b, u8[2], u16[1], u16[2], u8[3])
+                            elif entry == "verify_keys":
+                                if documented_refusal(entry, N, q, 3):
+                                    with pytest.raises(pkg.EngineError):
+                                        eng.verify_keys_batch_dev(N, q, 3, u8[0], u8[1], u16[0], u8[2], u16[1], b, u16[2], u16[3],
+                                                                  u8[3], u8[4], u16[4], u16[5], u8[5])
+                                    continue
+                                eng.verify_keys_batch_dev(N, q, 3, u8[0], u8[1], u16[0], u8[2], u16[1], b, u16[2], u16[3], u8[3],
+                                                          u8[4], u16[4], u16[5], u8[5])
+                            else:
+                                eng.polymul_split_dev(N, q, u16[0], u16[1], b, u16[2], u16[3])
+                        except pkg.EngineError as exc:
+                            failed.append((N, q, path, str(exc)))
+                            continue
+                        if eng.last_kernel() not in kv.LAST_KERNELS:
+                            unknown.add((eng.last_kernel(), N, q, path))
+                eng.synchronize()
+        finally:
+            eng.set_kernel_path(0)
+    assert not failed, (len(failed), failed[:12])
+    assert not unknown, sorted(unknown)[:12]
