@@ -9,8 +9,13 @@
                                                           a CHILD `python -m torch.distributed.run`, before anything touches HIP)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR        (also writes the last timed step's outputs to DIR/*.npy)
+  python bench.py --gpus 1 --steps K --warmup W --full                    (also everything beyond the headline figure, below)
 
 Every rank checks WORLD_SIZE == --gpus and refuses to run otherwise.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  --full also runs what the headline
+figure does not need, as before: the CPU baseline, the bit-exact check of a row sample against the CPU oracle, the VALU-families
+and verify_keys legs of the default workload, the gather-to-root with more than one rank and the sustained power phase.
 
 One "step" = one pass of the hot path over one batch of B synthetic plaintexts that are already resident in
 HBM: ntru_encrypt_batch_dev (encryptBits, index.js:87-110) followed by ntru_decrypt_batch_dev of the fresh
@@ -65,8 +70,11 @@ def parse_args(argv=None):
     ap.add_argument("--profile", default=None, help="golden key / parameter set under tests/golden; default: the workload's")
     ap.add_argument("--mode", choices=["witness", "value"], default="witness",
                     help="witness: every array the reference returns; value: ciphertext / plaintext only")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also run the CPU baseline, the oracle check, the VALU-families and verify_keys legs, "
+                         "the gather-to-root with more than one rank and the power phase (off: only what the headline figure needs)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--kernel-path", choices=["auto", "mac", "add", "matrix", "lockstep", "rolesplit", "chunk", "dma", "lockstep-encrypt", "rowimage"], default="auto",
                     help="kernel family: packed-u16 MAC, ternary add path, matrix cores as two workgroups per CU / with the lock-step "
                          "decrypt, or the engine's choice (same results); rolesplit, chunk, dma, lockstep-encrypt need the library "
@@ -82,15 +90,15 @@ def parse_args(argv=None):
                          "instead of torch; the timed region is unchanged")
     ap.add_argument("--gather", action="store_true",
                     help="after timing, gather the workload's result rows of every rank onto rank 0 (one gather-to-root, RCCL over "
-                         "xGMI; with gloo through host memory); reported under `gather`.  Always on with more than one rank")
+                         "xGMI; with gloo through host memory); reported under `gather`.  Always on under --full with more than one rank")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed and run the timing all_reduce / barrier / gather even with ONE rank "
                          "(RCCL refuses two ranks on one device, so this is how the RCCL code path is exercised on a 1-GPU box)")
-    ap.add_argument("--check-rows", type=int, default=1 << 14, help="rows of the batch verified against the CPU oracle")
-    ap.add_argument("--power-seconds", type=float, default=6.0,
+    ap.add_argument("--check-rows", type=int, default=1 << 14, help="rows of the batch verified against the CPU oracle (--full)")
+    ap.add_argument("--power-seconds", type=float, default=None,
                     help="LAST phase of the run: keep stepping for this long while socket power and shader clock are sampled "
-                         "from sysfs (reported under `power`; 0 = skip).  Several seconds, so that a coarse external GPU-activity "
-                         "sampler sees the GPU busy too")
+                         "from sysfs (reported under `power`; 0 = skip; default 6 with --full, else 0).  Several seconds, so that a "
+                         "coarse external GPU-activity sampler sees the GPU busy too")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write the arrays the last one computed (rank 0's shard) as DIR/<name>.npy in "
                          "float32: a fixed seeded sample of rows, at most 60 MiB in all, for comparing two builds output for output")
@@ -108,6 +116,8 @@ def parse_args(argv=None):
         args.batch_log2 = w["batch_log2"]
     if args.profile is None:
         args.profile = w["profile"]
+    if args.power_seconds is None:
+        args.power_seconds = 6.0 if args.full else 0.0
     return args
 
 
@@ -565,9 +575,9 @@ def main():
             return unit
     eng.set_kernel_path(path_no)
 
-    # ---- CPU baseline FIRST (rank 0 at N = 1): the GPU phases then run back to back until the end of the process ----------------
+    # ---- --full: CPU baseline FIRST (rank 0 at N = 1): the GPU phases then run back to back until the end of the process ---------
     out_cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         n_cpu = max(4096, 64 * usable_cores())
         n_cpu = min(n_cpu, B)
         faithful, faithful_share, faithful_all, optimized = cpu_baseline(cpu_unit_factory(n_cpu), n_cpu, args.cpu_seconds, unit_name)
@@ -587,66 +597,69 @@ def main():
     # before anything else runs on these buffers (the alternative-path and sustained phases below write them again)
     dumped = dump_outputs(torch, args.dump_outputs, results, B, N) if args.dump_outputs and rank == 0 else None
 
-    # ---- bit-exact check of a strided sample against the CPU oracle (outside the timed region): every output array ---
-    n_chk = max(1, min(B, args.check_rows))
-    rows = torch.tensor(sorted(set(list(range(0, B, max(1, B // n_chk))) + [B - 1])), device=dev)
-    host = lambda t: to_u16(t[rows][:, :N].contiguous().cpu().numpy())
-    if wl in ("roundtrip", "encrypt_n701"):
-        ins = (host(r), host(m))
-        got = {"e": host(e)}
-        if witness:
-            got["quotE"] = host(quotE)
-        if wl == "roundtrip":
-            got["value"] = host(value)
+    # ---- --full: bit-exact check of a strided sample against the CPU oracle (outside the timed region): every output array
+    verified = {}
+    if args.full:
+        n_chk = max(1, min(B, args.check_rows))
+        rows = torch.tensor(sorted(set(list(range(0, B, max(1, B // n_chk))) + [B - 1])), device=dev)
+        host = lambda t: to_u16(t[rows][:, :N].contiguous().cpu().numpy())
+        if wl in ("roundtrip", "encrypt_n701"):
+            ins = (host(r), host(m))
+            got = {"e": host(e)}
             if witness:
-                got.update(quot1=host(quot1), rem1=host(rem1), quot2=host(quot2))
-
-        def oracle_rows(lo, hi):
-            e_o, qe_o = orc.encrypt_batch(N, q, h_np, ins[0][lo:hi], ins[1][lo:hi])
-            want = {"e": e_o, "quotE": qe_o}
+                got["quotE"] = host(quotE)
             if wl == "roundtrip":
-                v_o, q1_o, r1_o, q2_o = orc.decrypt_batch(N, q, p, f_np, fp_np, e_o)
-                want.update(value=v_o, quot1=q1_o, rem1=r1_o, quot2=q2_o)
-            return want
-    else:
-        ins = tuple(host(t) for t in (kf, kg, kfq, kfp, kh))
-        knames = ("quot_fq", "rem_fq", "quot_fp", "rem_fp", "quot_h", "rem_h")
-        got = {n_: host(t) for n_, t in zip(knames, kouts)}
-        got["flags"] = kflags[rows].cpu().numpy()
-        if keys_info is not None:                              # the generated keys themselves: h = p fq g and no flag from the oracle's own products
-            keys_ok, _ = check_keys_against_oracle(orc, N, q, p, [a[:256] for a in ins])
-            keys_info["sample_equals_oracle"] = keys_ok
-            keys_info["flags_valid"] = int((kflags == 0).sum())
-            if not keys_ok or keys_info["flags_valid"] != B:
-                raise SystemExit("bench: generated keys fail verifyKeysInputs (%d of %d valid; oracle sample %s)" % (keys_info["flags_valid"], B, keys_ok))
+                got["value"] = host(value)
+                if witness:
+                    got.update(quot1=host(quot1), rem1=host(rem1), quot2=host(quot2))
 
-        def oracle_rows(lo, hi):
-            return orc.verify_keys_batch(N, q, p, *[a[lo:hi] for a in ins])
-    n_thr = max(1, min(GPU_SHARE_CORES, usable_cores()))
-    bad, done = [], []
+            def oracle_rows(lo, hi):
+                e_o, qe_o = orc.encrypt_batch(N, q, h_np, ins[0][lo:hi], ins[1][lo:hi])
+                want = {"e": e_o, "quotE": qe_o}
+                if wl == "roundtrip":
+                    v_o, q1_o, r1_o, q2_o = orc.decrypt_batch(N, q, p, f_np, fp_np, e_o)
+                    want.update(value=v_o, quot1=q1_o, rem1=r1_o, quot2=q2_o)
+                return want
+        else:
+            ins = tuple(host(t) for t in (kf, kg, kfq, kfp, kh))
+            knames = ("quot_fq", "rem_fq", "quot_fp", "rem_fp", "quot_h", "rem_h")
+            got = {n_: host(t) for n_, t in zip(knames, kouts)}
+            got["flags"] = kflags[rows].cpu().numpy()
+            if keys_info is not None:                              # the generated keys themselves: h = p fq g and no flag from the oracle's own products
+                keys_ok, _ = check_keys_against_oracle(orc, N, q, p, [a[:256] for a in ins])
+                keys_info["sample_equals_oracle"] = keys_ok
+                keys_info["flags_valid"] = int((kflags == 0).sum())
+                if not keys_ok or keys_info["flags_valid"] != B:
+                    raise SystemExit("bench: generated keys fail verifyKeysInputs (%d of %d valid; oracle sample %s)" % (keys_info["flags_valid"], B, keys_ok))
 
-    def check(lo, hi):
-        try:
-            want = oracle_rows(lo, hi)
-            for k, a in got.items():
-                if not np.array_equal(a[lo:hi], want[k]):
-                    bad.append(k)
-            done.append(hi - lo)
-        except BaseException as exc:        # a worker that dies must not read as "nothing differed"
-            bad.append("check(%d, %d) raised %r" % (lo, hi, exc))
+            def oracle_rows(lo, hi):
+                return orc.verify_keys_batch(N, q, p, *[a[lo:hi] for a in ins])
+        n_thr = max(1, min(GPU_SHARE_CORES, usable_cores()))
+        bad, done = [], []
 
-    cuts = np.linspace(0, len(ins[0]), n_thr + 1).astype(int)
-    ths = [threading.Thread(target=check, args=(int(cuts[i]), int(cuts[i + 1]))) for i in range(n_thr) if cuts[i] < cuts[i + 1]]
-    [t.start() for t in ths]; [t.join() for t in ths]
-    if sum(done) != len(ins[0]) and not bad:
-        bad.append("only %d of %d rows were compared" % (sum(done), len(ins[0])))
-    ok = not bad
-    if not ok:
-        raise SystemExit("bench: GPU results differ from the oracle (%s) -- refusing to report a number" % sorted(set(bad)))
+        def check(lo, hi):
+            try:
+                want = oracle_rows(lo, hi)
+                for k, a in got.items():
+                    if not np.array_equal(a[lo:hi], want[k]):
+                        bad.append(k)
+                done.append(hi - lo)
+            except BaseException as exc:        # a worker that dies must not read as "nothing differed"
+                bad.append("check(%d, %d) raised %r" % (lo, hi, exc))
+
+        cuts = np.linspace(0, len(ins[0]), n_thr + 1).astype(int)
+        ths = [threading.Thread(target=check, args=(int(cuts[i]), int(cuts[i + 1]))) for i in range(n_thr) if cuts[i] < cuts[i + 1]]
+        [t.start() for t in ths]; [t.join() for t in ths]
+        if sum(done) != len(ins[0]) and not bad:
+            bad.append("only %d of %d rows were compared" % (sum(done), len(ins[0])))
+        ok = not bad
+        if not ok:
+            raise SystemExit("bench: GPU results differ from the oracle (%s) -- refusing to report a number" % sorted(set(bad)))
+        verified = {"verified_bit_exact_rows": int(rows.numel()), "verified_arrays": sorted(got.keys())}
 
     # ---- multi-rank evidence: who took part, and the final gather-to-root (outside the timed region) --------------------------
     dist_info, gathered = None, None
-    if dist and (args.gather or world > 1):
+    if dist and (args.gather or (args.full and world > 1)):
         # The final gather: every rank's result rows onto rank 0, once (gather-to-root; nccl = RCCL over xGMI, GPU
         # memory to GPU memory; gloo = through host memory).  Its time is reported, not hidden.
         on_dev = args.dist_backend == "nccl"
@@ -673,9 +686,10 @@ def main():
         common = {"value": total / elapsed, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                   "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
                   "scaling": "strong" if args.total_batch_log2 is not None else "weak", "vs_baseline": None,
-                  "data": "synthetic", "verified_bit_exact_rows": int(rows.numel()), "verified_arrays": sorted(got.keys()),
+                  "data": "synthetic", "full": args.full,
                   "variance": "device to device 3-5 % (the headline measured 259-269 M round trips/s on the boxes of rounds 1-5), run to run "
                               "< 1 % on one device: gains below that are only claimed from same-device A/B runs (EXPERIMENTS.md)"}
+        common.update(verified)
         par = "batch-sharded x%d, no collective" % world
     if rank == 0 and wl == "roundtrip":
         enc_ms, dec_ms = seg_ms
@@ -740,7 +754,7 @@ def main():
             "valu": valu, "mfma": mfma,
             "hbm_gbs_round_trip": (dec_bytes + enc_bytes) * B / ((dec_ms + enc_ms) * 1e-3) / 1e9,
         })
-        if world == 1 and args.kernel_path == "auto" and dname.startswith("k_decrypt_m"):
+        if args.full and world == 1 and args.kernel_path == "auto" and dname.startswith("k_decrypt_m"):
             # The wavefront-per-ciphertext VALU families (BASELINE north_star's design), same buffers, outside the timed
             # region: a few steps, and their outputs must equal the ones just verified.
             cmp_names = ("e", "quotientE", "value", "quotient1", "remainder1", "quotient2") if witness else ("e", "value")
@@ -768,7 +782,7 @@ def main():
             names["encrypt"], names["decrypt"] = list(out["kernels_ms"])
             eng.set_kernel_path(0)
             del ref_out
-        if world == 1 and args.kernel_path == "auto":
+        if args.full and world == 1 and args.kernel_path == "auto":
             # The other function of the path with per-item operands, verifyKeysInputs (index.js:141-197, BASELINE config 5),
             # outside the timed region: 2^18 TRUE key pairs generated on the device (config 5's size), kernel time of 10 launches,
             # a sample of the keys and of every witness array against the oracle (`--workload verify_keys` is the same thing as a

@@ -100,22 +100,26 @@ def test_two_ranks_on_the_hip_kernels_gather_to_root_matches_the_oracle():
     assert kernel.startswith("k_encrypt_m")
 
 
-def _run_bench(extra, env_extra=None):
+def _bench_line(argv, env_extra=None):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env.update(env_extra or {})
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                           "--check-rows", "512"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=300)
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          env=env, timeout=300)
     assert proc.returncode == 0, proc.stderr.decode()[-2000:]
     lines = [l for l in proc.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1, lines                     # ONE JSON line, whatever the ranks and RCCL print
     return json.loads(lines[0])
 
 
+def _run_bench(extra, env_extra=None):
+    return _bench_line(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--check-rows", "512"] + extra, env_extra)
+
+
 def test_bench_gpus_2_starts_two_ranks_by_itself_and_gathers():
     """`python bench.py --gpus 2` (the driver's command shape without a launcher) must really run two ranks."""
-    d = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--batch-log2", "16", "--power-seconds", "0"])   # no --gather: it runs anyway
+    d = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--batch-log2", "16", "--power-seconds", "0", "--full"])   # no --gather: --full runs it
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["dist"]["backend"] == "gloo" and d["dist"]["world"] == 2 and len(d["dist"]["ranks"]) == 2
     # every rank reports its own time, kernel times and items: a straggler shows by itself, and the maximum is the line's ms_per_step
@@ -133,10 +137,10 @@ def test_bench_gpus_2_starts_two_ranks_by_itself_and_gathers():
 
 def test_bench_workloads_config_4_and_5_have_a_multi_rank_entry():
     """BASELINE.json configs 4 (N=701 encryptBits) and 5 (verifyKeysInputs with per-item keys) under the same launcher: two ranks
-    on device 0 over gloo, oracle-checked rows, the gather-to-root runs without being asked for, and the line says who took part."""
+    on device 0 over gloo; with --full, oracle-checked rows and the gather-to-root without --gather; the line says who took part."""
     for wl, unit, kern in (("verify_keys", "key_pairs/s", "k_verify_keys_m"), ("encrypt_n701", "encrypts/s", "k_encrypt_m")):
         d = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--workload", wl, "--batch-log2", "14",
-                        "--power-seconds", "0"])
+                        "--power-seconds", "0", "--full"])
         assert d["n_gpus"] == 2 and d["unit"] == unit and d["scaling"] == "weak"
         assert any(k.startswith(kern) for k in d["kernels_ms"]), d["kernels_ms"]
         assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1 and d["roofline"]["int8"]["unit"].startswith("TOP/s")
@@ -196,7 +200,7 @@ def test_bench_exits_non_zero_when_the_process_group_does_not_come_up():
 def test_bench_four_ranks_report_each_rank():
     """Four ranks (gloo, all on device 0: the box has one GPU and allows six processes on it) through the same launcher the 8-GPU run
     uses: the line carries four rank records with distinct pids, each with its own time and kernel times, and the whole-job value."""
-    d = _run_bench(["--gpus", "4", "--dist-backend", "gloo", "--device", "0", "--batch-log2", "14", "--power-seconds", "0"])
+    d = _run_bench(["--gpus", "4", "--dist-backend", "gloo", "--device", "0", "--batch-log2", "14", "--power-seconds", "0", "--full"])
     ranks = d["dist"]["ranks"]
     assert d["n_gpus"] == 4 and [r["rank"] for r in ranks] == [0, 1, 2, 3] and len({r["pid"] for r in ranks}) == 4
     assert all(r["ms_per_step"] > 0 and r["items_per_step"] == 1 << 14 and len(r["kernels_ms"]) == 2 for r in ranks)
@@ -223,3 +227,30 @@ def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
         assert runs[0][n].dtype == np.float32 and runs[0][n].shape == (rows, 821), n
         assert np.array_equal(runs[0][n], runs[1][n]), n
     assert runs[0]["e"].max() < 4096 and runs[0]["value"].max() <= 2 and runs[0]["e"].any()
+
+
+def test_bench_plain_run_reports_the_headline_only():
+    """The plain command shape (no --full): set-up, warm-up, the timed steps and the line -- no CPU baseline, no oracle check, no
+    extra legs, no gather and no power phase."""
+    d = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "14"])
+    assert d["metric"] == "NTRU encrypt+decrypt round trips per second at N=821, q=4096" and d["unit"] == "round_trips/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "i8" and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - (1 << 14) / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["full"] is False and d["power"] is None
+    for k in ("cpu_baseline", "verified_bit_exact_rows", "valu_families", "verify_keys", "gather", "dist"):
+        assert k not in d, k
+
+
+def test_bench_full_runs_every_leg_of_one_rank():
+    """--full on one rank: the CPU baseline, the oracle check of every array, the VALU-families and verify_keys legs and the power
+    phase all run beside the headline, as a plain run did before --full existed."""
+    d = _bench_line(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "14", "--full", "--cpu-seconds", "0.5",
+                     "--check-rows", "512", "--power-seconds", "0.5"])
+    assert d["full"] is True and d["verified_bit_exact_rows"] >= 512
+    assert d["verified_arrays"] == ["e", "quot1", "quot2", "quotE", "rem1", "value"]
+    for k in ("cpu_baseline", "cpu_baseline_gpu_share", "cpu_baseline_all_cores", "cpu_baseline_optimized"):
+        assert d[k]["value"] > 0 and d[k]["unit"] == "round_trips/s", k
+    assert d["valu_families"]["outputs_equal_matrix_path"] and d["valu_families"]["rows_compared"] == 1 << 14
+    vk = d["verify_keys"]
+    assert vk["flags_valid"] == 1 << 18 and vk["keys"]["sample_equals_oracle"] and vk["ms"] > 0
+    assert "power" in d

@@ -141,6 +141,15 @@ def test_bench_steps_must_be_positive():
         bench.parse_args(["--warmup", "-1"])
 
 
+def test_bench_full_is_off_by_default_and_brings_the_power_phase():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and plain.power_seconds == 0
+    full = bench.parse_args(["--full"])
+    assert full.full and full.power_seconds == 6.0
+    assert bench.parse_args(["--full", "--power-seconds", "0"]).power_seconds == 0
+    assert bench.parse_args(["--power-seconds", "1"]).power_seconds == 1
+
+
 def test_bench_dump_outputs_writes_a_seeded_row_sample_in_float32(tmp_path, monkeypatch):
     """--dump-outputs on host tensors shaped like the bench's buffers: pitched int16 rows holding uint16 patterns, uint8 rows, a
     per-item flag.  The same rows every time, the whole batch when it fits, and never more than the size cap."""

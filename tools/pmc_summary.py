@@ -14,7 +14,7 @@ HBM bytes per launch = (2*FETCH_SIZE + WRITE_SIZE) KiB: FETCH_SIZE counts 64 B p
 (MI355X_MICROARCH.md, HBM section), WRITE_SIZE is exact.
 
 Scaling is PER LAUNCH: the k-th dispatch of a kernel in the counter file is matched with the k-th record of that kernel in the
-launch log, so a kernel that one run launches at several sizes (bench.py: verify_keys at 2^18 beside the 2^20 headline;
+launch log, so a kernel that one run launches at several sizes (bench.py --full: verify_keys at 2^18 beside the 2^20 headline;
 bench_configs.py: k_encrypt_md at three N) gets each launch divided by ITS algorithmic bytes.  A kernel whose dispatch count
 differs from its log (launched by a multi-kernel call that is not logged) gets no ratio instead of a wrong one.
 Durations: the first two launches of every kernel are dropped (cold instruction cache, first-touch page faults of the output
