@@ -323,6 +323,32 @@ int ntru_unpack_batch(ntru_engine_t *eng, int max_val, int packed_bits, const ui
 int ntru_unpack_batch_dev(ntru_engine_t *eng, int max_val, int packed_bits, const uint64_t *d_in, int packed_size,
                           int64_t B, uint16_t *d_out);
 
+/* ---- witness checks: does a witness satisfy the reference's circuit (circuits/ntru.circom with circomlib 2.0.5 LessThan, LessEqThan,
+ *      IsEqual, IsZero, Num2Bits)?  VerifyEncrypt(q, nq, N), VerifyDecrypt(q, nq, p, np, N), VerifyInverse(M, n, N) -- the witnesses
+ *      of encryptBits, decryptBits and verifyKeysInputs()[fq | fp | h] (index.js:87-197).  Every operand is per item, every array dense
+ *      uint16_t: [B][N] for the N-long signals, [B][N+1] for the quotients and remainders; every entry must be below 65536.
+ *      The constraint system is evaluated exactly, range checks included (Modulus's ltP / gteZeroY / ltQ, decrypt's LessThan(nq)).
+ *      flags[b] = 0: item b is accepted; else the OR of the NTRU_CHECK_* bits below, VerifyDecrypt's second stage (mod p) shifted
+ *      left by 3.  Domain: 2 <= N <= NTRU_MAX_N; 2 <= q, M, p <= 65536; q even for VerifyDecrypt; 1 <= nq, np, n <= 252; anything
+ *      else is NTRU_ERR_ARG, checked on the host before the engine.  One item per wavefront (k_check_encrypt / _decrypt / _inverse). */
+#define NTRU_CHECK_EQ 1     /* some a_k differs from the reduced P_k of VerifyDividePolynomials */
+#define NTRU_CHECK_TAIL 2   /* a reduced P_{2N-1} or P_{2N} is nonzero */
+#define NTRU_CHECK_RANGE 4  /* some Modulus or LessThan range check of the stage fails */
+int ntru_check_encrypt_batch(ntru_engine_t *eng, int N, int q, int nq, const uint16_t *r, const uint16_t *m, const uint16_t *h,
+                             const uint16_t *quotE, const uint16_t *remE, int64_t B, uint8_t *flags);
+int ntru_check_encrypt_batch_dev(ntru_engine_t *eng, int N, int q, int nq, const uint16_t *d_r, const uint16_t *d_m,
+                                 const uint16_t *d_h, const uint16_t *d_quotE, const uint16_t *d_remE, int64_t B, uint8_t *d_flags);
+int ntru_check_decrypt_batch(ntru_engine_t *eng, int N, int q, int nq, int p, int np, const uint16_t *f, const uint16_t *fp,
+                             const uint16_t *e, const uint16_t *quot1, const uint16_t *rem1, const uint16_t *quot2,
+                             const uint16_t *rem2, int64_t B, uint8_t *flags);
+int ntru_check_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int nq, int p, int np, const uint16_t *d_f, const uint16_t *d_fp,
+                                 const uint16_t *d_e, const uint16_t *d_quot1, const uint16_t *d_rem1, const uint16_t *d_quot2,
+                                 const uint16_t *d_rem2, int64_t B, uint8_t *d_flags);
+int ntru_check_inverse_batch(ntru_engine_t *eng, int N, int M, int n, const uint16_t *f, const uint16_t *fq, const uint16_t *quotI,
+                             const uint16_t *remI, int64_t B, uint8_t *flags);
+int ntru_check_inverse_batch_dev(ntru_engine_t *eng, int N, int M, int n, const uint16_t *d_f, const uint16_t *d_fq,
+                                 const uint16_t *d_quotI, const uint16_t *d_remI, int64_t B, uint8_t *d_flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,5 +18,5 @@ from .engine import Engine, EngineError, MultiEngine, library_path, load_library
 from . import sharding  # noqa: F401
 from .ntru import (NTRU, addCiphertexts, addPolynomials, bigintToBits, bitsToBigInt, bitsToString, degree,  # noqa: F401
                    dividePolynomials, expandArray, extendedEuclideanAlgorithm, generateCustomArray, modInverse,
-                   multiplyPolynomials, multiplyPolynomialsByScalar, packOutput, polyInv, stringToBits,
+                   multiplyPolynomials, multiplyPolynomialsByScalar, packOutput, polyInv, stringToBits, checkWitnesses,
                    subtractPolynomials, trimPolynomial, unpackInput)

@@ -8,6 +8,7 @@
 //   keygen_sampler_pack.hip  key inversion, ternary sampler, field packing, elementwise kernels + their *_dev entry points
 //   ntru_host.hip            host-pointer entry points: pinned staging, three stage streams, chunked H2D / kernel / D2H pipeline
 //   ntru_generic.hip         reference-faithful generic family (arbitrary divisors, moduli up to 2^26, signed coefficients)
+//   witness_check.hip        witness checks against the Verify* circuits (kernels, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -15,10 +16,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "ntru_engine.h"
 
@@ -163,5 +166,156 @@ NTRU_HIDDEN int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int
                                              const uint16_t *d_fq, const uint8_t *d_fp, const uint16_t *d_h, int64_t B,
                                              uint16_t *d_quot_fq, uint16_t *d_rem_fq, uint8_t *d_quot_fp, uint8_t *d_rem_fp,
                                              uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags);
+
+// ---- host-pointer entry points (ntru_host.hip, witness_check.hip) --------------------------------------------------------------
+// True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).
+NTRU_HIDDEN bool ntru_is_pinned(const void *p);
+// memcpy on several threads once the block is large enough for the extra threads to pay for themselves.
+NTRU_HIDDEN void ntru_big_memcpy(void *dst, const void *src, size_t bytes);
+// Items per chunk of a Pipeline run.
+NTRU_HIDDEN int64_t ntru_chunk_items(int64_t B);
+
+// The chunked H2D / compute / D2H pipeline behind every host-pointer entry point: declare the arrays (in / out / tmp), then run()
+// calls launch(first item, items, device pointers in declaration order) once per chunk on eng->stream.
+struct Pipeline {
+  static constexpr int MAX_ARR = 16;
+  static constexpr size_t ALIGN = 256;
+  struct HArr {
+    const void *src = nullptr;   // host source (inputs)
+    void *dst = nullptr;         // host destination (outputs); an output with dst == nullptr is not wanted
+    size_t row = 0;              // bytes per item, or total bytes when `shared`
+    bool shared = false;         // the same bytes for every chunk (key rows)
+    bool direct = false;         // host memory is pinned: DMA straight from / to it
+    bool temp = false;           // lives on the device only (an intermediate of a multi-stage chunk): no copy either way
+    size_t dev_off = 0, pin_off = 0;
+  };
+  struct Pending { void *dst; const void *pin; size_t bytes; };
+  static size_t up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
+
+  ntru_engine *eng;
+  HArr arr[MAX_ARR];
+  int n = 0;
+  std::vector<Pending> pending[NTRU_HOST_SLOTS];
+  hipStream_t saved_stream;
+  GrowBuf *saved_scratch;
+
+  explicit Pipeline(ntru_engine *e) : eng(e), saved_stream(e->stream), saved_scratch(e->cur_scratch) {}
+  ~Pipeline() { eng->stream = saved_stream; eng->cur_scratch = saved_scratch; }
+
+  int in(const void *p, size_t row, bool shared = false) {
+    arr[n].src = p; arr[n].row = row; arr[n].shared = shared; arr[n].direct = !shared && ntru_is_pinned(p);
+    return n++;
+  }
+  int out(void *p, size_t row) {
+    arr[n].dst = p; arr[n].row = row; arr[n].direct = p && ntru_is_pinned(p);
+    return n++;
+  }
+  int tmp(size_t row) {          // device-only rows of a chunk (what one stage hands the next)
+    arr[n].row = row; arr[n].temp = true;
+    return n++;
+  }
+
+  // Waits until the chunk that owns buffer set s has been downloaded, then hands its staged outputs to the caller's arrays.
+  int drain(int s) {
+    HostSlot &sl = eng->slot[s];
+    if (!sl.busy) return NTRU_OK;
+    HIP_TRY(hipEventSynchronize(sl.down_done));
+    sl.busy = false;
+    for (const Pending &p : pending[s]) ntru_big_memcpy(p.dst, p.pin, p.bytes);
+    pending[s].clear();
+    return NTRU_OK;
+  }
+
+  // launch(first item, items, device pointers in the order the arrays were declared) enqueues on eng->stream.
+  template <class F>
+  int run(int64_t B, int64_t C, F launch) {
+    HIP_TRY(hipSetDevice(eng->device));
+    if (C > B) C = B;
+    if (C < 1) C = 1;
+    size_t dev_bytes = 0, pin_bytes = 0;
+    for (int i = 0; i < n; i++) {
+      HArr &a = arr[i];
+      const size_t bytes = a.shared ? a.row : a.row * (size_t)C;
+      if (!a.src && !a.dst && !a.temp) continue;
+      a.dev_off = dev_bytes; dev_bytes += up(bytes);
+      if (!a.direct && !a.temp) { a.pin_off = pin_bytes; pin_bytes += up(bytes); }
+    }
+    for (hipStream_t *st : {&eng->st_up, &eng->st_comp, &eng->st_down})
+      if (!*st) HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    const int64_t nchunks = (B + C - 1) / C;
+    // A single chunk (every call of the reference's own API) has nothing to overlap with: its three stages go onto ONE stream, in
+    // order, without events between them.
+    const bool single = nchunks == 1;
+    const hipStream_t s_up = single ? eng->st_comp : eng->st_up, s_down = single ? eng->st_comp : eng->st_down;
+    for (int s = 0; s < NTRU_HOST_SLOTS && s < nchunks; s++) {          // a single chunk touches one buffer set only
+      HostSlot &sl = eng->slot[s];
+      for (hipEvent_t *ev : {&sl.up_done, &sl.comp_done, &sl.down_done})
+        if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      if (int rc = ntru_grow_dev(&sl.dev, dev_bytes)) return rc;
+      if (int rc = ntru_grow_pinned(&sl.pinned, pin_bytes)) return rc;
+    }
+    int rc = NTRU_OK;
+    int64_t k = 0;
+    for (int64_t o = 0; o < B && rc == NTRU_OK; o += C, k++) {
+      const int s = (int)(k % NTRU_HOST_SLOTS);
+      const int64_t cnt = std::min(C, B - o);
+      HostSlot &sl = eng->slot[s];
+      if ((rc = drain(s))) break;                        // chunk k - 3 is out of this buffer set
+      // ---- stage 1: upload (staging copies on this thread, DMA on the upload stream)
+      void *dev[MAX_ARR];
+      for (int i = 0; i < n && rc == NTRU_OK; i++) {
+        HArr &a = arr[i];
+        dev[i] = (a.src || a.dst || a.temp) ? (char *)sl.dev.p + a.dev_off : nullptr;
+        if (!a.src) continue;
+        const size_t bytes = a.shared ? a.row : a.row * (size_t)cnt;
+        const char *from = (const char *)a.src + (a.shared ? 0 : a.row * (size_t)o);
+        if (!a.direct) {
+          char *pin = (char *)sl.pinned.p + a.pin_off;
+          ntru_big_memcpy(pin, from, bytes);
+          from = pin;
+        }
+        if (hipMemcpyAsync(dev[i], from, bytes, hipMemcpyHostToDevice, s_up) != hipSuccess)
+          rc = ntru_fail(NTRU_ERR_HIP, "hipMemcpyAsync (host to device) failed");
+      }
+      if (!single && rc == NTRU_OK && hipEventRecord(sl.up_done, s_up) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
+      // ---- stage 2: compute, behind this chunk's upload
+      if (!single && rc == NTRU_OK && hipStreamWaitEvent(eng->st_comp, sl.up_done, 0) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipStreamWaitEvent failed");
+      eng->stream = eng->st_comp;
+      eng->cur_scratch = &sl.scratch;
+      if (rc == NTRU_OK) rc = launch(o, cnt, dev);
+      if (!single && rc == NTRU_OK && hipEventRecord(sl.comp_done, eng->st_comp) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
+      // ---- stage 3: download, behind this chunk's kernels
+      if (!single && rc == NTRU_OK && hipStreamWaitEvent(s_down, sl.comp_done, 0) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipStreamWaitEvent failed");
+      for (int i = 0; i < n && rc == NTRU_OK; i++) {
+        HArr &a = arr[i];
+        if (!a.dst) continue;
+        const size_t bytes = a.row * (size_t)cnt;
+        char *to = (char *)a.dst + a.row * (size_t)o;
+        if (!a.direct) {
+          char *pin = (char *)sl.pinned.p + a.pin_off;
+          pending[s].push_back({to, pin, bytes});
+          to = pin;
+        }
+        if (hipMemcpyAsync(to, dev[i], bytes, hipMemcpyDeviceToHost, s_down) != hipSuccess)
+          rc = ntru_fail(NTRU_ERR_HIP, "hipMemcpyAsync (device to host) failed");
+      }
+      // (recorded even after a failure: whatever was enqueued for this set must be waited for before the set is reused)
+      if (hipEventRecord(sl.down_done, s_down) == hipSuccess) sl.busy = true;
+      else if (rc == NTRU_OK) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
+    }
+    // results of the chunks still in flight, oldest first; on failure still wait so nothing is left in flight
+    const std::string err = rc ? std::string(ntru_last_error()) : std::string();
+    for (int t = 0; t < NTRU_HOST_SLOTS; t++) {
+      const int s = (int)((k + t) % NTRU_HOST_SLOTS);
+      if (rc) {
+        HostSlot &sl = eng->slot[s];
+        if (sl.busy) { (void)hipStreamSynchronize(eng->st_up); (void)hipStreamSynchronize(eng->st_comp); (void)hipStreamSynchronize(eng->st_down); sl.busy = false; }
+        pending[s].clear();
+      } else rc = drain(s);
+    }
+    if (!err.empty()) ntru_fail(rc, err);
+    return rc;
+  }
+};
 
 #endif

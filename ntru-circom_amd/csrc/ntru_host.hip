@@ -22,32 +22,14 @@
 
 #include "engine_internal.h"
 
-namespace {
-
-constexpr int MAX_ARR = 16;
-constexpr size_t ALIGN = 256;
-
-struct HArr {
-  const void *src = nullptr;   // host source (inputs)
-  void *dst = nullptr;         // host destination (outputs); an output with dst == nullptr is not wanted
-  size_t row = 0;              // bytes per item, or total bytes when `shared`
-  bool shared = false;         // the same bytes for every chunk (key rows)
-  bool direct = false;         // host memory is pinned: DMA straight from / to it
-  bool temp = false;           // lives on the device only (an intermediate of a multi-stage chunk): no copy either way
-  size_t dev_off = 0, pin_off = 0;
-};
-
-inline size_t up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
-
-// True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).
-bool is_pinned(const void *p) {
+// ---- the helpers of Pipeline (engine_internal.h)
+bool ntru_is_pinned(const void *p) {
   hipPointerAttribute_t at;
   if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
   return at.type == hipMemoryTypeHost;
 }
 
-// memcpy on several threads once the block is large enough for the extra threads to pay for themselves.
-void big_memcpy(void *dst, const void *src, size_t bytes) {
+void ntru_big_memcpy(void *dst, const void *src, size_t bytes) {
   constexpr size_t PER_THREAD = (size_t)4 << 20;
   unsigned hw = std::thread::hardware_concurrency();
   size_t nt = std::min<size_t>(std::min<size_t>(hw ? hw : 1, 8), bytes / PER_THREAD);
@@ -62,145 +44,14 @@ void big_memcpy(void *dst, const void *src, size_t bytes) {
   for (auto &t : th) t.join();
 }
 
-struct Pending { void *dst; const void *pin; size_t bytes; };
-
-struct Pipeline {
-  ntru_engine *eng;
-  HArr arr[MAX_ARR];
-  int n = 0;
-  std::vector<Pending> pending[NTRU_HOST_SLOTS];
-  hipStream_t saved_stream;
-  GrowBuf *saved_scratch;
-
-  explicit Pipeline(ntru_engine *e) : eng(e), saved_stream(e->stream), saved_scratch(e->cur_scratch) {}
-  ~Pipeline() { eng->stream = saved_stream; eng->cur_scratch = saved_scratch; }
-
-  int in(const void *p, size_t row, bool shared = false) {
-    arr[n].src = p; arr[n].row = row; arr[n].shared = shared; arr[n].direct = !shared && is_pinned(p);
-    return n++;
-  }
-  int out(void *p, size_t row) {
-    arr[n].dst = p; arr[n].row = row; arr[n].direct = p && is_pinned(p);
-    return n++;
-  }
-  int tmp(size_t row) {          // device-only rows of a chunk (what one stage hands the next)
-    arr[n].row = row; arr[n].temp = true;
-    return n++;
-  }
-
-  // Waits until the chunk that owns buffer set s has been downloaded, then hands its staged outputs to the caller's arrays.
-  int drain(int s) {
-    HostSlot &sl = eng->slot[s];
-    if (!sl.busy) return NTRU_OK;
-    HIP_TRY(hipEventSynchronize(sl.down_done));
-    sl.busy = false;
-    for (const Pending &p : pending[s]) big_memcpy(p.dst, p.pin, p.bytes);
-    pending[s].clear();
-    return NTRU_OK;
-  }
-
-  // launch(first item, items, device pointers in the order the arrays were declared) enqueues on eng->stream.
-  template <class F>
-  int run(int64_t B, int64_t C, F launch) {
-    HIP_TRY(hipSetDevice(eng->device));
-    if (C > B) C = B;
-    if (C < 1) C = 1;
-    size_t dev_bytes = 0, pin_bytes = 0;
-    for (int i = 0; i < n; i++) {
-      HArr &a = arr[i];
-      const size_t bytes = a.shared ? a.row : a.row * (size_t)C;
-      if (!a.src && !a.dst && !a.temp) continue;
-      a.dev_off = dev_bytes; dev_bytes += up(bytes);
-      if (!a.direct && !a.temp) { a.pin_off = pin_bytes; pin_bytes += up(bytes); }
-    }
-    for (hipStream_t *st : {&eng->st_up, &eng->st_comp, &eng->st_down})
-      if (!*st) HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-    const int64_t nchunks = (B + C - 1) / C;
-    // A single chunk (every call of the reference's own API) has nothing to overlap with: its three stages go onto ONE stream, in
-    // order, without events between them.
-    const bool single = nchunks == 1;
-    const hipStream_t s_up = single ? eng->st_comp : eng->st_up, s_down = single ? eng->st_comp : eng->st_down;
-    for (int s = 0; s < NTRU_HOST_SLOTS && s < nchunks; s++) {          // a single chunk touches one buffer set only
-      HostSlot &sl = eng->slot[s];
-      for (hipEvent_t *ev : {&sl.up_done, &sl.comp_done, &sl.down_done})
-        if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-      if (int rc = ntru_grow_dev(&sl.dev, dev_bytes)) return rc;
-      if (int rc = ntru_grow_pinned(&sl.pinned, pin_bytes)) return rc;
-    }
-    int rc = NTRU_OK;
-    int64_t k = 0;
-    for (int64_t o = 0; o < B && rc == NTRU_OK; o += C, k++) {
-      const int s = (int)(k % NTRU_HOST_SLOTS);
-      const int64_t cnt = std::min(C, B - o);
-      HostSlot &sl = eng->slot[s];
-      if ((rc = drain(s))) break;                        // chunk k - 3 is out of this buffer set
-      // ---- stage 1: upload (staging copies on this thread, DMA on the upload stream)
-      void *dev[MAX_ARR];
-      for (int i = 0; i < n && rc == NTRU_OK; i++) {
-        HArr &a = arr[i];
-        dev[i] = (a.src || a.dst || a.temp) ? (char *)sl.dev.p + a.dev_off : nullptr;
-        if (!a.src) continue;
-        const size_t bytes = a.shared ? a.row : a.row * (size_t)cnt;
-        const char *from = (const char *)a.src + (a.shared ? 0 : a.row * (size_t)o);
-        if (!a.direct) {
-          char *pin = (char *)sl.pinned.p + a.pin_off;
-          big_memcpy(pin, from, bytes);
-          from = pin;
-        }
-        if (hipMemcpyAsync(dev[i], from, bytes, hipMemcpyHostToDevice, s_up) != hipSuccess)
-          rc = ntru_fail(NTRU_ERR_HIP, "hipMemcpyAsync (host to device) failed");
-      }
-      if (!single && rc == NTRU_OK && hipEventRecord(sl.up_done, s_up) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
-      // ---- stage 2: compute, behind this chunk's upload
-      if (!single && rc == NTRU_OK && hipStreamWaitEvent(eng->st_comp, sl.up_done, 0) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipStreamWaitEvent failed");
-      eng->stream = eng->st_comp;
-      eng->cur_scratch = &sl.scratch;
-      if (rc == NTRU_OK) rc = launch(o, cnt, dev);
-      if (!single && rc == NTRU_OK && hipEventRecord(sl.comp_done, eng->st_comp) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
-      // ---- stage 3: download, behind this chunk's kernels
-      if (!single && rc == NTRU_OK && hipStreamWaitEvent(s_down, sl.comp_done, 0) != hipSuccess) rc = ntru_fail(NTRU_ERR_HIP, "hipStreamWaitEvent failed");
-      for (int i = 0; i < n && rc == NTRU_OK; i++) {
-        HArr &a = arr[i];
-        if (!a.dst) continue;
-        const size_t bytes = a.row * (size_t)cnt;
-        char *to = (char *)a.dst + a.row * (size_t)o;
-        if (!a.direct) {
-          char *pin = (char *)sl.pinned.p + a.pin_off;
-          pending[s].push_back({to, pin, bytes});
-          to = pin;
-        }
-        if (hipMemcpyAsync(to, dev[i], bytes, hipMemcpyDeviceToHost, s_down) != hipSuccess)
-          rc = ntru_fail(NTRU_ERR_HIP, "hipMemcpyAsync (device to host) failed");
-      }
-      // (recorded even after a failure: whatever was enqueued for this set must be waited for before the set is reused)
-      if (hipEventRecord(sl.down_done, s_down) == hipSuccess) sl.busy = true;
-      else if (rc == NTRU_OK) rc = ntru_fail(NTRU_ERR_HIP, "hipEventRecord failed");
-    }
-    // results of the chunks still in flight, oldest first; on failure still wait so nothing is left in flight
-    const std::string err = rc ? std::string(ntru_last_error()) : std::string();
-    for (int t = 0; t < NTRU_HOST_SLOTS; t++) {
-      const int s = (int)((k + t) % NTRU_HOST_SLOTS);
-      if (rc) {
-        HostSlot &sl = eng->slot[s];
-        if (sl.busy) { (void)hipStreamSynchronize(eng->st_up); (void)hipStreamSynchronize(eng->st_comp); (void)hipStreamSynchronize(eng->st_down); sl.busy = false; }
-        pending[s].clear();
-      } else rc = drain(s);
-    }
-    if (!err.empty()) ntru_fail(rc, err);
-    return rc;
-  }
-};
-
 // Items per chunk: large enough that a kernel launch fills the chip, small enough that a batch has several chunks in
 // flight (a chunk of 2^15 N=821 round trips is ~0.4 GB over PCIe, ~7 ms; its kernels take ~0.15 ms).
-int64_t chunk_items(int64_t B) {
+int64_t ntru_chunk_items(int64_t B) {
   const int64_t big = 1 << 15;
   if (B >= 4 * big) return big;
   if (B >= 4 * 2048) return (B + 3) / 4;
   return B;
 }
-
-}  // namespace
 
 extern "C" void *ntru_host_alloc(size_t bytes) {
   void *p = nullptr;
@@ -228,7 +79,7 @@ extern "C" int ntru_encrypt_batch(ntru_engine_t *eng, int N, int q, const uint16
   Pipeline P(eng);
   const int ih = P.in(h, (size_t)N * 2, true), ir = P.in(r, N), im = P.in(m, N), ie = P.out(e, (size_t)N * 2),
             iq = P.out(quotE, (size_t)N * 2);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_encrypt_batch_dev(eng, N, q, (const uint16_t *)d[ih], (const uint8_t *)d[ir], (const uint8_t *)d[im], n,
                                   (uint16_t *)d[ie], (uint16_t *)d[iq]);
   });
@@ -244,7 +95,7 @@ extern "C" int ntru_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const
   Pipeline P(eng);
   const int jf = P.in(f, N, true), jfp = P.in(fp, N, true), je = P.in(e, (size_t)N * 2), jv = P.out(value, N),
             jq1 = P.out(quot1, (size_t)N * 2), jr1 = P.out(rem1, (size_t)N * 2), jq2 = P.out(quot2, N);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_decrypt_batch_dev(eng, N, q, p, (const int8_t *)d[jf], (const uint8_t *)d[jfp], (const uint16_t *)d[je], n,
                                   (uint8_t *)d[jv], (uint16_t *)d[jq1], (uint16_t *)d[jr1], (uint8_t *)d[jq2]);
   });
@@ -259,7 +110,7 @@ extern "C" int ntru_polymul_split(ntru_engine_t *eng, int N, int mod, const uint
   Pipeline P(eng);
   const size_t row = (size_t)N * 2;
   const int ia = P.in(a, row), ib = P.in(b, row), iq = P.out(quot, row), ir = P.out(rem, row);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_polymul_split_dev(eng, N, mod, (const uint16_t *)d[ia], (const uint16_t *)d[ib], n, (uint16_t *)d[iq],
                                   (uint16_t *)d[ir]);
   });
@@ -273,7 +124,7 @@ extern "C" int ntru_invert_key_batch(ntru_engine_t *eng, int N, int q, int p, co
   if (!f || (!fq && !fp) || !flags) return ntru_fail(NTRU_ERR_ARG, "ntru_invert_key_batch: NULL buffer");
   Pipeline P(eng);
   const int jf = P.in(f, N), jfq = P.out(fq, (size_t)N * 2), jfp = P.out(fp, N), jfl = P.out(flags, 1);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_invert_key_batch_dev(eng, N, q, p, (const int8_t *)d[jf], n, (uint16_t *)d[jfq], (uint8_t *)d[jfp],
                                      (uint8_t *)d[jfl]);
   });
@@ -287,7 +138,7 @@ extern "C" int ntru_public_key_batch(ntru_engine_t *eng, int N, int q, int p, co
   if (!fq || !g || !h) return ntru_fail(NTRU_ERR_ARG, "ntru_public_key_batch: NULL buffer");
   Pipeline P(eng);
   const int jfq = P.in(fq, (size_t)N * 2), jg = P.in(g, N), jh = P.out(h, (size_t)N * 2);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_public_key_batch_dev(eng, N, q, p, (const uint16_t *)d[jfq], (const int8_t *)d[jg], n, (uint16_t *)d[jh]);
   });
 }
@@ -307,7 +158,7 @@ extern "C" int ntru_verify_keys_batch(ntru_engine_t *eng, int N, int q, int p, c
   const int jf = P.in(f, r8), jg = P.in(g, r8), jfq = P.in(fq, r16), jfp = P.in(fp, r8), jh = P.in(h, r16);
   const int o1 = P.out(quot_fq, r16), o2 = P.out(rem_fq, r16), o3 = P.out(quot_fp, r8), o4 = P.out(rem_fp, r8),
             o5 = P.out(quot_h, r16), o6 = P.out(rem_h, r16), ofl = P.out(flags, 1);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_verify_keys_batch_dev(eng, N, q, p, (const int8_t *)d[jf], (const int8_t *)d[jg], (const uint16_t *)d[jfq],
                                       (const uint8_t *)d[jfp], (const uint16_t *)d[jh], n, (uint16_t *)d[o1], (uint16_t *)d[o2],
                                       (uint8_t *)d[o3], (uint8_t *)d[o4], (uint16_t *)d[o5], (uint16_t *)d[o6], (uint8_t *)d[ofl]);
@@ -323,7 +174,7 @@ extern "C" int ntru_split_by_I(ntru_engine_t *eng, int N, int mod, const uint16_
   Pipeline P(eng);
   const size_t row = (size_t)N * 2;
   const int ia = P.in(a, 2 * row), iq = P.out(quot, row), ir = P.out(rem, row);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_split_by_I_dev(eng, N, mod, (const uint16_t *)d[ia], n, (uint16_t *)d[iq], (uint16_t *)d[ir]);
   });
 }
@@ -337,7 +188,7 @@ extern "C" int ntru_add_batch(ntru_engine_t *eng, int N, int mod, const uint16_t
   Pipeline P(eng);
   const size_t row = (size_t)N * 2;
   const int ia = P.in(a, row), ib = P.in(b, row), io = P.out(out, row);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_add_batch_dev(eng, N, mod, (const uint16_t *)d[ia], (const uint16_t *)d[ib], n, (uint16_t *)d[io]);
   });
 }
@@ -350,7 +201,7 @@ extern "C" int ntru_sample_ternary(ntru_engine_t *eng, int N, int n1, int n2, in
   if (int rc = ntru_sample_ternary_dev(eng, N, n1, n2, other, key, first_item, 0, nullptr)) return rc;
   Pipeline P(eng);
   const int io = P.out(out, N);
-  return P.run(B, chunk_items(B), [&](int64_t o, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) {
     return ntru_sample_ternary_dev(eng, N, n1, n2, other, key, first_item + (uint64_t)o, n, (uint8_t *)d[io]);
   });
 }
@@ -364,7 +215,7 @@ extern "C" int ntru_pack_batch(ntru_engine_t *eng, int max_val, int data_len, co
   if ((!data && data_len) || !out) return ntru_fail(NTRU_ERR_ARG, "ntru_pack_batch: NULL buffer");
   Pipeline P(eng);
   const int ii = P.in(data_len ? data : nullptr, (size_t)data_len * 2), io = P.out(out, (size_t)os * 32);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_pack_batch_dev(eng, max_val, data_len, (const uint16_t *)d[ii], n, (uint64_t *)d[io]);
   });
 }
@@ -381,7 +232,7 @@ extern "C" int ntru_unpack_batch(ntru_engine_t *eng, int max_val, int packed_bit
   const int per = packed_bits / bits;
   Pipeline P(eng);
   const int ii = P.in(in, (size_t)packed_size * 32), io = P.out(out, (size_t)packed_size * per * 2);
-  return P.run(B, chunk_items(B), [&](int64_t, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
     return ntru_unpack_batch_dev(eng, max_val, packed_bits, (const uint64_t *)d[ii], packed_size, n, (uint16_t *)d[io]);
   });
 }
@@ -417,7 +268,7 @@ extern "C" int ntru_pipeline_batch(ntru_engine_t *eng, int N, int q, int p, cons
   const int ie = e ? P.out(e, (size_t)N * 2) : P.tmp((size_t)N * 2);
   const int iv = !decrypt ? -1 : (value ? P.out(value, N) : P.tmp(N));
   const int ip = packed ? P.out(packed, (size_t)os * 32) : -1;
-  return P.run(B, chunk_items(B), [&](int64_t o, int64_t n, void **d) {
+  return P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) {
     if (key) if (int rc = ntru_sample_ternary_dev(eng, N, n1, n2, p - 1, key, first_item + (uint64_t)o, n, (uint8_t *)d[ir])) return rc;
     if (!decrypt && packed) {   // packOutput of e: out of the encrypt kernel itself when e is not an output too and the row-image kernel applies
       if (!e) {                                            // the launcher itself says whether the fused kernel applies (NTRU_NOT_TAKEN:

@@ -10,6 +10,8 @@ _LIB = None
 ERR_NAMES = {1: "NTRU_ERR_NO_DEVICE", 2: "NTRU_ERR_ARG", 3: "NTRU_ERR_UNSUPPORTED", 4: "NTRU_ERR_HIP"}
 FLAG_INVALID_FQ, FLAG_INVALID_FP, FLAG_INVALID_H = 1, 2, 4
 FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP = 8, 16
+# bits of the witness-check flags (include/ntru_engine.h NTRU_CHECK_*); VerifyDecrypt's second stage is shifted left by 3
+CHECK_EQ, CHECK_TAIL, CHECK_RANGE = 1, 2, 4
 # status codes of the generic family = the errors the reference throws (include/ntru_engine.h NTRU_GENERIC_*)
 GENERIC_ERRORS = {1: "Cannot divide by zero polynomial.", 2: "No inverse exists for division.", 3: "invalid_gcd",
                   4: "ntru engine: generic work area exhausted"}
@@ -81,6 +83,10 @@ _SIGS["ntru_multi_verify_keys_batch"] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 
 _SIGS["ntru_multi_polymul_split"] = (C.c_int, [_vp, _i, _i, _vp, _vp, _i64, _vp, _vp])
 _SIGS["ntru_multi_invert_key_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp])
 _SIGS["ntru_multi_public_key_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp])
+for _sfx in ("", "_dev"):
+    _SIGS["ntru_check_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _vp])
+    _SIGS["ntru_check_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i64, _vp])
+    _SIGS["ntru_check_inverse_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 4 + [_i64, _vp])
 _SIGS["ntru_encrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
 _SIGS["ntru_decrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
 
@@ -345,6 +351,54 @@ class Engine:
         flags = np.empty(B, np.uint8)
         self._chk(self._lib.ntru_invert_key_batch(self._h, N, q, p, _ptr(f), B, _ptr(fq), _ptr(fp), _ptr(flags)))
         return fq, fp, flags
+
+    # ---- witness checks (VerifyEncrypt / VerifyDecrypt / VerifyInverse): uint16 rows [B][N] and [B][N + 1] -> flags uint8[B] ----
+    @staticmethod
+    def _rows(a, n):
+        return _np(a, np.uint16).reshape(-1, n)
+
+    def check_encrypt_batch(self, N, q, nq, r, m, h, quotE, remE):
+        r, m, h = (self._rows(x, N) for x in (r, m, h))
+        quotE, remE = self._rows(quotE, N + 1), self._rows(remE, N + 1)
+        B = r.shape[0]
+        flags = np.empty(B, np.uint8)
+        self._chk(self._lib.ntru_check_encrypt_batch(self._h, N, q, nq, _ptr(r), _ptr(m), _ptr(h), _ptr(quotE), _ptr(remE), B,
+                                                     _ptr(flags)))
+        return flags
+
+    def check_decrypt_batch(self, N, q, nq, p, np_, f, fp, e, quot1, rem1, quot2, rem2):
+        f, fp, e = (self._rows(x, N) for x in (f, fp, e))
+        quot1, rem1, quot2, rem2 = (self._rows(x, N + 1) for x in (quot1, rem1, quot2, rem2))
+        B = f.shape[0]
+        flags = np.empty(B, np.uint8)
+        self._chk(self._lib.ntru_check_decrypt_batch(self._h, N, q, nq, p, np_, _ptr(f), _ptr(fp), _ptr(e), _ptr(quot1), _ptr(rem1),
+                                                     _ptr(quot2), _ptr(rem2), B, _ptr(flags)))
+        return flags
+
+    def check_inverse_batch(self, N, M, n, f, fq, quotI, remI):
+        f, fq = self._rows(f, N), self._rows(fq, N)
+        quotI, remI = self._rows(quotI, N + 1), self._rows(remI, N + 1)
+        B = f.shape[0]
+        flags = np.empty(B, np.uint8)
+        self._chk(self._lib.ntru_check_inverse_batch(self._h, N, M, n, _ptr(f), _ptr(fq), _ptr(quotI), _ptr(remI), B, _ptr(flags)))
+        return flags
+
+    def check_encrypt_batch_dev(self, N, q, nq, d_r, d_m, d_h, d_quotE, d_remE, B, d_flags):
+        dp = self._dp
+        self._chk(self._lib.ntru_check_encrypt_batch_dev(self._h, N, q, nq, dp(d_r), dp(d_m), dp(d_h), dp(d_quotE), dp(d_remE), B,
+                                                         dp(d_flags)))
+        self._note(N, B, 6 * N + 4 * (N + 1) + 1)
+
+    def check_decrypt_batch_dev(self, N, q, nq, p, np_, d_f, d_fp, d_e, d_quot1, d_rem1, d_quot2, d_rem2, B, d_flags):
+        dp = self._dp
+        self._chk(self._lib.ntru_check_decrypt_batch_dev(self._h, N, q, nq, p, np_, dp(d_f), dp(d_fp), dp(d_e), dp(d_quot1), dp(d_rem1),
+                                                         dp(d_quot2), dp(d_rem2), B, dp(d_flags)))
+        self._note(N, B, 6 * N + 8 * (N + 1) + 1)
+
+    def check_inverse_batch_dev(self, N, M, n, d_f, d_fq, d_quotI, d_remI, B, d_flags):
+        dp = self._dp
+        self._chk(self._lib.ntru_check_inverse_batch_dev(self._h, N, M, n, dp(d_f), dp(d_fq), dp(d_quotI), dp(d_remI), B, dp(d_flags)))
+        self._note(N, B, 4 * N + 4 * (N + 1) + 1)
 
     # ---- pinned host memory ---------------------------------------------------------------------------------
     def pinned_empty(self, shape, dtype):

@@ -261,6 +261,53 @@ static napi_value VerifyKeysBatch(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* Witness checks (ntru_check_*_batch): check<Kind>Batch(N, params..., signals as Uint16Array [B*N] / [B*(N+1)]..., B,
+ * flags:Uint8Array[B]); the signals in the order of the template's inputs (circuits/ntru.circom). */
+static int get_rows(napi_env env, napi_value *argv, int first, int count, int n_long, size_t N, size_t B, void **out) {
+  for (int i = 0; i < count; i++)
+    if (!get_buf(env, argv[first + i], napi_uint16_array, (i < n_long ? N : N + 1) * B, 0, &out[i])) return 0;
+  return 1;
+}
+
+/* checkEncryptBatch(N, q, nq, r, m, h, quotientE, remainderE, B, flags) */
+static napi_value CheckEncryptBatch(napi_env env, napi_callback_info info) {
+  ARGS(10)
+  int32_t N, q, nq, B; void *a[5], *fl;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &nq) || !get_i32(env, argv[8], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  if (!get_rows(env, argv, 3, 5, 3, (size_t)N, (size_t)B, a) || !get_buf(env, argv[9], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_check_encrypt_batch(g_engine, N, q, nq, a[0], a[1], a[2], a[3], a[4], B, fl));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* checkDecryptBatch(N, q, nq, p, np, f, fp, e, quotient1, remainder1, quotient2, remainder2, B, flags) */
+static napi_value CheckDecryptBatch(napi_env env, napi_callback_info info) {
+  ARGS(14)
+  int32_t N, q, nq, p, np, B; void *a[7], *fl;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &nq) || !get_i32(env, argv[3], &p) ||
+      !get_i32(env, argv[4], &np) || !get_i32(env, argv[12], &B) || N < 1 || B < 0) BAD_ARGS();
+  if (!get_rows(env, argv, 5, 7, 3, (size_t)N, (size_t)B, a) || !get_buf(env, argv[13], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_check_decrypt_batch(g_engine, N, q, nq, p, np, a[0], a[1], a[2], a[3], a[4], a[5], a[6], B, fl));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* checkInverseBatch(N, M, n, f, fq, quotientI, remainderI, B, flags) */
+static napi_value CheckInverseBatch(napi_env env, napi_callback_info info) {
+  ARGS(9)
+  int32_t N, M, n, B; void *a[4], *fl;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &M) || !get_i32(env, argv[2], &n) || !get_i32(env, argv[7], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  if (!get_rows(env, argv, 3, 4, 2, (size_t)N, (size_t)B, a) || !get_buf(env, argv[8], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_check_inverse_batch(g_engine, N, M, n, a[0], a[1], a[2], a[3], B, fl));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
 /* sampleTernary(N, n1, n2, other, key:Uint32Array[8], firstItem:Number, B, out:Uint8Array[B*N]) */
 static napi_value SampleTernary(napi_env env, napi_callback_info info) {
   ARGS(8)
@@ -763,6 +810,9 @@ static napi_value Init(napi_env env, napi_value exports) {
     {"encryptBatch", NULL, EncryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatch", NULL, DecryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"verifyKeysBatch", NULL, VerifyKeysBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"checkEncryptBatch", NULL, CheckEncryptBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"checkDecryptBatch", NULL, CheckDecryptBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"checkInverseBatch", NULL, CheckInverseBatch, NULL, NULL, NULL, napi_default, NULL},
     {"publicKeyBatch", NULL, PublicKeyBatch, NULL, NULL, NULL, napi_default, NULL},
     {"invertKeyBatch", NULL, InvertKeyBatch, NULL, NULL, NULL, napi_default, NULL},
     {"sampleTernary", NULL, SampleTernary, NULL, NULL, NULL, napi_default, NULL},

@@ -533,3 +533,48 @@ export default class NTRU {
       .then(() => ({ value, quotient1: q1, remainder1: r1, quotient2: q2 }));
   }
 }
+
+// ---- witness checks: does a witness satisfy VerifyEncrypt / VerifyDecrypt / VerifyInverse (circuits/ntru.circom)? ----------------
+// checkWitnesses(template, witnesses): witnesses = [{inputs, params}] as encryptBits, decryptBits and verifyKeysInputs()[fq|fp|h]
+// return them, all with the same params; returns one flag value per witness: 0 = accepted, else the OR of EQ 1, TAIL 2, RANGE 4
+// (VerifyDecrypt's mod-p stage shifted left by 3) -- include/ntru_engine.h, NTRU_CHECK_*.
+const CHECK_SIGNALS = {
+  VerifyEncrypt: [['r', 0], ['m', 0], ['h', 0], ['quotientE', 1], ['remainderE', 1]],
+  VerifyDecrypt: [['f', 0], ['fp', 0], ['e', 0], ['quotient1', 1], ['remainder1', 1], ['quotient2', 1], ['remainder2', 1]],
+  VerifyInverse: [['f', 0], ['fq', 0], ['quotientI', 1], ['remainderI', 1]],
+};
+const CHECK_PARAMS = { VerifyEncrypt: 3, VerifyDecrypt: 5, VerifyInverse: 3 };
+
+export function checkWitnesses(template, witnesses) {
+  const signals = CHECK_SIGNALS[template];
+  if (!signals) throw new Error(`checkWitnesses: unknown template ${template} (VerifyEncrypt, VerifyDecrypt or VerifyInverse)`);
+  if (!Array.isArray(witnesses)) throw new Error('checkWitnesses: witnesses must be an array of {inputs, params}');
+  const B = witnesses.length;
+  if (B === 0) return [];
+  const params = witnesses[0].params;
+  if (!Array.isArray(params) || params.length !== CHECK_PARAMS[template] || !params.every(Number.isInteger))
+    throw new Error(`checkWitnesses: ${template} takes ${CHECK_PARAMS[template]} integer params`);
+  const N = params[params.length - 1];
+  const rows = signals.map(([name, extra]) => {
+    const len = N + extra;
+    const out = new Uint16Array(B * len);
+    witnesses.forEach((w, i) => {
+      if (!Array.isArray(w.params) || w.params.length !== params.length || w.params.some((x, j) => x !== params[j]))
+        throw new Error(`checkWitnesses: item ${i} has params ${JSON.stringify(w.params)}, item 0 ${JSON.stringify(params)}`);
+      const v = w.inputs[name];
+      if (!v || v.length !== len) throw new Error(`checkWitnesses: item ${i}: ${name} has length ${v ? v.length : 0}, expected ${len}`);
+      for (let k = 0; k < len; k++) {
+        const x = v[k];
+        if (!Number.isInteger(x) || x < 0 || x > 65535)
+          throw new Error(`checkWitnesses: item ${i}: ${name}[${k}] = ${x} is not an integer in [0, 65535]`);
+        out[i * len + k] = x;
+      }
+    });
+    return out;
+  });
+  const flags = new Uint8Array(B);
+  if (template === 'VerifyEncrypt') engine().checkEncryptBatch(N, params[0], params[1], ...rows, B, flags);
+  else if (template === 'VerifyDecrypt') engine().checkDecryptBatch(N, params[0], params[1], params[2], params[3], ...rows, B, flags);
+  else engine().checkInverseBatch(N, params[0], params[1], ...rows, B, flags);
+  return Array.from(flags);
+}

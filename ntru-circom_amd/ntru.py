@@ -440,3 +440,49 @@ class NTRU:
         bits = self.decryptBits(encrypted)["value"]
         bits = bits + [0] * (-len(bits) % 8)                                     # expandArrayToMultiple(.., 8)
         return bitsToString(bits)
+
+
+# ---- witness checks: VerifyEncrypt / VerifyDecrypt / VerifyInverse (circuits/ntru.circom) on the engine -------------------------
+CHECK_SIGNALS = {"VerifyEncrypt": (("r", 0), ("m", 0), ("h", 0), ("quotientE", 1), ("remainderE", 1)),
+                 "VerifyDecrypt": (("f", 0), ("fp", 0), ("e", 0), ("quotient1", 1), ("remainder1", 1), ("quotient2", 1),
+                                   ("remainder2", 1)),
+                 "VerifyInverse": (("f", 0), ("fq", 0), ("quotientI", 1), ("remainderI", 1))}
+CHECK_PARAMS = {"VerifyEncrypt": 3, "VerifyDecrypt": 5, "VerifyInverse": 3}
+
+
+def checkWitnesses(template, witnesses, engine=None):
+    """Flags of each {inputs, params} witness (as encryptBits, decryptBits and verifyKeysInputs()[fq|fp|h] return them) against
+    the circuit `template`: 0 = the constraint system is satisfied, else the NTRU_CHECK_* bits (EQ 1, TAIL 2, RANGE 4; VerifyDecrypt's
+    mod-p stage shifted left by 3).  Every item must have the same params; every entry must be an integer in [0, 65535]."""
+    if template not in CHECK_SIGNALS:
+        raise ValueError("checkWitnesses: unknown template %r (VerifyEncrypt, VerifyDecrypt or VerifyInverse)" % (template,))
+    witnesses = list(witnesses)
+    if not witnesses:
+        return []
+    params = [int(x) for x in witnesses[0]["params"]]
+    if len(params) != CHECK_PARAMS[template]:
+        raise ValueError("checkWitnesses: %s takes %d params, got %d" % (template, CHECK_PARAMS[template], len(params)))
+    N = params[-1]
+    arrays = []
+    for name, extra in CHECK_SIGNALS[template]:
+        rows = []
+        for i, w in enumerate(witnesses):
+            if [int(x) for x in w["params"]] != params:
+                raise ValueError("checkWitnesses: item %d has params %r, item 0 %r" % (i, list(w["params"]), params))
+            v = w["inputs"].get(name)
+            if v is None:
+                raise ValueError("checkWitnesses: item %d: missing signal %s" % (i, name))
+            if len(v) != N + extra:
+                raise ValueError("checkWitnesses: item %d: %s has length %d, expected %d" % (i, name, len(v), N + extra))
+            if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and 0 <= x <= 65535 for x in v):
+                raise ValueError("checkWitnesses: item %d: %s holds an entry that is not an integer in [0, 65535]" % (i, name))
+            rows.append(v)
+        arrays.append(np.array(rows, np.uint16))
+    eng = engine or default_engine()
+    if template == "VerifyEncrypt":
+        flags = eng.check_encrypt_batch(N, params[0], params[1], *arrays)
+    elif template == "VerifyDecrypt":
+        flags = eng.check_decrypt_batch(N, params[0], params[1], params[2], params[3], *arrays)
+    else:
+        flags = eng.check_inverse_batch(N, params[0], params[1], *arrays)
+    return [int(x) for x in flags]
