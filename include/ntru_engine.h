@@ -202,7 +202,8 @@ int ntru_decrypt_batch_pitched_dev(ntru_engine_t *eng, int N, int q, int p, int 
  * inverse modulo 2, then Newton rounds v <- 2v - f v^2), fp[b] = f[b]^-1 modulo p = 3; f in {-1,0,1}.  The inverse is
  * unique, so for units the result equals the reference's Euclidean algorithm bit for bit.  For f that is not a unit the
  * matching flag is set and the row is zero; the reference throws 'invalid_gcd' / 'invalid fq' for most such f but its
- * `&&` checks (index.js:41-45, :451) accept some and return meaningless polynomials -- that artefact is not reproduced.
+ * `&&` checks (index.js:41-45, :451) accept some and return meaningless polynomials -- that artefact is not reproduced, and neither
+ * does ntru_keygen_batch reproduce it: its redraw keeps the first f that is a unit, where the reference may keep an earlier non-unit.
  * Either of fq / fp may be NULL when only the other inverse is wanted (polyInv(f, I, 3) / polyInv(f, I, q)).
  * The Newton temporaries (4 x 2N bytes per key, at most 65536 keys at a time) live in an engine-owned buffer that only
  * grows; nothing is allocated per call and the _dev form does not synchronise.  [§8(f) #1] */
@@ -210,6 +211,38 @@ int ntru_invert_key_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t 
                           uint8_t *flags);
 int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, int64_t B, uint16_t *d_fq,
                               uint8_t *d_fp, uint8_t *d_flags);
+
+/* ---- key generation: generatePrivateKeyF + generateNewPublicKeyGH (index.js:51-79) for B items in one call, non-units redrawn on the
+ *      device.  Item i = first_item + b (0 <= b < B, first_item + B <= 2^40); every position below is a stream position of
+ *      ntru_sample_ternary, always with the 20-round ChaCha20 stream whatever ntru_engine_set_sampler_rounds says (the engine's setting is
+ *      the same after the call):
+ *        g[b]          row 0 of ntru_sample_ternary(N, dg, dg, 255, key, (1 << 40) + i, 1) as int8 (255 = -1), drawn once;
+ *        attempt t     row 0 of ntru_sample_ternary(N, df, df - 1, 255, key, (t << 44) + i, 1), t = 0 .. max_tries - 1;
+ *        f[b]          the first attempt that is a unit modulo 2 and modulo p; fq[b], fp[b] its inverses, bit-identical to
+ *                      ntru_invert_key_batch; h[b] = ntru_public_key_batch(fq[b], g[b]); tries[b] = t + 1, flags[b] = 0;
+ *        no unit       flags[b] = the NTRU_FLAG_NOT_UNIT_MOD2 / _MODP bits of the last attempt, f[b] = the last attempt, fq, fp and h
+ *                      zero rows, tries[b] = max_tries.  The call still returns NTRU_OK: a failed item is data (the shims throw the
+ *                      reference's 'Could not find invertible f', index.js:63).
+ *      The results of item i depend on (key, i, N, q, df, dg, max_tries) only -- not on B, chunking, the device or the kernel path -- so
+ *      a host replays any item with a stock ChaCha20 ("Generating keys").  Unlike the reference, whose `&&` checks
+ *      (index.js:41-45) accept some non-units, every kept f is a unit (see ntru_invert_key_batch).
+ *      `key` (8 words, a HOST pointer) is secret material: take it from a CSPRNG, and never use it as the key that draws the encryption
+ *      randomness r -- position i of attempt 0 would be the r of item i.
+ *      Domain: p == 3, q a power of two with 2 <= q and p * (q - 1) < 65536 (the public key's domain), 2 <= N <= NTRU_MAX_N, 1 <= df,
+ *      2 df - 1 <= N, 0 <= dg, 2 dg <= N, 1 <= max_tries <= 255; anything else is NTRU_ERR_ARG / NTRU_ERR_UNSUPPORTED before any launch.
+ *   _dev: d_work is a caller-owned device workspace of ntru_keygen_workspace_bytes(N, B) bytes (bounded in B: redraws run in passes of
+ *      at most 4096 rows); nothing is allocated per call.  Every output is needed except d_tries (may be NULL).  Unlike the other _dev
+ *      calls this one SYNCHRONISES the engine's stream: it reads back one 4-byte count of the items still to redraw, once per call and
+ *      once per redraw pass.  Without non-units that is one small kernel and that readback on top of sample -> invert -> public key.
+ *   host form: every output is optional except flags; packed_h [B][output_size][4] = packOutput(q - 1, N, h) (index.js:572-596, sizes
+ *      from ntru_pack_params(q - 1, N, ...)) may be NULL. */
+int ntru_keygen_workspace_bytes(int N, int64_t B, size_t *bytes);
+int ntru_keygen_batch_dev(ntru_engine_t *eng, int N, int q, int p, int df, int dg, const uint32_t *key, uint64_t first_item, int max_tries,
+                          int64_t B, void *d_work, int8_t *d_f, int8_t *d_g, uint16_t *d_fq, uint8_t *d_fp, uint16_t *d_h,
+                          uint8_t *d_tries, uint8_t *d_flags);
+int ntru_keygen_batch(ntru_engine_t *eng, int N, int q, int p, int df, int dg, const uint32_t *key, uint64_t first_item, int max_tries,
+                      int64_t B, int8_t *f, int8_t *g, uint16_t *fq, uint8_t *fp, uint16_t *h, uint8_t *tries, uint8_t *flags,
+                      uint64_t *packed_h);
 
 /* generatePublicKeyH (index.js:72-79) for B keys: h[b] = remainder of ((p * fq[b]) mod q) * g[b] by 1 - x^N, mod q
  * (before trimPolynomial).  fq: mod-q inverse of f, g in {-1,0,1}; p*(q-1) must fit 16 bits.  Per-item operands on both

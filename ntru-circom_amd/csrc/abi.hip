@@ -138,6 +138,7 @@ extern "C" void ntru_engine_destroy(ntru_engine_t *eng) {
   }
   if (eng->shared_dev.p) (void)hipFree(eng->shared_dev.p);
   if (eng->scratch_dev.p) (void)hipFree(eng->scratch_dev.p);
+  if (eng->keygen_work.p) (void)hipFree(eng->keygen_work.p);
   if (eng->scratch_event) (void)hipEventDestroy(eng->scratch_event);
   delete eng;
 }

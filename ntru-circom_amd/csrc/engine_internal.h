@@ -9,6 +9,7 @@
 //   ntru_host.hip            host-pointer entry points: pinned staging, three stage streams, chunked H2D / kernel / D2H pipeline
 //   ntru_generic.hip         reference-faithful generic family (arbitrary divisors, moduli up to 2^26, signed coefficients)
 //   witness_check.hip        witness checks against the Verify* circuits (kernels, *_dev and host-pointer entry points)
+//   keygen_batch.hip         batched key generation with on-device redraws (kernels, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -73,6 +74,7 @@ struct ntru_engine {
   hipEvent_t ev_fork, ev_join;   // vector-ALU bound, runs beside the Newton chain on the matrix cores); created at first use
   GrowBuf shared_dev;       // shared key rows of the host path (h, f, fp)
   GrowBuf scratch_dev;      // temporaries of *_dev calls (Newton rounds, generic family) on the caller's stream
+  GrowBuf keygen_work;      // workspace of the host-pointer ntru_keygen_batch (ntru_keygen_workspace_bytes of one chunk)
   hipStream_t scratch_stream;   // the stream whose work used scratch_dev last, and an event recorded behind that work: a call on
   hipEvent_t scratch_event;     // ANOTHER stream waits for it before it touches the buffer (ntru_scratch_acquire / _release)
   bool scratch_used;

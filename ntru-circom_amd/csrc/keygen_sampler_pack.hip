@@ -4,6 +4,7 @@
 //   BN254 field packing (packOutput / unpackInput, index.js:572-620): k_pack, k_unpack
 //   elementwise: stand-alone dividePolynomials(., I, mod) and addPolynomials on ciphertexts (index.js:358-401, :235-244)
 #include "kernels_common.h"
+#include "sampler_common.h"
 
 // dividePolynomials(a, I, mod) for reduced dividends, elementwise (HBM-bound): a is [B][2N].
 __global__ void k_split_by_I(int N, u32 mod, const u16 *__restrict__ a, long B, u16 *__restrict__ quot,
@@ -51,31 +52,11 @@ __global__ void k_add_mod(u32 mod, const u16 *__restrict__ a, const u16 *__restr
 // N = 821 -> 12 waves per CU, and the launcher asks for as much LDS as makes the resident count a MULTIPLE OF FOUR: the
 // kernel is bound by vector issue, every workgroup is one wave, and 9 waves on 4 SIMDs (what the round-2 layout with its
 // per-wave reciprocal table got) left three SIMDs idle a third of the time (profiles/archive/r03_ablation_sampler.txt).
-// i is wave-uniform: the word that holds position i stays in a register until i leaves it, u32 % (i+1) is a multiply by
-// a reciprocal floor(2^32 / d) that arrives through the scalar cache (constant table, d < 2048; an LDS table above),
-// one 24-bit multiply-subtract (the remainder is below 2d < 2^24, so the product is only needed modulo 2^24) and one
-// correction -- instead of a 35-instruction division.
-struct ChaChaKey { u32 k[8]; };
 // A workgroup is WAVES = 4 independent waves (no barrier, private LDS regions) wherever four rows regions fit the LDS: as TWELVE
 // single-wave workgroups per CU the same kernel took 3.4 ms per 2^20 items at N = 821, as three four-wave workgroups 2.2 ms
 // (profiles/archive/r03_ab_sampler.txt; the inversion kernel, eight single-wave workgroups per CU, does not care: more than eight workgroups
 // per CU do not seem to be resident together, whatever the occupancy query says).
-struct RecipTable {
-  u32 v[2048];
-  constexpr RecipTable() : v() { for (unsigned d = 2; d < 2048; d++) v[d] = (u32)(0x100000000ULL / d); }
-};
-static __constant__ const RecipTable g_recip = RecipTable();
-
-#define CHACHA_QR(a, b, c, d)                                                          \
-  a += b; d ^= a; d = __builtin_rotateleft32(d, 16); c += d; b ^= c; b = __builtin_rotateleft32(b, 12); \
-  a += b; d ^= a; d = __builtin_rotateleft32(d, 8);  c += d; b ^= c; b = __builtin_rotateleft32(b, 7);
-
-// word w (symbols 16 w .. 16 w + 15) of the start row [1]*n1 ++ [2]*n2 ++ [0]*...
-static __device__ __forceinline__ u32 sampler_start_word(int w, int n1, int n2) {
-  auto below = [](int k) { return k <= 0 ? 0u : (k >= 16 ? 0xFFFFFFFFu : (1u << (2 * k)) - 1u); };   // symbols 0 .. k-1 of a word
-  const u32 m1 = below(n1 - 16 * w), m2 = below(n1 + n2 - 16 * w);
-  return (0x55555555u & m1) | (0xAAAAAAAAu & m2 & ~m1);
-}
+// The block function, reciprocal table, start row and shuffle walk are in sampler_common.h (shared with keygen_batch.hip).
 
 // DR: double rounds of the block function: 10 = ChaCha20 (RFC 8439, the default), 6 = ChaCha12, 4 = ChaCha8 (ntru_engine_set_sampler_rounds:
 // the kernel is bound by the vector issue of these rounds; generateCustomArray's contract is the shuffle and its `u32 % (i + 1)` draws,
@@ -93,59 +74,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_sample_ternary(int N, int n1, in
     for (int d = lane; d <= N; d += 64) recip_l[d] = d >= 2 ? (u32)(0x100000000ULL / (unsigned)d) : 0u;
     wave_lds_fence();
   }
-  auto recip_of = [&](int d) -> u32 { return d < 2 ? 0u : (BIGN ? recip_l[d] : g_recip.v[d]); };
   u32 *col = rows + lane;                                // word w of this lane's row: col[64 w]
   const bool out_aligned = (((unsigned long long)out) & 15) == 0 && N >= 16;
   for (long base = ((long)blockIdx.x * WAVES + wave) * 64; base < B; base += (long)gridDim.x * WAVES * 64) {
     for (int w = 0; w < NW; w++) col[64 * w] = sampler_start_word(w, n1, n2);
     const unsigned long long item = first_item + (unsigned long long)(base + lane);
-    const u32 n0 = (u32)item, nn1 = (u32)(item >> 32), nn2 = 0x4e545255u;
-    int i = N - 1;
-    u32 a = col[64 * (i >> 4)];                          // the word that holds position i
-    for (u32 ctr = 0; i >= 1; ctr++) {                  // i is the same in every lane: uniform loop
-      u32 rc[16];
-      if (!BIGN) {                                       // requested now, needed after the rounds
-#pragma unroll
-        for (int w = 0; w < 16; w++) rc[w] = recip_of(i + 1 - w);
-      }
-      u32 x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
-      u32 x4 = key.k[0], x5 = key.k[1], x6 = key.k[2], x7 = key.k[3], x8 = key.k[4], x9 = key.k[5], x10 = key.k[6],
-          x11 = key.k[7], x12 = ctr, x13 = n0, x14 = nn1, x15 = nn2;
-#pragma unroll
-      for (int r = 0; r < DR; r++) {
-        CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
-        CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
-      }
-      const u32 ks[16] = {x0 + 0x61707865u, x1 + 0x3320646eu, x2 + 0x79622d32u, x3 + 0x6b206574u,
-                          x4 + key.k[0], x5 + key.k[1], x6 + key.k[2], x7 + key.k[3], x8 + key.k[4], x9 + key.k[5],
-                          x10 + key.k[6], x11 + key.k[7], x12 + ctr, x13 + n0, x14 + nn1, x15 + nn2};
-#pragma unroll
-      for (int w = 0; w < 16; w++) {
-        if (i >= 1) {
-          const u32 d = (u32)(i + 1);
-          const u32 hi = __umulhi(ks[w], BIGN ? recip_of((int)d) : rc[w]);
-          u32 j;                                                         // ks - hi d is in [0, 2d): its low 24 bits are all of it
-          asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(j) : "v"(hi), "s"(0 - (int)d), "v"(ks[w]));
-          j &= 0xFFFFFFu;
-          j = min(j, j - d);
-          const int wi = i >> 4, si = 2 * (i & 15), wj = (int)(j >> 4), sj = 2 * (int)(j & 15);
-          const u32 bl = col[64 * wj];
-          const bool same = wj == wi;
-          const u32 b = same ? a : bl;
-          const u32 x = ((a >> si) ^ (b >> sj)) & 3u;                    // swap two 2-bit fields by their difference
-          a ^= x << si;
-          const u32 nb = (same ? a : b) ^ (x << sj);
-          col[64 * wj] = nb;
-          a = same ? nb : a;
-          i--;
-          if ((i & 15) == 15) {                                          // uniform: position i has moved into the word below
-            col[64 * wi] = a;
-            a = col[64 * (i >> 4)];
-          }
-        }
-      }
-    }
-    col[0] = a;                                          // i == 0: the register copy of word 0 (N == 1: unchanged)
+    sampler_shuffle_row<BIGN, DR>(col, N, key, (u32)item, (u32)(item >> 32), SAMPLER_NONCE2, recip_l);
     wave_lds_fence();
     if (out_aligned && base + 64 <= B) {
       // rows -> row-major byte output.  The 64 rows of the block are ONE contiguous run of 64 N bytes that starts on a 64-byte

@@ -87,6 +87,9 @@ for _sfx in ("", "_dev"):
     _SIGS["ntru_check_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _vp])
     _SIGS["ntru_check_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i64, _vp])
     _SIGS["ntru_check_inverse_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 4 + [_i64, _vp])
+_SIGS["ntru_keygen_workspace_bytes"] = (C.c_int, [_i, _i64, C.POINTER(C.c_size_t)])
+_SIGS["ntru_keygen_batch_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
+_SIGS["ntru_keygen_batch"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
 _SIGS["ntru_encrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
 _SIGS["ntru_decrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
 
@@ -456,6 +459,45 @@ class Engine:
         """polyInv per row (index.js:491-514) -> (inverses, status[B])."""
         r = self._generic(3, a, poly_i, mod, False)
         return r[0], r[2]
+
+    # ---- key generation (generatePrivateKeyF + generateNewPublicKeyGH for B items, non-units redrawn on the device) -----------
+    def keygen_workspace_bytes(self, N, B):
+        n = C.c_size_t()
+        self._chk(self._lib.ntru_keygen_workspace_bytes(int(N), int(B), C.byref(n)))
+        return int(n.value)
+
+    def keygen_batch(self, N, q, p, df, dg, key, B, first_item=0, max_tries=100, want=("f", "g", "fq", "fp", "h", "tries"),
+                     packed_h=False, out=None):
+        """ntru_keygen_batch: item i = first_item + b from the stream positions of include/ntru_engine.h.  Returns a dict of numpy
+        arrays: `flags` always, the arrays named in `want` (f, g int8 [B][N]; fq, h uint16; fp uint8; tries uint8 [B]), and
+        `packed_h` ([B][output_size][4] uint64, packOutput(q - 1, N, h)) on request.  out: dict of preallocated arrays to fill
+        (e.g. from pinned_empty)."""
+        key = _np(key, np.uint32, (8,))
+        B = int(B)
+        shapes = {"f": ((B, N), np.int8), "g": ((B, N), np.int8), "fq": ((B, N), np.uint16), "fp": ((B, N), np.uint8),
+                  "h": ((B, N), np.uint16), "tries": ((B,), np.uint8), "flags": ((B,), np.uint8)}
+        if packed_h:
+            shapes["packed_h"] = ((B, self.pack_params(q - 1, N)["outputSize"], 4), np.uint64)
+        out = dict(out or {})
+        res = {}
+        for name, (shape, dt) in shapes.items():
+            if name in out:
+                res[name] = out[name]
+                assert res[name].dtype == dt and res[name].shape == shape and res[name].flags.c_contiguous, name
+            elif name in want or name in ("flags", "packed_h"):
+                res[name] = np.empty(shape, dt)
+        g = lambda n: _ptr(res.get(n))
+        self._chk(self._lib.ntru_keygen_batch(self._h, N, q, p, df, dg, _ptr(key), int(first_item), int(max_tries), B, g("f"), g("g"),
+                                              g("fq"), g("fp"), g("h"), g("tries"), g("flags"), g("packed_h")))
+        return res
+
+    def keygen_batch_dev(self, N, q, p, df, dg, key, first_item, max_tries, B, d_work, d_f, d_g, d_fq, d_fp, d_h, d_tries, d_flags):
+        """ntru_keygen_batch_dev on device pointers; d_work of keygen_workspace_bytes(N, B) bytes.  Synchronises the engine's stream
+        (one 4-byte readback per call and per redraw pass)."""
+        key = _np(key, np.uint32, (8,))
+        dp = self._dp
+        self._chk(self._lib.ntru_keygen_batch_dev(self._h, N, q, p, df, dg, _ptr(key), int(first_item), int(max_tries), int(B), dp(d_work),
+                                                  dp(d_f), dp(d_g), dp(d_fq), dp(d_fp), dp(d_h), dp(d_tries), dp(d_flags)))
 
     def invert_key_batch_dev(self, N, q, p, d_f, B, d_fq, d_fp, d_flags):
         dp = self._dp

@@ -654,6 +654,138 @@ static napi_value PackBatchDev(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* verifyKeysBatchDev(N, q, p, f, g:handle[B*N i8], fq:handle[B*N u16], fp:handle[B*N u8], h:handle[B*N u16], B,
+ *                    quotFq, remFq:handle[B*N u16], quotFp, remFp:handle[B*N u8], quotH, remH:handle[B*N u16], flags:handle[B]) */
+static napi_value VerifyKeysBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(16)
+  int32_t N, q, p, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(3, n, 0, f) DEV(4, n, 0, g) DEV(5, 2 * n, 0, fq) DEV(6, n, 0, fp) DEV(7, 2 * n, 0, h)
+  DEV(9, 2 * n, 0, o1) DEV(10, 2 * n, 0, o2) DEV(11, n, 0, o3) DEV(12, n, 0, o4) DEV(13, 2 * n, 0, o5) DEV(14, 2 * n, 0, o6)
+  DEV(15, (size_t)B, 0, fl)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_verify_keys_batch_dev(g_engine, N, q, p, f->p, g->p, fq->p, fp->p, h->p, B, o1->p, o2->p, o3->p, o4->p, o5->p,
+                                             o6->p, fl->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* invertKeyBatchDev(N, q, p, f:handle[B*N i8], B, fq:handle[B*N u16]|null, fp:handle[B*N u8]|null, flags:handle[B]) */
+static napi_value InvertKeyBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(8)
+  int32_t N, q, p, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[4], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(3, n, 0, f) DEV(5, 2 * n, 1, fq) DEV(6, n, 1, fp) DEV(7, (size_t)B, 0, fl)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_invert_key_batch_dev(g_engine, N, q, p, f->p, B, fq ? fq->p : NULL, fp ? fp->p : NULL, fl->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* publicKeyBatchDev(N, q, p, fq:handle[B*N u16], g:handle[B*N i8], B, h:handle[B*N u16]) */
+static napi_value PublicKeyBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(7)
+  int32_t N, q, p, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[5], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(3, 2 * n, 0, fq) DEV(4, n, 0, g) DEV(6, 2 * n, 0, h)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_public_key_batch_dev(g_engine, N, q, p, fq->p, g->p, B, h->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* polymulSplitDev(N, mod, a:handle[B*N u16], b:handle[B*N u16], B, quot:handle[B*N u16], rem:handle[B*N u16]) */
+static napi_value PolymulSplitDev(napi_env env, napi_callback_info info) {
+  ARGS(7)
+  int32_t N, mod, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[4], &B) || N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(2, 2 * n, 0, a) DEV(3, 2 * n, 0, b) DEV(5, 2 * n, 0, quot) DEV(6, 2 * n, 0, rem)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_polymul_split_dev(g_engine, N, mod, a->p, b->p, B, quot->p, rem->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* ---- key generation (ntru_keygen_batch): generatePrivateKeyF + generateNewPublicKeyGH for B items, non-units redrawn on the device.
+ * keygenWorkspaceBytes(N, B) -> bytes of the workspace handle keygenBatchDev needs */
+static napi_value KeygenWorkspaceBytes(napi_env env, napi_callback_info info) {
+  ARGS(2)
+  int32_t N, B;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &B) || B < 0) BAD_ARGS();
+  size_t bytes = 0;
+  int rc = ntru_keygen_workspace_bytes(N, B, &bytes);
+  if (rc) return throw_engine(env, rc);
+  napi_value v;
+  NAPI_OK(napi_create_double(env, (double)bytes, &v));
+  return v;
+}
+
+/* The arguments shared by keygenBatch / keygenBatchAsync: (N, q, p, df, dg, key:Uint32Array[8], firstItem, maxTries, B,
+ * f:Int8Array|null, g:Int8Array|null, fq:Uint16Array|null, fp:Uint8Array|null, h:Uint16Array|null, tries:Uint8Array|null,
+ * flags:Uint8Array[B], packedH:BigUint64Array[B*outputSize*4]|null); ptr = key, f, g, fq, fp, h, tries, flags, packedH. */
+typedef struct { int32_t N, q, p, df, dg, max_tries, B; uint64_t first; void *ptr[9]; } KeygenArgs;
+static int keygen_args(napi_env env, napi_value *argv, KeygenArgs *a) {
+  double first;
+  if (!get_i32(env, argv[0], &a->N) || !get_i32(env, argv[1], &a->q) || !get_i32(env, argv[2], &a->p) || !get_i32(env, argv[3], &a->df) ||
+      !get_i32(env, argv[4], &a->dg) || napi_get_value_double(env, argv[6], &first) != napi_ok || !get_i32(env, argv[7], &a->max_tries) ||
+      !get_i32(env, argv[8], &a->B) || a->N < 1 || a->B < 0 || first < 0 || first > 9007199254740991.0) return 0;
+  a->first = (uint64_t)first;
+  const size_t n = (size_t)a->N * (size_t)a->B;
+  size_t need_packed = 0;
+  int bits, per, al, os;
+  if (ntru_pack_params(a->q - 1, a->N, &bits, &per, &al, &os) == 0) need_packed = (size_t)a->B * (size_t)os * 4;
+  return get_buf(env, argv[5], napi_uint32_array, 8, 0, &a->ptr[0]) && get_buf(env, argv[9], napi_int8_array, n, 1, &a->ptr[1]) &&
+         get_buf(env, argv[10], napi_int8_array, n, 1, &a->ptr[2]) && get_buf(env, argv[11], napi_uint16_array, n, 1, &a->ptr[3]) &&
+         get_buf(env, argv[12], napi_uint8_array, n, 1, &a->ptr[4]) && get_buf(env, argv[13], napi_uint16_array, n, 1, &a->ptr[5]) &&
+         get_buf(env, argv[14], napi_uint8_array, (size_t)a->B, 1, &a->ptr[6]) &&
+         get_buf(env, argv[15], napi_uint8_array, (size_t)a->B, 0, &a->ptr[7]) &&
+         get_buf(env, argv[16], napi_biguint64_array, need_packed, 1, &a->ptr[8]);
+}
+static int keygen_run(const KeygenArgs *a) {
+  return ntru_keygen_batch(g_engine, a->N, a->q, a->p, a->df, a->dg, a->ptr[0], a->first, a->max_tries, a->B, a->ptr[1], a->ptr[2],
+                           a->ptr[3], a->ptr[4], a->ptr[5], a->ptr[6], a->ptr[7], a->ptr[8]);
+}
+
+/* keygenBatch(...the arguments above...): host arrays; returns when every asked-for array is filled */
+static napi_value KeygenBatch(napi_env env, napi_callback_info info) {
+  ARGS(17)
+  KeygenArgs a;
+  if (!keygen_args(env, argv, &a)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, keygen_run(&a));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* keygenBatchDev(N, q, p, df, dg, key:Uint32Array[8], firstItem, maxTries, B, work:handle[keygenWorkspaceBytes(N, B)],
+ *                f, g:handle[B*N i8], fq:handle[B*N u16], fp:handle[B*N u8], h:handle[B*N u16], tries:handle[B]|null, flags:handle[B])
+ * Waits for the engine's stream once per call and once per redraw pass (a 4-byte count). */
+static napi_value KeygenBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(17)
+  int32_t N, q, p, df, dg, max_tries, B; double first; void *key; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[3], &df) ||
+      !get_i32(env, argv[4], &dg) || napi_get_value_double(env, argv[6], &first) != napi_ok || !get_i32(env, argv[7], &max_tries) ||
+      !get_i32(env, argv[8], &B) || N < 1 || B < 0 || first < 0 || first > 9007199254740991.0 ||
+      !get_buf(env, argv[5], napi_uint32_array, 8, 0, &key)) BAD_ARGS();
+  size_t wbytes = 0;
+  int rc = ntru_keygen_workspace_bytes(N, B, &wbytes);
+  if (rc) return throw_engine(env, rc);
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(9, wbytes, 0, work) DEV(10, n, 0, f) DEV(11, n, 0, g) DEV(12, 2 * n, 0, fq) DEV(13, n, 0, fp) DEV(14, 2 * n, 0, h)
+  DEV(15, (size_t)B, 1, tries) DEV(16, (size_t)B, 0, fl)
+  if (!ensure_engine(env)) return NULL;
+  ENGINE_CALL(rc, ntru_keygen_batch_dev(g_engine, N, q, p, df, dg, key, (uint64_t)first, max_tries, B, work->p, f->p, g->p, fq->p, fp->p,
+                                        h->p, tries ? tries->p : NULL, fl->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
 /* ---- asynchronous batch calls (additive; the reference API stays synchronous).  encryptBatchAsync / decryptBatchAsync take
  *      the arguments of their synchronous twins and return a Promise; the engine call runs on a libuv worker thread, so the
  *      event loop keeps turning while a 2^18-item batch (tens of milliseconds of PCIe) is in flight.  The typed arrays are
@@ -663,10 +795,11 @@ typedef struct {
   napi_deferred deferred;
   napi_ref keep[12];
   int n_keep;
-  int kind;                       /* 0 encrypt, 1 decrypt, 2 pipeline */
+  int kind;                       /* 0 encrypt, 1 decrypt, 2 pipeline, 3 keygen */
   int N, q, p, B, n1, n2;
   uint64_t first;
   void *ptr[12];
+  KeygenArgs keygen;
   int rc;
   char err[400];
 } AsyncJob;
@@ -680,6 +813,8 @@ static void async_execute(napi_env env, void *data) {
     if (j->kind == 0)
       j->rc = g_multi ? ntru_multi_encrypt_batch(g_multi, j->N, j->q, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4])
                       : ntru_encrypt_batch(g_engine, j->N, j->q, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4]);
+    else if (j->kind == 3)
+      j->rc = keygen_run(&j->keygen);
     else if (j->kind == 2)
       j->rc = ntru_pipeline_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->ptr[3], j->first, j->n1, j->n2, j->ptr[4],
                                   j->ptr[5], j->B, j->ptr[6], j->ptr[7], j->ptr[8], j->ptr[9]);
@@ -796,6 +931,19 @@ static napi_value PipelineBatchAsync(napi_env env, napi_callback_info info) {
   return async_start(env, j, hold, 10, "ntru.pipelineAsync");
 }
 
+/* keygenBatchAsync(...the arguments of keygenBatch...) -> Promise<undefined> */
+static napi_value KeygenBatchAsync(napi_env env, napi_callback_info info) {
+  ARGS(17)
+  KeygenArgs a;
+  if (!keygen_args(env, argv, &a)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
+  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  j->kind = 3; j->keygen = a;
+  napi_value hold[9] = {argv[5], argv[9], argv[10], argv[11], argv[12], argv[13], argv[14], argv[15], argv[16]};
+  return async_start(env, j, hold, 9, "ntru.keygenBatchAsync");
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
     {"deviceCount", NULL, DeviceCount, NULL, NULL, NULL, napi_default, NULL},
@@ -834,6 +982,14 @@ static napi_value Init(napi_env env, napi_value exports) {
     {"packBatchDev", NULL, PackBatchDev, NULL, NULL, NULL, napi_default, NULL},
     {"encryptBatchAsync", NULL, EncryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatchAsync", NULL, DecryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
+    {"verifyKeysBatchDev", NULL, VerifyKeysBatchDev, NULL, NULL, NULL, napi_default, NULL},
+    {"invertKeyBatchDev", NULL, InvertKeyBatchDev, NULL, NULL, NULL, napi_default, NULL},
+    {"publicKeyBatchDev", NULL, PublicKeyBatchDev, NULL, NULL, NULL, napi_default, NULL},
+    {"polymulSplitDev", NULL, PolymulSplitDev, NULL, NULL, NULL, napi_default, NULL},
+    {"keygenWorkspaceBytes", NULL, KeygenWorkspaceBytes, NULL, NULL, NULL, napi_default, NULL},
+    {"keygenBatch", NULL, KeygenBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"keygenBatchAsync", NULL, KeygenBatchAsync, NULL, NULL, NULL, napi_default, NULL},
+    {"keygenBatchDev", NULL, KeygenBatchDev, NULL, NULL, NULL, napi_default, NULL},
   };
   if (napi_define_properties(env, exports, sizeof props / sizeof props[0], props) != napi_ok) return NULL;
   return exports;

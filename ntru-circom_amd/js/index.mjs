@@ -511,6 +511,61 @@ export default class NTRU {
     engine().decryptBatchDev(this.N, this.q, this.p, fDev, fpDev, eDev, B, valueDev, q1Dev, r1Dev, q2Dev);
   }
   static packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes = false) { engine().packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes); }
+  // per-item key products on device buffers (f, g: Int8 rows; fq, h and every quotient / remainder of fq and h: Uint16 rows; fp and its
+  // quotient / remainder: Uint8 rows; flags: one byte per item)
+  verifyKeysBatchDev(fDev, gDev, fqDev, fpDev, hDev, B, quotFqDev, remFqDev, quotFpDev, remFpDev, quotHDev, remHDev, flagsDev) {
+    engine().verifyKeysBatchDev(this.N, this.q, this.p, fDev, gDev, fqDev, fpDev, hDev, B, quotFqDev, remFqDev, quotFpDev, remFpDev,
+      quotHDev, remHDev, flagsDev);
+  }
+  invertKeyBatchDev(fDev, B, fqDev, fpDev, flagsDev) { engine().invertKeyBatchDev(this.N, this.q, this.p, fDev, B, fqDev, fpDev, flagsDev); }
+  publicKeyBatchDev(fqDev, gDev, B, hDev) { engine().publicKeyBatchDev(this.N, this.q, this.p, fqDev, gDev, B, hDev); }
+  static polymulSplitDev(N, mod, aDev, bDev, B, quotDev, remDev) { engine().polymulSplitDev(N, mod, aDev, bDev, B, quotDev, remDev); }
+
+  // ---- batched key generation: generatePrivateKeyF + generateNewPublicKeyGH (index.js:51-79) for B items, non-units redrawn on the GPU.
+  // key: Uint32Array[8], secret (fill it from crypto.randomFillSync; never the key that draws r).  Item i = firstItem + b draws g at
+  // ChaCha20 stream position 2^40 + i and attempt t of f at t * 2^44 + i (include/ntru_engine.h, ntru_keygen_batch): any host can replay
+  // it.  want: which arrays come back ({ f, g, fq, fp, h, tries }, default all); flags always (nonzero: no invertible f in maxTries
+  // draws); pack: also packedH = packOutput(q - 1, N, h) as BigUint64Array[B*outputSize*4].  Arrays in `out` are filled in place.
+  generateKeysBatch(opts) { return this._keygen(opts, false); }
+  generateKeysBatchAsync(opts) { return this._keygen(opts, true); }
+  _keygen({ B, key, firstItem = 0, maxTries = 100, want = null, pack = false, out = {} }, asynchronous) {
+    const { N, p, q, df, dg } = this;
+    if (!(key instanceof Uint32Array) || key.length < 8) throw new TypeError('generateKeysBatch: key must be a Uint32Array[8]');
+    const w = want || { f: true, g: true, fq: true, fp: true, h: true, tries: true };
+    const rows = { f: Int8Array, g: Int8Array, fq: Uint16Array, fp: Uint8Array, h: Uint16Array };
+    const res = { B };
+    for (const [name, T] of Object.entries(rows)) if (w[name]) res[name] = out[name] || new T(B * N);
+    if (w.tries) res.tries = out.tries || new Uint8Array(B);
+    res.flags = out.flags || new Uint8Array(B);
+    if (pack) {
+      res.outputSize = engine().packParams(q - 1, N)[3];
+      res.packedH = out.packedH || new BigUint64Array(B * res.outputSize * 4);
+    }
+    const args = [N, q, p, df, dg, key, firstItem, maxTries, B, res.f || null, res.g || null, res.fq || null, res.fp || null,
+      res.h || null, res.tries || null, res.flags, res.packedH || null];
+    if (asynchronous) return engine().keygenBatchAsync(...args).then(() => res);
+    engine().keygenBatch(...args);
+    return res;
+  }
+  // The same on device buffers: workDev of NTRU.keygenWorkspaceBytes(N, B) bytes, f, g (B*N bytes), fq, h (2*B*N), fp (B*N), tries (B,
+  // may be null), flags (B).  Waits for the GPU once per call and once per redraw pass (a 4-byte count of the items left to redraw).
+  generateKeysBatchDev({ B, key, firstItem = 0, maxTries = 100, workDev, fDev, gDev, fqDev, fpDev, hDev, triesDev = null, flagsDev }) {
+    engine().keygenBatchDev(this.N, this.q, this.p, this.df, this.dg, key, firstItem, maxTries, B, workDev, fDev, gDev, fqDev, fpDev,
+      hDev, triesDev, flagsDev);
+  }
+  static keygenWorkspaceBytes(N, B) { return engine().keygenWorkspaceBytes(N, B); }
+  // f, fq, fp, g, h of item i of a generateKeysBatch result, as generatePrivateKeyF + generateNewPublicKeyGH leave them.
+  loadKeyFromBatch(keys, i) {
+    if (keys.flags[i]) throw new Error('Could not find invertible f');
+    const { N } = this;
+    const row = a => Array.from(a.subarray(i * N, (i + 1) * N));
+    this.f = row(keys.f);
+    this.fq = trimPolynomial(row(keys.fq));
+    this.fp = trimPolynomial(row(keys.fp));
+    this.g = row(keys.g);
+    this.h = trimPolynomial(row(keys.h));
+    return this;
+  }
 
   // Promise-returning twins of the two batch calls: the engine call runs on a libuv worker thread, the event loop keeps
   // turning meanwhile (calls are serialised inside the addon: one engine).  Same arguments, same results; the input and

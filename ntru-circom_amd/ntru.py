@@ -369,6 +369,25 @@ class NTRU:
         self.g = generateCustomArray(self.N, self.dg, self.dg)
         self.generatePublicKeyH()
 
+    # -- batched key generation: generatePrivateKeyF + generateNewPublicKeyGH (index.js:51-79) for B items on the device --------
+    def generateKeysBatch(self, B, key, firstItem=0, maxTries=100):
+        """B key pairs from the ChaCha20 stream under `key` (8 uint32, secret: take it from a CSPRNG, never the key that draws r):
+        item i = firstItem + b, positions as include/ntru_engine.h ntru_keygen_batch says.  Returns the engine's dict of arrays
+        (f, g, fq, fp, h, tries, flags); a nonzero flags[b] is an item for which no f of maxTries draws was invertible."""
+        return self.engine.keygen_batch(self.N, self.q, self.p, self.df, self.dg, key, B, first_item=firstItem, max_tries=maxTries)
+
+    def loadKeyFromBatch(self, keys, i):
+        """Sets f, fq, fp, g, h from item i of generateKeysBatch as generatePrivateKeyF + generateNewPublicKeyGH leave them: f and g
+        signed length-N lists, fq, fp and h trimmed.  Throws the reference's 'Could not find invertible f' for a failed item."""
+        if int(keys["flags"][i]):
+            raise ValueError("Could not find invertible f")
+        self.f = [int(x) for x in keys["f"][i]]
+        self.fq = trimPolynomial([int(x) for x in keys["fq"][i]])
+        self.fp = trimPolynomial([int(x) for x in keys["fp"][i]])
+        self.g = [int(x) for x in keys["g"][i]]
+        self.h = trimPolynomial([int(x) for x in keys["h"][i]])
+        return self
+
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
         """h = trim((p*fq mod q) * g mod (x^N - 1, q)) on the device."""
