@@ -182,6 +182,26 @@ int ntru_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t
                            const uint16_t *d_e, int64_t B, uint8_t *d_value, uint16_t *d_quot1,
                            uint16_t *d_rem1, uint8_t *d_quot2);
 
+/* ---- the same two operations with a SEPARATE key pair for every item (one ciphertext per recipient, one decryption per key
+ *      holder): h, f and fp are [B][N] batch arrays with the types and layout of ntru_keygen_batch's outputs, so its device arrays
+ *      feed straight in.  Row b of every result is exactly what ntru_encrypt_batch / ntru_decrypt_batch return for item b's input
+ *      under item b's key: every witness array, the centred lift, the symbol preconditions, any byte of m added mod q.  The witness
+ *      outputs (quotE; quot1, rem1, quot2) may be NULL.  Domain as above: 2 <= N <= NTRU_MAX_N, q a power of two <= 65536,
+ *      ntru_engine_supports(N, p); anything else is NTRU_ERR_ARG / NTRU_ERR_UNSUPPORTED before any launch, B == 0 launches nothing.
+ *      128 <= N <= 1024 (64 with kernel path 4), q <= 8192 (and p == 3 for decrypt) run on the int8 matrix cores, one item per
+ *      wavefront (k_encrypt_pi_m, k_decrypt_pi_m); elsewhere, and on kernel paths 1-3, the call composes per-item products
+ *      (ntru_polymul_split_dev) with elementwise steps, its temporaries in an engine-owned buffer that only grows.  The _dev forms
+ *      do not synchronise and allocate nothing per call; the host forms run the chunked pipeline. */
+int ntru_encrypt_peritem_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *m,
+                               int64_t B, uint16_t *e, uint16_t *quotE);
+int ntru_encrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r,
+                                   const uint8_t *d_m, int64_t B, uint16_t *d_e, uint16_t *d_quotE);
+int ntru_decrypt_peritem_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e,
+                               int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2);
+int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
+                                   const uint16_t *d_e, int64_t B, uint8_t *d_value, uint16_t *d_quot1,
+                                   uint16_t *d_rem1, uint8_t *d_quot2);
+
 /* The same two operations on PITCHED batch arrays: row b of every batch array (r, m, e, quotE / e, value, quot1, rem1,
  * quot2) starts at element b * ld of its array, ld >= N elements (so 2 * ld bytes for the uint16 arrays and ld bytes for
  * the byte arrays); each array holds B * ld elements, the ld - N pad elements of a row are neither read into the result

@@ -60,6 +60,8 @@ for _sfx in ("", "_dev"):
     _SIGS["ntru_add_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _i64, _vp])
     _SIGS["ntru_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
     _SIGS["ntru_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
+    _SIGS["ntru_encrypt_peritem_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
+    _SIGS["ntru_decrypt_peritem_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
     _SIGS["ntru_verify_keys_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64] + [_vp] * 7)
 _SIGS["ntru_pack_bytes_batch_dev"] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp])
 _SIGS["ntru_pipeline_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
@@ -321,6 +323,34 @@ class Engine:
                                                _ptr(q1), _ptr(r1), _ptr(q2)))
         return value, q1, r1, q2
 
+    def encrypt_peritem_batch(self, N, q, h, r, m, want_quot=True):
+        """encrypt_batch with a separate public key per item: h, r, m are [B][N]; row b of e / quotE is encrypt_batch of row b
+        under h[b]."""
+        h = _np(h, np.uint16).reshape(-1, N)
+        r, m = _np(r, np.uint8).reshape(-1, N), _np(m, np.uint8).reshape(-1, N)
+        B = r.shape[0]
+        if h.shape[0] != B or m.shape[0] != B:
+            raise ValueError("encrypt_peritem_batch: h, r and m need the same number of rows")
+        e = np.empty((B, N), np.uint16)
+        quot = np.empty((B, N), np.uint16) if want_quot else None
+        self._chk(self._lib.ntru_encrypt_peritem_batch(self._h, N, q, _ptr(h), _ptr(r), _ptr(m), B, _ptr(e), _ptr(quot)))
+        return e, quot
+
+    def decrypt_peritem_batch(self, N, q, p, f, fp, e, want_witness=True):
+        """decrypt_batch with a separate private key per item: f, fp, e are [B][N]; row b is decrypt_batch of e[b] under f[b], fp[b]."""
+        f, fp = _np(f, np.int8).reshape(-1, N), _np(fp, np.uint8).reshape(-1, N)
+        e = _np(e, np.uint16).reshape(-1, N)
+        B = e.shape[0]
+        if f.shape[0] != B or fp.shape[0] != B:
+            raise ValueError("decrypt_peritem_batch: f, fp and e need the same number of rows")
+        value = np.empty((B, N), np.uint8)
+        q1 = np.empty((B, N), np.uint16) if want_witness else None
+        r1 = np.empty((B, N), np.uint16) if want_witness else None
+        q2 = np.empty((B, N), np.uint8) if want_witness else None
+        self._chk(self._lib.ntru_decrypt_peritem_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(value),
+                                                       _ptr(q1), _ptr(r1), _ptr(q2)))
+        return value, q1, r1, q2
+
     def verify_keys_batch(self, N, q, p, f, g, fq, fp, h):
         f, g = _np(f, np.int8).reshape(-1, N), _np(g, np.int8).reshape(-1, N)
         fq, h = _np(fq, np.uint16).reshape(-1, N), _np(h, np.uint16).reshape(-1, N)
@@ -559,6 +589,19 @@ class Engine:
             self._chk(self._lib.ntru_decrypt_batch_pitched_dev(self._h, N, q, p, int(ld), dp(d_f), dp(d_fp), dp(d_e), B,
                                                                dp(d_value), dp(d_quot1), dp(d_rem1), dp(d_quot2)))
         self._note(N, B, (3 + (2 if d_quot1 else 0) + (2 if d_rem1 else 0) + (1 if d_quot2 else 0)) * N)
+
+    def encrypt_peritem_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_quotE=None):
+        """d_h: [B][N] public keys, one per item."""
+        dp = self._dp
+        self._chk(self._lib.ntru_encrypt_peritem_batch_dev(self._h, N, q, dp(d_h), dp(d_r), dp(d_m), B, dp(d_e), dp(d_quotE)))
+        self._note(N, B, (6 if d_quotE else 4) * N + 2 * N)      # h, r, m in; e (+ quotientE) out
+
+    def decrypt_peritem_batch_dev(self, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1=None, d_rem1=None, d_quot2=None):
+        """d_f, d_fp: [B][N] private keys, one per item."""
+        dp = self._dp
+        self._chk(self._lib.ntru_decrypt_peritem_batch_dev(self._h, N, q, p, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_value),
+                                                           dp(d_quot1), dp(d_rem1), dp(d_quot2)))
+        self._note(N, B, (5 + (2 if d_quot1 else 0) + (2 if d_rem1 else 0) + (1 if d_quot2 else 0)) * N)
 
     def verify_keys_batch_dev(self, N, q, p, d_f, d_g, d_fq, d_fp, d_h, B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp,
                               d_quot_h, d_rem_h, d_flags):

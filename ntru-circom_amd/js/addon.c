@@ -240,6 +240,40 @@ static napi_value DecryptBatch(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* encryptPeritemBatch(N, q, h:Uint16Array[B*N], r:Uint8Array[B*N], m:Uint8Array[B*N], B, e:Uint16Array, quotE:Uint16Array|null):
+ * row b under key b (ntru_encrypt_peritem_batch) */
+static napi_value EncryptPeritemBatch(napi_env env, napi_callback_info info) {
+  ARGS(8)
+  int32_t N, q, B; void *h, *r, *m, *e, *quot;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
+  size_t n = (size_t)N * (size_t)B;
+  if (!get_buf(env, argv[2], napi_uint16_array, n, 0, &h) || !get_buf(env, argv[3], napi_uint8_array, n, 0, &r) ||
+      !get_buf(env, argv[4], napi_uint8_array, n, 0, &m) || !get_buf(env, argv[6], napi_uint16_array, n, 0, &e) ||
+      !get_buf(env, argv[7], napi_uint16_array, n, 1, &quot)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_encrypt_peritem_batch(g_engine, N, q, h, r, m, B, e, quot));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* decryptPeritemBatch(N, q, p, f:Int8Array[B*N], fp:Uint8Array[B*N], e:Uint16Array[B*N], B, value:Uint8Array,
+ *                     quot1:Uint16Array|null, rem1:Uint16Array|null, quot2:Uint8Array|null): row b under key b */
+static napi_value DecryptPeritemBatch(napi_env env, napi_callback_info info) {
+  ARGS(11)
+  int32_t N, q, p, B; void *f, *fp, *e, *value, *q1, *r1, *q2;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
+      !get_i32(env, argv[6], &B) || N < 1 || B < 0) BAD_ARGS();
+  size_t n = (size_t)N * (size_t)B;
+  if (!get_buf(env, argv[3], napi_int8_array, n, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, n, 0, &fp) ||
+      !get_buf(env, argv[5], napi_uint16_array, n, 0, &e) || !get_buf(env, argv[7], napi_uint8_array, n, 0, &value) ||
+      !get_buf(env, argv[8], napi_uint16_array, n, 1, &q1) || !get_buf(env, argv[9], napi_uint16_array, n, 1, &r1) ||
+      !get_buf(env, argv[10], napi_uint8_array, n, 1, &q2)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_decrypt_peritem_batch(g_engine, N, q, p, f, fp, e, B, value, q1, r1, q2));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
 /* verifyKeysBatch(N, q, p, f:Int8Array, g:Int8Array, fq:Uint16Array, fp:Uint8Array, h:Uint16Array, B,
  *                 quotFq, remFq :Uint16Array, quotFp, remFp :Uint8Array, quotH, remH :Uint16Array, flags:Uint8Array[B]) */
 static napi_value VerifyKeysBatch(napi_env env, napi_callback_info info) {
@@ -638,6 +672,35 @@ static napi_value DecryptBatchDev(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* encryptPeritemBatchDev(N, q, h:handle[B*N u16], r:handle[B*N u8], m:handle[B*N u8], B, e:handle[B*N u16], quotE:handle|null) */
+static napi_value EncryptPeritemBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(8)
+  int32_t N, q, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(2, 2 * n, 0, h) DEV(3, n, 0, r) DEV(4, n, 0, m) DEV(6, 2 * n, 0, e) DEV(7, 2 * n, 1, quot)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_encrypt_peritem_batch_dev(g_engine, N, q, h->p, r->p, m->p, B, e->p, quot ? quot->p : NULL));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* decryptPeritemBatchDev(N, q, p, f:handle[B*N i8], fp:handle[B*N u8], e:handle[B*N u16], B, value:handle[B*N u8],
+ *                        quot1:handle|null, rem1:handle|null, quot2:handle|null) */
+static napi_value DecryptPeritemBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(11)
+  int32_t N, q, p, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[6], &B) ||
+      N < 1 || B < 0) BAD_ARGS();
+  const size_t n = (size_t)N * (size_t)B;
+  DEV(3, n, 0, f) DEV(4, n, 0, fp) DEV(5, 2 * n, 0, e) DEV(7, n, 0, value) DEV(8, 2 * n, 1, q1) DEV(9, 2 * n, 1, r1) DEV(10, n, 1, q2)
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_decrypt_peritem_batch_dev(g_engine, N, q, p, f->p, fp->p, e->p, B, value->p, q1 ? q1->p : NULL,
+                                                 r1 ? r1->p : NULL, q2 ? q2->p : NULL));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
 /* packBatchDev(maxVal, dataLen, data:handle, B, out:handle[B*outputSize*32 bytes], bytes:boolean)   bytes: data holds uint8 values */
 static napi_value PackBatchDev(napi_env env, napi_callback_info info) {
   ARGS(6)
@@ -957,6 +1020,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     {"addBatch", NULL, AddBatch, NULL, NULL, NULL, napi_default, NULL},
     {"encryptBatch", NULL, EncryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatch", NULL, DecryptBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"encryptPeritemBatch", NULL, EncryptPeritemBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"decryptPeritemBatch", NULL, DecryptPeritemBatch, NULL, NULL, NULL, napi_default, NULL},
     {"verifyKeysBatch", NULL, VerifyKeysBatch, NULL, NULL, NULL, napi_default, NULL},
     {"checkEncryptBatch", NULL, CheckEncryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"checkDecryptBatch", NULL, CheckDecryptBatch, NULL, NULL, NULL, napi_default, NULL},
@@ -979,6 +1044,8 @@ static napi_value Init(napi_env env, napi_value exports) {
     {"sampleTernaryDev", NULL, SampleTernaryDev, NULL, NULL, NULL, napi_default, NULL},
     {"encryptBatchDev", NULL, EncryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatchDev", NULL, DecryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
+    {"encryptPeritemBatchDev", NULL, EncryptPeritemBatchDev, NULL, NULL, NULL, napi_default, NULL},
+    {"decryptPeritemBatchDev", NULL, DecryptPeritemBatchDev, NULL, NULL, NULL, napi_default, NULL},
     {"packBatchDev", NULL, PackBatchDev, NULL, NULL, NULL, napi_default, NULL},
     {"encryptBatchAsync", NULL, EncryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatchAsync", NULL, DecryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},

@@ -459,6 +459,36 @@ export default class NTRU {
     return { value, quotient1: q1, remainder1: r1, quotient2: q2 };
   }
 
+  // ---- one key pair per item (additive): row b of r, m / e goes with key b of `keys`, a generateKeysBatch result (its first B rows are
+  // used; an item flagged there throws the reference's 'Could not find invertible f').  Same results, row by row, as loadKeyFromBatch(keys, b)
+  // followed by encryptBatch / decryptBatch of that one row.
+  _perKeyRows(keys, B, names) {
+    const { N } = this;
+    if (!keys.flags || keys.flags.length < B) throw new TypeError('batch per key: keys hold fewer than B items');
+    for (let b = 0; b < B; b++) if (keys.flags[b]) throw new Error('Could not find invertible f');
+    return names.map(n => {
+      if (!keys[n] || keys[n].length < B * N) throw new TypeError(`batch per key: keys.${n} is missing or short`);
+      return keys[n].subarray(0, B * N);
+    });
+  }
+  encryptBatchPerKey(keys, r, m, B, wantWitness = true, out = {}) {
+    const { N, q } = this;
+    const [h] = this._perKeyRows(keys, B, ['h']);
+    const e = out.e || new Uint16Array(B * N), quot = wantWitness ? (out.quotientE || new Uint16Array(B * N)) : null;
+    engine().encryptPeritemBatch(N, q, h, r, m, B, e, quot);
+    return { e, quotientE: quot };
+  }
+  decryptBatchPerKey(keys, e, B, wantWitness = true, out = {}) {
+    const { N, p, q } = this;
+    const [f, fp] = this._perKeyRows(keys, B, ['f', 'fp']);
+    const value = out.value || new Uint8Array(B * N);
+    const q1 = wantWitness ? (out.quotient1 || new Uint16Array(B * N)) : null;
+    const r1 = wantWitness ? (out.remainder1 || new Uint16Array(B * N)) : null;
+    const q2 = wantWitness ? (out.quotient2 || new Uint8Array(B * N)) : null;
+    engine().decryptPeritemBatch(N, q, p, f, fp, e, B, value, q1, r1, q2);
+    return { value, quotient1: q1, remainder1: r1, quotient2: q2 };
+  }
+
   // Device-resident pipeline for a batch of plaintexts (additive): the stages of the reference's encrypt / decrypt flow that the
   // caller names run back to back on the GPU, chunk by chunk, and only what is asked for crosses PCIe:
   //   sampleR: { key: Uint32Array[8], firstItem }   r = generateCustomArray(N, dr, dr) with -1 -> p-1 (index.js:89, :461-488) drawn on the
@@ -509,6 +539,13 @@ export default class NTRU {
   encryptBatchDev(hDev, rDev, mDev, B, eDev, quotDev = null) { engine().encryptBatchDev(this.N, this.q, hDev, rDev, mDev, B, eDev, quotDev); }
   decryptBatchDev(fDev, fpDev, eDev, B, valueDev, q1Dev = null, r1Dev = null, q2Dev = null) {
     engine().decryptBatchDev(this.N, this.q, this.p, fDev, fpDev, eDev, B, valueDev, q1Dev, r1Dev, q2Dev);
+  }
+  // one key pair per item on device buffers: hDev [B*N] u16 / fDev [B*N] i8, fpDev [B*N] u8 (e.g. generateKeysBatchDev's outputs)
+  encryptBatchPerKeyDev(hDev, rDev, mDev, B, eDev, quotDev = null) {
+    engine().encryptPeritemBatchDev(this.N, this.q, hDev, rDev, mDev, B, eDev, quotDev);
+  }
+  decryptBatchPerKeyDev(fDev, fpDev, eDev, B, valueDev, q1Dev = null, r1Dev = null, q2Dev = null) {
+    engine().decryptPeritemBatchDev(this.N, this.q, this.p, fDev, fpDev, eDev, B, valueDev, q1Dev, r1Dev, q2Dev);
   }
   static packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes = false) { engine().packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes); }
   // per-item key products on device buffers (f, g: Int8 rows; fq, h and every quotient / remainder of fq and h: Uint16 rows; fp and its

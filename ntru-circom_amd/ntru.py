@@ -388,6 +388,35 @@ class NTRU:
         self.h = trimPolynomial([int(x) for x in keys["h"][i]])
         return self
 
+    # -- one key pair per item: row b goes with item b of a generateKeysBatch result ------------------------------------------------
+    def _per_key_rows(self, keys, B, names):
+        flags = np.asarray(keys["flags"])
+        if flags.shape[0] < B:
+            raise ValueError("batch per key: keys hold fewer than B items")
+        if np.any(flags[:B]):
+            raise ValueError("Could not find invertible f")
+        return [np.asarray(keys[n])[:B] for n in names]
+
+    def encryptBatchPerKey(self, keys, r, m):
+        """encryptBits for B items, item b under key b of `keys` (generateKeysBatch; its first B items are used).  r: [B][N] signed
+        ternary or already mapped to {0, 1, p-1} (index.js:89); m: [B][N] bytes (index.js:91 adds them mod q).  Returns
+        {"e", "quotientE"} as [B][N] uint16 arrays: row b equals remainderE / quotientE of loadKeyFromBatch(keys, b).encryptBits."""
+        N, q, p = self.N, self.q, self.p
+        r = np.asarray(r).reshape(-1, N)
+        r = np.where(r == -1, p - 1, r).astype(np.uint8)
+        (h,) = self._per_key_rows(keys, r.shape[0], ["h"])
+        e, quot = self.engine.encrypt_peritem_batch(N, q, h, r, m)
+        return {"e": e, "quotientE": quot}
+
+    def decryptBatchPerKey(self, keys, e):
+        """decryptBits for B ciphertexts, item b under key b of `keys`.  Returns {"value", "quotient1", "remainder1", "quotient2"} as
+        [B][N] arrays: row b equals the witness arrays of loadKeyFromBatch(keys, b).decryptBits(e[b])."""
+        N, q, p = self.N, self.q, self.p
+        e = np.asarray(e).reshape(-1, N)
+        f, fp = self._per_key_rows(keys, e.shape[0], ["f", "fp"])
+        value, q1, r1, q2 = self.engine.decrypt_peritem_batch(N, q, p, f, fp, e)
+        return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
         """h = trim((p*fq mod q) * g mod (x^N - 1, q)) on the device."""
