@@ -144,6 +144,39 @@ int ntru_add_batch(ntru_engine_t *eng, int N, int mod, const uint16_t *a, const 
 int ntru_add_batch_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_a, const uint16_t *d_b, int64_t B,
                        uint16_t *d_out);
 
+/* ---- sums of ciphertexts in groups, with weights: the additive homomorphism folded over a whole tally -- addPolynomials
+ *      (index.js:235-244) over every row of a group, each row first scaled as multiplyPolynomialsByScalar does -- in one pass over
+ *      the rows.  rows: the dense [B][N] ciphertext array, entries below mod; weights: [B], one uint16_t < mod per row, or NULL for
+ *      all ones (that path does not multiply); out: [G][N],
+ *        out[g][k] = (sum over the rows of group g of weights[row] * rows[row][k]) % mod.
+ *      offsets == NULL: uniform groups, group g is rows [g K, (g + 1) K), K >= 1, B = G K.  offsets != NULL: [G + 1] row indices,
+ *      non-decreasing, offsets[0] >= 0; group g is rows [offsets[g], offsets[g + 1]) and K is ignored.  An empty group gives a zero row.
+ *      Domain: 2 <= N <= NTRU_MAX_N, 2 <= mod <= 65536, a power of two or not; exact for groups of up to 2^31 rows (a power-of-two
+ *      modulus accumulates in wrapping 32-bit words, any other in 64-bit words).  G == 0 launches nothing.
+ *      Integer sums do not depend on the order of the summands: the result is the same bytes whatever the decomposition into
+ *      workgroups, the grid, the chunking of the host form or the kernel path.
+ *   _dev: d_offsets is a DEVICE array that the call neither reads on the host nor waits for: it does not synchronise, and the kernels
+ *      (k_sum_groups, k_sum_groups_finish) cope with any distribution of group sizes.  Malformed device offsets are the caller's error
+ *      (unspecified rows are read).  Groups that are split over wavefronts leave partial rows in the engine-owned scratch buffer, whose
+ *      size depends on N and the grid only; nothing is allocated per call.
+ *   host form: validates the offsets and weights (NTRU_ERR_ARG before any launch); the rows run through the chunked pipeline, a group
+ *      larger than a chunk is accumulated across chunks on the device. */
+int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_t *rows, const uint16_t *weights, const int64_t *offsets,
+                    int64_t K, int64_t G, uint16_t *out);
+int ntru_sum_groups_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_rows, const uint16_t *d_weights,
+                        const int64_t *d_offsets, int64_t K, int64_t G, uint16_t *d_out);
+/* The tally: sum = ntru_sum_groups(rows) modulo q, then decryptBits (index.js:111-140) of every sum under one private key with the
+ * kernels ntru_decrypt_batch_dev picks.  sum [G][N] is needed as the intermediate (NULL is NTRU_ERR_ARG) and may be read afterwards;
+ * quot1 / rem1 / quot2 may be NULL.  Row g of value, quot1, rem1, quot2 is bit-identical to ntru_decrypt_batch on sum[g]; with f, fp
+ * and sum[g] it is a VerifyDecrypt witness for the tally.  Domain: that of ntru_decrypt_batch (q a power of two).  Whether value equals
+ * the sum of the plaintexts modulo p depends on the noise of the summed ciphertext, as in the reference ("Tallies"). */
+int ntru_tally_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *rows,
+                             const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G, uint16_t *sum, uint8_t *value,
+                             uint16_t *quot1, uint16_t *rem1, uint8_t *quot2);
+int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
+                                 const uint16_t *d_rows, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K, int64_t G,
+                                 uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2);
+
 /* ---- on-device ternary sampler: generateCustomArray(N, n1, n2) (index.js:461-488) for B items, so that encryptBits'
  *      randomness r never crosses PCIe.  Row b (item index first_item + b) gets n1 ones, n2 entries equal to `other`
  *      (2 = p-1 for r after the index.js:89 map) and zeros, shuffled exactly like the reference: for i = N-1 .. 1:

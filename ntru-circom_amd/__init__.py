@@ -19,4 +19,4 @@ from . import sharding  # noqa: F401
 from .ntru import (NTRU, addCiphertexts, addPolynomials, bigintToBits, bitsToBigInt, bitsToString, degree,  # noqa: F401
                    dividePolynomials, expandArray, extendedEuclideanAlgorithm, generateCustomArray, modInverse,
                    multiplyPolynomials, multiplyPolynomialsByScalar, packOutput, polyInv, stringToBits, checkWitnesses,
-                   subtractPolynomials, trimPolynomial, unpackInput)
+                   subtractPolynomials, sumCiphertexts, trimPolynomial, unpackInput)

@@ -89,6 +89,9 @@ for _sfx in ("", "_dev"):
     _SIGS["ntru_check_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _vp])
     _SIGS["ntru_check_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i64, _vp])
     _SIGS["ntru_check_inverse_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 4 + [_i64, _vp])
+for _sfx in ("", "_dev"):
+    _SIGS["ntru_sum_groups" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp])
+    _SIGS["ntru_tally_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _i64] + [_vp] * 5)
 _SIGS["ntru_keygen_workspace_bytes"] = (C.c_int, [_i, _i64, C.POINTER(C.c_size_t)])
 _SIGS["ntru_keygen_batch_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
 _SIGS["ntru_keygen_batch"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
@@ -215,6 +218,49 @@ class Engine:
         out = np.empty((B, N), np.uint16)
         self._chk(self._lib.ntru_add_batch(self._h, N, mod, _ptr(a), _ptr(b), B, _ptr(out)))
         return out
+
+    @staticmethod
+    def _groups(rows, offsets, K, weights):
+        """(offsets as int64 or None, K, G, weights as uint16 or None) of a sum over the rows [B][N]."""
+        B = rows.shape[0]
+        if offsets is not None:
+            offsets = _np(offsets, np.int64).reshape(-1)
+            if offsets.size < 1 or (offsets.size > 1 and int(offsets[-1]) > B) or (offsets.size == 1 and int(offsets[0]) > B):
+                raise ValueError("sum_groups: offsets must hold G + 1 row indices within the %d rows" % B)
+            K, G = 0, offsets.size - 1
+        else:
+            K = B if K is None else int(K)
+            if K < 1 or B % K:
+                raise ValueError("sum_groups: %d rows are not whole groups of K = %s" % (B, K))
+            G = B // K
+        if weights is not None:
+            weights = _np(weights, np.uint16).reshape(-1)
+            if weights.size != B:
+                raise ValueError("sum_groups: need one weight per row")
+        return offsets, K, G, weights
+
+    def sum_groups(self, N, mod, rows, offsets=None, K=None, weights=None):
+        """out[g] = (sum of weights[row] * rows[row] over group g) % mod.  offsets: [G + 1] row indices (CSR), else uniform groups of K
+        rows (K=None: one group of every row).  Returns [G][N] uint16."""
+        rows = _np(rows, np.uint16).reshape(-1, N)
+        offsets, K, G, weights = self._groups(rows, offsets, K, weights)
+        out = np.empty((G, N), np.uint16)
+        self._chk(self._lib.ntru_sum_groups(self._h, N, mod, _ptr(rows), _ptr(weights), _ptr(offsets), K, G, _ptr(out)))
+        return out
+
+    def tally_decrypt_batch(self, N, q, p, f, fp, rows, offsets=None, K=None, weights=None, want_witness=True):
+        """sum_groups modulo q, then decrypt_batch of the sums.  Returns (sum, value, quot1, rem1, quot2)."""
+        f, fp = _np(f, np.int8, (N,)), _np(fp, np.uint8, (N,))
+        rows = _np(rows, np.uint16).reshape(-1, N)
+        offsets, K, G, weights = self._groups(rows, offsets, K, weights)
+        total = np.empty((G, N), np.uint16)
+        value = np.empty((G, N), np.uint8)
+        q1 = np.empty((G, N), np.uint16) if want_witness else None
+        r1 = np.empty((G, N), np.uint16) if want_witness else None
+        q2 = np.empty((G, N), np.uint8) if want_witness else None
+        self._chk(self._lib.ntru_tally_decrypt_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(rows), _ptr(weights), _ptr(offsets), K, G,
+                                                     _ptr(total), _ptr(value), _ptr(q1), _ptr(r1), _ptr(q2)))
+        return total, value, q1, r1, q2
 
     def pack_params(self, max_val, data_len):
         v = [C.c_int(0) for _ in range(4)]
@@ -568,6 +614,18 @@ class Engine:
     def add_batch_dev(self, N, mod, d_a, d_b, B, d_out):
         dp = self._dp
         self._chk(self._lib.ntru_add_batch_dev(self._h, N, mod, dp(d_a), dp(d_b), B, dp(d_out)))
+
+    def sum_groups_dev(self, N, mod, d_rows, d_out, G, d_offsets=None, K=None, d_weights=None):
+        """d_offsets: DEVICE int64 [G + 1], or None for uniform groups of K rows."""
+        dp = self._dp
+        self._chk(self._lib.ntru_sum_groups_dev(self._h, N, mod, dp(d_rows), dp(d_weights), dp(d_offsets), int(K or 0), int(G), dp(d_out)))
+
+    def tally_decrypt_batch_dev(self, N, q, p, d_f, d_fp, d_rows, d_sum, d_value, G, d_offsets=None, K=None, d_weights=None,
+                                d_quot1=None, d_rem1=None, d_quot2=None):
+        dp = self._dp
+        self._chk(self._lib.ntru_tally_decrypt_batch_dev(self._h, N, q, p, dp(d_f), dp(d_fp), dp(d_rows), dp(d_weights), dp(d_offsets),
+                                                         int(K or 0), int(G), dp(d_sum), dp(d_value), dp(d_quot1), dp(d_rem1),
+                                                         dp(d_quot2)))
 
     def encrypt_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_quotE=None, ld=None):
         """ld: row pitch of r, m, e, quotE in elements (None = dense rows of N; see ntru_encrypt_batch_pitched_dev)."""

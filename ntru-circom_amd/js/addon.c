@@ -510,6 +510,52 @@ static napi_value PipelineBatch(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* The groups of a sum over B rows: offsets (BigInt64Array[G + 1], non-decreasing, 0 <= offsets[0], offsets[G] <= B) or uniform K with
+ * G * K == B.  Only what keeps the engine inside the arrays is checked here; the engine reports the rest. */
+static int groups_fit(const int64_t *off, int64_t K, int64_t G, int64_t B) {
+  if (G < 0 || B < 0) return 0;
+  if (!off) return K >= 1 && G <= B / K + 1 && G * K == B;
+  if (off[0] < 0) return 0;
+  for (int64_t g = 0; g < G; g++) if (off[g + 1] < off[g]) return 0;
+  return off[G] <= B;
+}
+
+/* sumGroups(N, mod, rows:Uint16Array[B*N], weights:Uint16Array[B]|null, offsets:BigInt64Array[G+1]|null, K, G, B, out:Uint16Array[G*N]) */
+static napi_value SumGroups(napi_env env, napi_callback_info info) {
+  ARGS(9)
+  int32_t N, mod, K, G, B; void *rows, *w, *off, *out;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[5], &K) || !get_i32(env, argv[6], &G) ||
+      !get_i32(env, argv[7], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
+  if (!get_buf(env, argv[2], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[3], napi_uint16_array, (size_t)B, 1, &w) ||
+      !get_buf(env, argv[4], napi_bigint64_array, (size_t)G + 1, 1, &off) ||
+      !get_buf(env, argv[8], napi_uint16_array, (size_t)N * (size_t)G, 0, &out)) BAD_ARGS();
+  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_sum_groups(g_engine, N, mod, rows, w, off, K, G, out));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* tallyDecryptBatch(N, q, p, f:Int8Array[N], fp:Uint8Array[N], rows:Uint16Array[B*N], weights|null, offsets|null, K, G, B,
+ *                   sum:Uint16Array[G*N], value:Uint8Array[G*N], quot1|null, rem1|null, quot2|null) */
+static napi_value TallyDecryptBatch(napi_env env, napi_callback_info info) {
+  ARGS(16)
+  int32_t N, q, p, K, G, B; void *f, *fp, *rows, *w, *off, *sum, *value, *q1, *r1, *q2;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
+      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
+  const size_t gn = (size_t)N * (size_t)G;
+  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
+      !get_buf(env, argv[5], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[6], napi_uint16_array, (size_t)B, 1, &w) ||
+      !get_buf(env, argv[7], napi_bigint64_array, (size_t)G + 1, 1, &off) || !get_buf(env, argv[11], napi_uint16_array, gn, 0, &sum) ||
+      !get_buf(env, argv[12], napi_uint8_array, gn, 0, &value) || !get_buf(env, argv[13], napi_uint16_array, gn, 1, &q1) ||
+      !get_buf(env, argv[14], napi_uint16_array, gn, 1, &r1) || !get_buf(env, argv[15], napi_uint8_array, gn, 1, &q2)) BAD_ARGS();
+  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_tally_decrypt_batch(g_engine, N, q, p, f, fp, rows, w, off, K, G, sum, value, q1, r1, q2));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
 typedef struct DevBuf { void *p; size_t bytes; struct DevBuf *next; } DevBuf;
 /* Every live handle of THIS addon.  An external value made by anybody else (another addon, a foreign napi_external) carries a data
  * pointer that is not in this list and is refused by get_dev without ever being dereferenced. */
@@ -669,6 +715,40 @@ static napi_value DecryptBatchDev(napi_env env, napi_callback_info info) {
   int rc;
   ENGINE_CALL(rc, ntru_decrypt_batch_dev(g_engine, N, q, p, f->p, fp->p, e->p, B, value->p, q1 ? q1->p : NULL, r1 ? r1->p : NULL,
                                          q2 ? q2->p : NULL));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* sumGroupsDev(N, mod, rows:handle[B*N u16], weights:handle[B u16]|null, offsets:handle[(G+1) i64]|null, K, G, B, out:handle[G*N u16]).
+ * The offsets live on the device, so the handle sizes are checked against the B the caller states: offsets[G] <= B is the caller's
+ * promise. */
+static napi_value SumGroupsDev(napi_env env, napi_callback_info info) {
+  ARGS(9)
+  int32_t N, mod, K, G, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[5], &K) || !get_i32(env, argv[6], &G) ||
+      !get_i32(env, argv[7], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
+  DEV(2, 2 * (size_t)N * (size_t)B, 0, rows) DEV(3, 2 * (size_t)B, 1, w) DEV(4, 8 * ((size_t)G + 1), 1, off) DEV(8, 2 * (size_t)N * (size_t)G, 0, out)
+  if (!off && !groups_fit(NULL, K, G, B)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_sum_groups_dev(g_engine, N, mod, rows->p, w ? w->p : NULL, off ? off->p : NULL, K, G, out->p));
+  return rc ? throw_engine(env, rc) : undefined(env);
+}
+
+/* tallyDecryptBatchDev(N, q, p, f:handle[N i8], fp:handle[N u8], rows:handle, weights:handle|null, offsets:handle|null, K, G, B,
+ *                      sum:handle[G*N u16], value:handle[G*N u8], quot1:handle|null, rem1:handle|null, quot2:handle|null) */
+static napi_value TallyDecryptBatchDev(napi_env env, napi_callback_info info) {
+  ARGS(16)
+  int32_t N, q, p, K, G, B; int ok;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
+      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
+  const size_t gn = (size_t)N * (size_t)G;
+  DEV(3, (size_t)N, 0, f) DEV(4, (size_t)N, 0, fp) DEV(5, 2 * (size_t)N * (size_t)B, 0, rows) DEV(6, 2 * (size_t)B, 1, w)
+  DEV(7, 8 * ((size_t)G + 1), 1, off) DEV(11, 2 * gn, 0, sum) DEV(12, gn, 0, value) DEV(13, 2 * gn, 1, q1) DEV(14, 2 * gn, 1, r1) DEV(15, gn, 1, q2)
+  if (!off && !groups_fit(NULL, K, G, B)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  int rc;
+  ENGINE_CALL(rc, ntru_tally_decrypt_batch_dev(g_engine, N, q, p, f->p, fp->p, rows->p, w ? w->p : NULL, off ? off->p : NULL, K, G, sum->p,
+                                               value->p, q1 ? q1->p : NULL, r1 ? r1->p : NULL, q2 ? q2->p : NULL));
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
@@ -858,8 +938,9 @@ typedef struct {
   napi_deferred deferred;
   napi_ref keep[12];
   int n_keep;
-  int kind;                       /* 0 encrypt, 1 decrypt, 2 pipeline, 3 keygen */
+  int kind;                       /* 0 encrypt, 1 decrypt, 2 pipeline, 3 keygen, 4 tally */
   int N, q, p, B, n1, n2;
+  int64_t K, G;                   /* tally */
   uint64_t first;
   void *ptr[12];
   KeygenArgs keygen;
@@ -878,6 +959,9 @@ static void async_execute(napi_env env, void *data) {
                       : ntru_encrypt_batch(g_engine, j->N, j->q, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4]);
     else if (j->kind == 3)
       j->rc = keygen_run(&j->keygen);
+    else if (j->kind == 4)
+      j->rc = ntru_tally_decrypt_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->ptr[3], j->ptr[4], j->K, j->G, j->ptr[5],
+                                       j->ptr[6], j->ptr[7], j->ptr[8], j->ptr[9]);
     else if (j->kind == 2)
       j->rc = ntru_pipeline_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->ptr[3], j->first, j->n1, j->n2, j->ptr[4],
                                   j->ptr[5], j->B, j->ptr[6], j->ptr[7], j->ptr[8], j->ptr[9]);
@@ -965,6 +1049,29 @@ static napi_value DecryptBatchAsync(napi_env env, napi_callback_info info) {
   return async_start(env, j, hold, 7, "ntru.decryptBatchAsync");
 }
 
+/* tallyDecryptBatchAsync(...the arguments of tallyDecryptBatch...) -> Promise<undefined> */
+static napi_value TallyDecryptBatchAsync(napi_env env, napi_callback_info info) {
+  ARGS(16)
+  int32_t N, q, p, K, G, B; void *f, *fp, *rows, *w, *off, *sum, *value, *q1, *r1, *q2;
+  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
+      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
+  const size_t gn = (size_t)N * (size_t)G;
+  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
+      !get_buf(env, argv[5], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[6], napi_uint16_array, (size_t)B, 1, &w) ||
+      !get_buf(env, argv[7], napi_bigint64_array, (size_t)G + 1, 1, &off) || !get_buf(env, argv[11], napi_uint16_array, gn, 0, &sum) ||
+      !get_buf(env, argv[12], napi_uint8_array, gn, 0, &value) || !get_buf(env, argv[13], napi_uint16_array, gn, 1, &q1) ||
+      !get_buf(env, argv[14], napi_uint16_array, gn, 1, &r1) || !get_buf(env, argv[15], napi_uint8_array, gn, 1, &q2)) BAD_ARGS();
+  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
+  if (!ensure_engine(env)) return NULL;
+  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
+  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  j->kind = 4; j->N = N; j->q = q; j->p = p; j->B = B; j->K = K; j->G = G;
+  j->ptr[0] = f; j->ptr[1] = fp; j->ptr[2] = rows; j->ptr[3] = w; j->ptr[4] = off; j->ptr[5] = sum; j->ptr[6] = value; j->ptr[7] = q1;
+  j->ptr[8] = r1; j->ptr[9] = q2;
+  napi_value hold[10] = {argv[3], argv[4], argv[5], argv[6], argv[7], argv[11], argv[12], argv[13], argv[14], argv[15]};
+  return async_start(env, j, hold, 10, "ntru.tallyBatchAsync");
+}
+
 /* pipelineBatchAsync(...the arguments of pipelineBatch...) -> Promise<undefined> */
 static napi_value PipelineBatchAsync(napi_env env, napi_callback_info info) {
   ARGS(17)
@@ -1018,6 +1125,11 @@ static napi_value Init(napi_env env, napi_value exports) {
     {"polymulSplit", NULL, PolymulSplit, NULL, NULL, NULL, napi_default, NULL},
     {"splitByI", NULL, SplitByI, NULL, NULL, NULL, napi_default, NULL},
     {"addBatch", NULL, AddBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"sumGroups", NULL, SumGroups, NULL, NULL, NULL, napi_default, NULL},
+    {"tallyDecryptBatch", NULL, TallyDecryptBatch, NULL, NULL, NULL, napi_default, NULL},
+    {"tallyDecryptBatchAsync", NULL, TallyDecryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
+    {"sumGroupsDev", NULL, SumGroupsDev, NULL, NULL, NULL, napi_default, NULL},
+    {"tallyDecryptBatchDev", NULL, TallyDecryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
     {"encryptBatch", NULL, EncryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"decryptBatch", NULL, DecryptBatch, NULL, NULL, NULL, napi_default, NULL},
     {"encryptPeritemBatch", NULL, EncryptPeritemBatch, NULL, NULL, NULL, napi_default, NULL},

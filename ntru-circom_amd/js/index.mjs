@@ -238,6 +238,30 @@ export function addCiphertexts(e1, e2, q) {
   return trimPolynomial(Array.from(out));
 }
 
+// The groups of a sum over B rows: offsets (Array or BigInt64Array of G + 1 row indices) or null for ONE group of every row.
+function tallyGroups(offsets, B) {
+  if (offsets == null) return { off: null, K: Math.max(B, 1), G: B > 0 ? 1 : 0 };
+  const off = offsets instanceof BigInt64Array ? offsets : BigInt64Array.from(Array.from(offsets), x => BigInt(x));
+  if (off.length < 1) throw new TypeError('offsets must hold G + 1 row indices');
+  return { off, K: 0, G: off.length - 1 };
+}
+
+// The homomorphic sum of many ciphertexts in one device pass: addPolynomials folded over every group of `rows` (arrays of coefficients in
+// [0, q)), each row first scaled by its weight as multiplyPolynomialsByScalar does.  offsets null: one group, returns the trimmed sum;
+// else an Array of them, group g = rows[offsets[g] .. offsets[g + 1]).
+export function sumCiphertexts(rows, q, offsets = null, weights = null) {
+  const B = rows.length;
+  const N = Math.max(2, ...rows.map(r => r.length));
+  const flat = new Uint16Array(B * N);
+  rows.forEach((r, b) => flat.set(r, b * N));
+  const w = weights ? Uint16Array.from(weights, x => ((x % q) + q) % q) : null;
+  const { off, K, G } = tallyGroups(offsets, B);
+  const out = new Uint16Array(G * N);
+  engine().sumGroups(N, q, flat, w, off, K, G, B, out);
+  const sums = Array.from({ length: G }, (_, g) => trimPolynomial(Array.from(out.subarray(g * N, (g + 1) * N))));
+  return offsets == null ? sums[0] : sums;
+}
+
 const limbsToBigInt = (l, at) => l[at] | (l[at + 1] << 64n) | (l[at + 2] << 128n) | (l[at + 3] << 192n);
 
 // index.js:572-596 on the GPU: same object as the reference (`expected` is an Array of BigInt).
@@ -457,6 +481,36 @@ export default class NTRU {
     engine().decryptBatch(N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(expandArray(this.fp, N, 0)),
       e, B, value, q1, r1, q2);
     return { value, quotient1: q1, remainder1: r1, quotient2: q2 };
+  }
+
+  // ---- tallies (additive): sums the ciphertexts rows: Uint16Array[B*N] in groups (offsets: G + 1 row indices, BigInt64Array or Array;
+  // null: one group of every row), each row scaled by its weight (Uint16Array[B] below q, or null), and decrypts every sum.
+  // -> { sum, value, quotient1, remainder1, quotient2 }, [G*N] each: row g is what decryptBatch returns for sum row g.
+  tallyBatch(rows, B, offsets = null, weights = null, wantWitness = true) { return this._tally(rows, B, offsets, weights, wantWitness, false); }
+  // The same on a libuv worker thread: a Promise of the same object; the arrays must be left alone until it settles.
+  tallyBatchAsync(rows, B, offsets = null, weights = null, wantWitness = true) { return this._tally(rows, B, offsets, weights, wantWitness, true); }
+  _tally(rows, B, offsets, weights, wantWitness, asynchronous) {
+    const { N, p, q } = this;
+    const { off, K, G } = tallyGroups(offsets, B);
+    const sum = new Uint16Array(G * N), value = new Uint8Array(G * N);
+    const q1 = wantWitness ? new Uint16Array(G * N) : null, r1 = wantWitness ? new Uint16Array(G * N) : null;
+    const q2 = wantWitness ? new Uint8Array(G * N) : null;
+    const args = [N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(expandArray(this.fp, N, 0)), rows, weights, off, K, G, B,
+      sum, value, q1, r1, q2];
+    const res = { sum, value, quotient1: q1, remainder1: r1, quotient2: q2 };
+    if (asynchronous) return engine().tallyDecryptBatchAsync(...args).then(() => res);
+    engine().tallyDecryptBatch(...args);
+    return res;
+  }
+
+  // The same on device handles (devAlloc): offsetsDev holds G + 1 int64 row indices on the device (null: uniform groups of K rows); only
+  // enqueues.  sumGroupsDev is the sum alone for any modulus.
+  tallyBatchDev(fDev, fpDev, rowsDev, B, G, sumDev, valueDev, { offsetsDev = null, K = 0, weightsDev = null, q1Dev = null, r1Dev = null, q2Dev = null } = {}) {
+    engine().tallyDecryptBatchDev(this.N, this.q, this.p, fDev, fpDev, rowsDev, weightsDev, offsetsDev, K, G, B, sumDev, valueDev, q1Dev, r1Dev, q2Dev);
+  }
+
+  static sumGroupsDev(N, mod, rowsDev, B, G, outDev, { offsetsDev = null, K = 0, weightsDev = null } = {}) {
+    engine().sumGroupsDev(N, mod, rowsDev, weightsDev, offsetsDev, K, G, B, outDev);
   }
 
   // ---- one key pair per item (additive): row b of r, m / e goes with key b of `keys`, a generateKeysBatch result (its first B rows are

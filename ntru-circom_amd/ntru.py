@@ -227,6 +227,22 @@ def addCiphertexts(e1, e2, q, engine=None):
     return trimPolynomial(out[0].tolist())
 
 
+def sumCiphertexts(rows, q, offsets=None, weights=None, engine=None):
+    """The homomorphic sum of many ciphertexts in one device pass: addPolynomials (index.js:235-244) folded over every group of
+    `rows` (lists of coefficients in [0, q)), each row first scaled by its weight as multiplyPolynomialsByScalar does.  offsets:
+    [G + 1] row indices, group g is rows[offsets[g]:offsets[g + 1]]; None: one group of all rows.  Returns the trimmed sum (one
+    list), or a list of them when offsets is given."""
+    eng = engine or default_engine()
+    rows = [list(r) for r in rows]
+    N = max([len(r) for r in rows] + [2])
+    if weights is not None:
+        weights = [int(w) % q for w in weights]
+    out = eng.sum_groups(N, q, np.array([expandArray(r, N) for r in rows], dtype=np.uint16).reshape(-1, N), offsets=offsets,
+                         weights=weights)
+    sums = [trimPolynomial(row.tolist()) for row in out]
+    return sums if offsets is not None else sums[0]
+
+
 def packOutput(maxVal, dataLen, data, engine=None):
     """index.js:572-596: same dict as the reference; `expected` is a list of Python ints (the reference's BigInts)."""
     eng = engine or default_engine()
@@ -416,6 +432,21 @@ class NTRU:
         f, fp = self._per_key_rows(keys, e.shape[0], ["f", "fp"])
         value, q1, r1, q2 = self.engine.decrypt_peritem_batch(N, q, p, f, fp, e)
         return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    # -- tallies: decryptBits of sums of ciphertexts -----------------------------------------------------------------------------------
+    def tallyBatch(self, rows, offsets=None, weights=None, wantWitness=True):
+        """Sums the ciphertexts `rows` [B][N] in groups (offsets: [G + 1] row indices; None: one group of every row), each row scaled
+        by its weight (None: 1), and decrypts every sum.  Returns {"sum", "value", "quotient1", "remainder1", "quotient2"} as [G][N]
+        arrays (the witness arrays are None without wantWitness): row g equals the witness arrays of decryptBits(sum[g])."""
+        N, q, p = self.N, self.q, self.p
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")
+        rows = np.asarray(rows).reshape(-1, N)
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.int64) % q
+        total, value, q1, r1, q2 = self.engine.tally_decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), rows,
+                                                                   offsets=offsets, weights=weights, want_witness=wantWitness)
+        return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
