@@ -1,13 +1,16 @@
 /*
- * addon.c -- N-API binding of include/ntru_engine.h for Node.js (N-API v3+, works on Node 12).
+ * addon.c -- N-API binding of include/ntru_engine.h for Node.js (N-API version 6: BigInt64Array / BigUint64Array; Node 12.17+).
  *
  * Thin by design: every exported function unpacks TypedArray arguments into the plain pointers the C ABI takes
  * (napi_get_typedarray_info), calls the engine, and throws a JS Error carrying ntru_last_error() on failure.
  * All reference-shaped behaviour (padding, trimming, {value, inputs, params} objects) lives in index.mjs.
+ * The batch calls are rows of one table (ops[], below the few calls written by hand); engine and handle management, the pack calls
+ * (their sizes come from ntru_pack_params, whose refusal is an engine error before any buffer is looked at) and genericOp are by hand.
  */
 #define NAPI_VERSION 6
 #include <node_api.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -126,236 +129,14 @@ static napi_value SetSamplerRounds(napi_env env, napi_callback_info info) {
   int32_t rounds;
   if (!get_i32(env, argv[0], &rounds)) BAD_ARGS();
   if (!ensure_engine(env)) return NULL;
-  if (rounds != 0) {
-    int rc = ntru_engine_set_sampler_rounds(g_engine, rounds);
-    if (rc) return throw_engine(env, rc);
-  }
-  napi_value r; NAPI_OK(napi_create_int32(env, ntru_engine_get_sampler_rounds(g_engine), &r)); return r;
+  pthread_mutex_lock(&g_lock);                       /* an Async pipeline job on a worker thread reads the setting */
+  const int rc = rounds != 0 ? ntru_engine_set_sampler_rounds(g_engine, rounds) : 0;
+  const int now = ntru_engine_get_sampler_rounds(g_engine);
+  pthread_mutex_unlock(&g_lock);
+  if (rc) return throw_engine(env, rc);
+  napi_value r; NAPI_OK(napi_create_int32(env, now, &r)); return r;
 }
 
-/* polymulSplit(N, mod, a:Uint16Array, b:Uint16Array, B, quot:Uint16Array, rem:Uint16Array) */
-static napi_value PolymulSplit(napi_env env, napi_callback_info info) {
-  ARGS(7)
-  int32_t N, mod, B; void *a, *b, *quot, *rem;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[4], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, n, 0, &a) || !get_buf(env, argv[3], napi_uint16_array, n, 0, &b) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &quot) || !get_buf(env, argv[6], napi_uint16_array, n, 0, &rem)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_polymul_split(g_engine, N, mod, a, b, B, quot, rem));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* splitByI(N, mod, a:Uint16Array[B*2N], B, quot, rem) */
-static napi_value SplitByI(napi_env env, napi_callback_info info) {
-  ARGS(6)
-  int32_t N, mod, B; void *a, *quot, *rem;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[3], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, 2 * n, 0, &a) || !get_buf(env, argv[4], napi_uint16_array, n, 0, &quot) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &rem)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_split_by_I(g_engine, N, mod, a, B, quot, rem));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* addBatch(N, mod, a, b, B, out) */
-static napi_value AddBatch(napi_env env, napi_callback_info info) {
-  ARGS(6)
-  int32_t N, mod, B; void *a, *b, *out;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[4], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, n, 0, &a) || !get_buf(env, argv[3], napi_uint16_array, n, 0, &b) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &out)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_add_batch(g_engine, N, mod, a, b, B, out));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* invertKeyBatch(N, q, p, f:Int8Array[B*N], B, fq:Uint16Array[B*N]|null, fp:Uint8Array[B*N]|null, flags:Uint8Array[B]) */
-static napi_value InvertKeyBatch(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, p, B; void *f, *fq, *fp, *flags;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[4], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_int8_array, n, 0, &f) || !get_buf(env, argv[5], napi_uint16_array, n, 1, &fq) ||
-      !get_buf(env, argv[6], napi_uint8_array, n, 1, &fp) || !get_buf(env, argv[7], napi_uint8_array, (size_t)B, 0, &flags)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_invert_key_batch(g_engine, N, q, p, f, B, fq, fp, flags));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* publicKeyBatch(N, q, p, fq:Uint16Array[B*N], g:Int8Array[B*N], B, h:Uint16Array[B*N]) */
-static napi_value PublicKeyBatch(napi_env env, napi_callback_info info) {
-  ARGS(7)
-  int32_t N, q, p, B; void *fq, *g, *h;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[5], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_uint16_array, n, 0, &fq) || !get_buf(env, argv[4], napi_int8_array, n, 0, &g) ||
-      !get_buf(env, argv[6], napi_uint16_array, n, 0, &h)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_public_key_batch(g_engine, N, q, p, fq, g, B, h));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* encryptBatch(N, q, h:Uint16Array[N], r:Uint8Array[B*N], m:Uint8Array[B*N], B, e:Uint16Array, quotE:Uint16Array|null) */
-static napi_value EncryptBatch(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, B; void *h, *r, *m, *e, *quot;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, (size_t)N, 0, &h) || !get_buf(env, argv[3], napi_uint8_array, n, 0, &r) ||
-      !get_buf(env, argv[4], napi_uint8_array, n, 0, &m) || !get_buf(env, argv[6], napi_uint16_array, n, 0, &e) ||
-      !get_buf(env, argv[7], napi_uint16_array, n, 1, &quot)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, g_multi ? ntru_multi_encrypt_batch(g_multi, N, q, h, r, m, B, e, quot)
-                   : ntru_encrypt_batch(g_engine, N, q, h, r, m, B, e, quot));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* decryptBatch(N, q, p, f:Int8Array[N], fp:Uint8Array[N], e:Uint16Array[B*N], B, value:Uint8Array,
- *              quot1:Uint16Array|null, rem1:Uint16Array|null, quot2:Uint8Array|null) */
-static napi_value DecryptBatch(napi_env env, napi_callback_info info) {
-  ARGS(11)
-  int32_t N, q, p, B; void *f, *fp, *e, *value, *q1, *r1, *q2;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      !get_i32(env, argv[6], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &e) || !get_buf(env, argv[7], napi_uint8_array, n, 0, &value) ||
-      !get_buf(env, argv[8], napi_uint16_array, n, 1, &q1) || !get_buf(env, argv[9], napi_uint16_array, n, 1, &r1) ||
-      !get_buf(env, argv[10], napi_uint8_array, n, 1, &q2)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, g_multi ? ntru_multi_decrypt_batch(g_multi, N, q, p, f, fp, e, B, value, q1, r1, q2)
-                   : ntru_decrypt_batch(g_engine, N, q, p, f, fp, e, B, value, q1, r1, q2));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* encryptPeritemBatch(N, q, h:Uint16Array[B*N], r:Uint8Array[B*N], m:Uint8Array[B*N], B, e:Uint16Array, quotE:Uint16Array|null):
- * row b under key b (ntru_encrypt_peritem_batch) */
-static napi_value EncryptPeritemBatch(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, B; void *h, *r, *m, *e, *quot;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, n, 0, &h) || !get_buf(env, argv[3], napi_uint8_array, n, 0, &r) ||
-      !get_buf(env, argv[4], napi_uint8_array, n, 0, &m) || !get_buf(env, argv[6], napi_uint16_array, n, 0, &e) ||
-      !get_buf(env, argv[7], napi_uint16_array, n, 1, &quot)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_encrypt_peritem_batch(g_engine, N, q, h, r, m, B, e, quot));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* decryptPeritemBatch(N, q, p, f:Int8Array[B*N], fp:Uint8Array[B*N], e:Uint16Array[B*N], B, value:Uint8Array,
- *                     quot1:Uint16Array|null, rem1:Uint16Array|null, quot2:Uint8Array|null): row b under key b */
-static napi_value DecryptPeritemBatch(napi_env env, napi_callback_info info) {
-  ARGS(11)
-  int32_t N, q, p, B; void *f, *fp, *e, *value, *q1, *r1, *q2;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      !get_i32(env, argv[6], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_int8_array, n, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, n, 0, &fp) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &e) || !get_buf(env, argv[7], napi_uint8_array, n, 0, &value) ||
-      !get_buf(env, argv[8], napi_uint16_array, n, 1, &q1) || !get_buf(env, argv[9], napi_uint16_array, n, 1, &r1) ||
-      !get_buf(env, argv[10], napi_uint8_array, n, 1, &q2)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_decrypt_peritem_batch(g_engine, N, q, p, f, fp, e, B, value, q1, r1, q2));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* verifyKeysBatch(N, q, p, f:Int8Array, g:Int8Array, fq:Uint16Array, fp:Uint8Array, h:Uint16Array, B,
- *                 quotFq, remFq :Uint16Array, quotFp, remFp :Uint8Array, quotH, remH :Uint16Array, flags:Uint8Array[B]) */
-static napi_value VerifyKeysBatch(napi_env env, napi_callback_info info) {
-  ARGS(16)
-  int32_t N, q, p, B; void *f, *g, *fq, *fp, *h, *o1, *o2, *o3, *o4, *o5, *o6, *fl;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      !get_i32(env, argv[8], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_int8_array, n, 0, &f) || !get_buf(env, argv[4], napi_int8_array, n, 0, &g) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &fq) || !get_buf(env, argv[6], napi_uint8_array, n, 0, &fp) ||
-      !get_buf(env, argv[7], napi_uint16_array, n, 0, &h) || !get_buf(env, argv[9], napi_uint16_array, n, 0, &o1) ||
-      !get_buf(env, argv[10], napi_uint16_array, n, 0, &o2) || !get_buf(env, argv[11], napi_uint8_array, n, 0, &o3) ||
-      !get_buf(env, argv[12], napi_uint8_array, n, 0, &o4) || !get_buf(env, argv[13], napi_uint16_array, n, 0, &o5) ||
-      !get_buf(env, argv[14], napi_uint16_array, n, 0, &o6) || !get_buf(env, argv[15], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, g_multi ? ntru_multi_verify_keys_batch(g_multi, N, q, p, f, g, fq, fp, h, B, o1, o2, o3, o4, o5, o6, fl)
-                   : ntru_verify_keys_batch(g_engine, N, q, p, f, g, fq, fp, h, B, o1, o2, o3, o4, o5, o6, fl));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* Witness checks (ntru_check_*_batch): check<Kind>Batch(N, params..., signals as Uint16Array [B*N] / [B*(N+1)]..., B,
- * flags:Uint8Array[B]); the signals in the order of the template's inputs (circuits/ntru.circom). */
-static int get_rows(napi_env env, napi_value *argv, int first, int count, int n_long, size_t N, size_t B, void **out) {
-  for (int i = 0; i < count; i++)
-    if (!get_buf(env, argv[first + i], napi_uint16_array, (i < n_long ? N : N + 1) * B, 0, &out[i])) return 0;
-  return 1;
-}
-
-/* checkEncryptBatch(N, q, nq, r, m, h, quotientE, remainderE, B, flags) */
-static napi_value CheckEncryptBatch(napi_env env, napi_callback_info info) {
-  ARGS(10)
-  int32_t N, q, nq, B; void *a[5], *fl;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &nq) || !get_i32(env, argv[8], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  if (!get_rows(env, argv, 3, 5, 3, (size_t)N, (size_t)B, a) || !get_buf(env, argv[9], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_check_encrypt_batch(g_engine, N, q, nq, a[0], a[1], a[2], a[3], a[4], B, fl));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* checkDecryptBatch(N, q, nq, p, np, f, fp, e, quotient1, remainder1, quotient2, remainder2, B, flags) */
-static napi_value CheckDecryptBatch(napi_env env, napi_callback_info info) {
-  ARGS(14)
-  int32_t N, q, nq, p, np, B; void *a[7], *fl;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &nq) || !get_i32(env, argv[3], &p) ||
-      !get_i32(env, argv[4], &np) || !get_i32(env, argv[12], &B) || N < 1 || B < 0) BAD_ARGS();
-  if (!get_rows(env, argv, 5, 7, 3, (size_t)N, (size_t)B, a) || !get_buf(env, argv[13], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_check_decrypt_batch(g_engine, N, q, nq, p, np, a[0], a[1], a[2], a[3], a[4], a[5], a[6], B, fl));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* checkInverseBatch(N, M, n, f, fq, quotientI, remainderI, B, flags) */
-static napi_value CheckInverseBatch(napi_env env, napi_callback_info info) {
-  ARGS(9)
-  int32_t N, M, n, B; void *a[4], *fl;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &M) || !get_i32(env, argv[2], &n) || !get_i32(env, argv[7], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  if (!get_rows(env, argv, 3, 4, 2, (size_t)N, (size_t)B, a) || !get_buf(env, argv[8], napi_uint8_array, (size_t)B, 0, &fl)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_check_inverse_batch(g_engine, N, M, n, a[0], a[1], a[2], a[3], B, fl));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* sampleTernary(N, n1, n2, other, key:Uint32Array[8], firstItem:Number, B, out:Uint8Array[B*N]) */
-static napi_value SampleTernary(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, n1, n2, other, B; double first; void *key, *out;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &n1) || !get_i32(env, argv[2], &n2) ||
-      !get_i32(env, argv[3], &other) || napi_get_value_double(env, argv[5], &first) != napi_ok ||
-      !get_i32(env, argv[6], &B) || N < 1 || B < 0 || first < 0 || first > 9007199254740991.0) BAD_ARGS();
-  if (!get_buf(env, argv[4], napi_uint32_array, 8, 0, &key) ||
-      !get_buf(env, argv[7], napi_uint8_array, (size_t)N * (size_t)B, 0, &out)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_sample_ternary(g_engine, N, n1, n2, other, key, (uint64_t)first, B, out));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
 
 /* packParams(maxVal, dataLen) -> [bits, perOutput, arrLen, outputSize] */
 static napi_value PackParams(napi_env env, napi_callback_info info) {
@@ -478,84 +259,9 @@ static napi_value GenericOp(napi_env env, napi_callback_info info) {
   return arr;
 }
 
-/* ---- device-resident use (additive).  pipelineBatch chains sampler -> encryptBits -> decryptBits -> packOutput on the GPU for a batch
- *      of host plaintexts (ntru_pipeline_batch); devAlloc / devUpload / devDownload / devFree plus the *Dev calls expose the engine's
- *      *_dev entry points on opaque device-buffer handles, for callers that want to compose the stages themselves.  Every *Dev call
- *      checks the byte size of each handle against what the kernel will touch before anything is launched. */
-
-/* pipelineBatch(N, q, p, h:Uint16Array[N], f:Int8Array[N]|null, fp:Uint8Array[N]|null, key:Uint32Array[8]|null, firstItem, n1, n2,
- *               r:Uint8Array[B*N]|null, m:Uint8Array[B*N], B, rOut:Uint8Array|null, e:Uint16Array|null, value:Uint8Array|null,
- *               packed:BigUint64Array[B*outputSize*4]|null) */
-static napi_value PipelineBatch(napi_env env, napi_callback_info info) {
-  ARGS(17)
-  int32_t N, q, p, n1, n2, B; double first; void *h, *f, *fp, *key, *r, *m, *r_out, *e, *value, *packed;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      napi_get_value_double(env, argv[7], &first) != napi_ok || !get_i32(env, argv[8], &n1) || !get_i32(env, argv[9], &n2) ||
-      !get_i32(env, argv[12], &B) || N < 1 || B < 0 || first < 0 || first > 9007199254740991.0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_uint16_array, (size_t)N, 0, &h) || !get_buf(env, argv[4], napi_int8_array, (size_t)N, 1, &f) ||
-      !get_buf(env, argv[5], napi_uint8_array, (size_t)N, 1, &fp) || !get_buf(env, argv[6], napi_uint32_array, 8, 1, &key) ||
-      !get_buf(env, argv[10], napi_uint8_array, n, 1, &r) || !get_buf(env, argv[11], napi_uint8_array, n, 0, &m) ||
-      !get_buf(env, argv[13], napi_uint8_array, n, 1, &r_out) || !get_buf(env, argv[14], napi_uint16_array, n, 1, &e) ||
-      !get_buf(env, argv[15], napi_uint8_array, n, 1, &value)) BAD_ARGS();
-  size_t need_packed = 0;
-  {
-    int bits, per, al, os;
-    if (ntru_pack_params(f ? p - 1 : q - 1, N, &bits, &per, &al, &os) == 0) need_packed = (size_t)B * (size_t)os * 4;
-  }
-  if (!get_buf(env, argv[16], napi_biguint64_array, need_packed, 1, &packed)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_pipeline_batch(g_engine, N, q, p, h, f, fp, key, (uint64_t)first, n1, n2, r, m, B, r_out, e, value, packed));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* The groups of a sum over B rows: offsets (BigInt64Array[G + 1], non-decreasing, 0 <= offsets[0], offsets[G] <= B) or uniform K with
- * G * K == B.  Only what keeps the engine inside the arrays is checked here; the engine reports the rest. */
-static int groups_fit(const int64_t *off, int64_t K, int64_t G, int64_t B) {
-  if (G < 0 || B < 0) return 0;
-  if (!off) return K >= 1 && G <= B / K + 1 && G * K == B;
-  if (off[0] < 0) return 0;
-  for (int64_t g = 0; g < G; g++) if (off[g + 1] < off[g]) return 0;
-  return off[G] <= B;
-}
-
-/* sumGroups(N, mod, rows:Uint16Array[B*N], weights:Uint16Array[B]|null, offsets:BigInt64Array[G+1]|null, K, G, B, out:Uint16Array[G*N]) */
-static napi_value SumGroups(napi_env env, napi_callback_info info) {
-  ARGS(9)
-  int32_t N, mod, K, G, B; void *rows, *w, *off, *out;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[5], &K) || !get_i32(env, argv[6], &G) ||
-      !get_i32(env, argv[7], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
-  if (!get_buf(env, argv[2], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[3], napi_uint16_array, (size_t)B, 1, &w) ||
-      !get_buf(env, argv[4], napi_bigint64_array, (size_t)G + 1, 1, &off) ||
-      !get_buf(env, argv[8], napi_uint16_array, (size_t)N * (size_t)G, 0, &out)) BAD_ARGS();
-  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_sum_groups(g_engine, N, mod, rows, w, off, K, G, out));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* tallyDecryptBatch(N, q, p, f:Int8Array[N], fp:Uint8Array[N], rows:Uint16Array[B*N], weights|null, offsets|null, K, G, B,
- *                   sum:Uint16Array[G*N], value:Uint8Array[G*N], quot1|null, rem1|null, quot2|null) */
-static napi_value TallyDecryptBatch(napi_env env, napi_callback_info info) {
-  ARGS(16)
-  int32_t N, q, p, K, G, B; void *f, *fp, *rows, *w, *off, *sum, *value, *q1, *r1, *q2;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
-      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
-  const size_t gn = (size_t)N * (size_t)G;
-  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
-      !get_buf(env, argv[5], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[6], napi_uint16_array, (size_t)B, 1, &w) ||
-      !get_buf(env, argv[7], napi_bigint64_array, (size_t)G + 1, 1, &off) || !get_buf(env, argv[11], napi_uint16_array, gn, 0, &sum) ||
-      !get_buf(env, argv[12], napi_uint8_array, gn, 0, &value) || !get_buf(env, argv[13], napi_uint16_array, gn, 1, &q1) ||
-      !get_buf(env, argv[14], napi_uint16_array, gn, 1, &r1) || !get_buf(env, argv[15], napi_uint8_array, gn, 1, &q2)) BAD_ARGS();
-  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_tally_decrypt_batch(g_engine, N, q, p, f, fp, rows, w, off, K, G, sum, value, q1, r1, q2));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
+/* ---- device buffers (additive): devAlloc / devUpload / devDownload / devFree hand out opaque handles for the engine's *_dev entry
+ *      points, for callers that compose the stages themselves.  Every call on handles checks the byte size of each against what the
+ *      kernel will touch before anything is launched. */
 typedef struct DevBuf { void *p; size_t bytes; struct DevBuf *next; } DevBuf;
 /* Every live handle of THIS addon.  An external value made by anybody else (another addon, a foreign napi_external) carries a data
  * pointer that is not in this list and is refused by get_dev without ever being dereferenced. */
@@ -635,15 +341,17 @@ static napi_value DevFree(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
+/* Bytes per element, by napi_typedarray_type (int8 .. biguint64) */
+static const size_t elem_width[] = {1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8};
+
 /* The bytes of any TypedArray. */
 static int get_any(napi_env env, napi_value v, void **data, size_t *bytes) {
   bool is_ta = false;
   if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return 0;
   napi_typedarray_type t; size_t len;
   if (napi_get_typedarray_info(env, v, &t, &len, data, NULL, NULL) != napi_ok) return 0;
-  static const size_t w[] = {1, 1, 1, 2, 2, 4, 4, 4, 8, 8, 8};
-  if ((int)t < 0 || (size_t)t >= sizeof w / sizeof w[0]) return 0;
-  *bytes = len * w[t];
+  if ((int)t < 0 || (size_t)t >= sizeof elem_width / sizeof elem_width[0]) return 0;
+  *bytes = len * elem_width[t];
   return 1;
 }
 
@@ -673,123 +381,17 @@ static napi_value DevDownload(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
-#define DEV(i, need, opt, var) DevBuf *var = get_dev(env, argv[i], (need), (opt), &ok); if (!ok) BAD_ARGS();
-
-/* sampleTernaryDev(N, n1, n2, other, key:Uint32Array[8], firstItem, B, out:handle[B*N]) */
-static napi_value SampleTernaryDev(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, n1, n2, other, B; double first; void *key; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &n1) || !get_i32(env, argv[2], &n2) || !get_i32(env, argv[3], &other) ||
-      napi_get_value_double(env, argv[5], &first) != napi_ok || !get_i32(env, argv[6], &B) || N < 1 || B < 0 || first < 0 ||
-      first > 9007199254740991.0 || !get_buf(env, argv[4], napi_uint32_array, 8, 0, &key)) BAD_ARGS();
-  DEV(7, (size_t)N * (size_t)B, 0, out)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_sample_ternary_dev(g_engine, N, n1, n2, other, key, (uint64_t)first, B, out->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* encryptBatchDev(N, q, h:handle[N u16], r:handle[B*N u8], m:handle[B*N u8], B, e:handle[B*N u16], quotE:handle|null) */
-static napi_value EncryptBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(2, 2 * (size_t)N, 0, h) DEV(3, n, 0, r) DEV(4, n, 0, m) DEV(6, 2 * n, 0, e) DEV(7, 2 * n, 1, quot)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_encrypt_batch_dev(g_engine, N, q, h->p, r->p, m->p, B, e->p, quot ? quot->p : NULL));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* decryptBatchDev(N, q, p, f:handle[N i8], fp:handle[N u8], e:handle[B*N u16], B, value:handle[B*N u8],
- *                 quot1:handle|null, rem1:handle|null, quot2:handle|null) */
-static napi_value DecryptBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(11)
-  int32_t N, q, p, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[6], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(3, (size_t)N, 0, f) DEV(4, (size_t)N, 0, fp) DEV(5, 2 * n, 0, e) DEV(7, n, 0, value) DEV(8, 2 * n, 1, q1) DEV(9, 2 * n, 1, r1) DEV(10, n, 1, q2)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_decrypt_batch_dev(g_engine, N, q, p, f->p, fp->p, e->p, B, value->p, q1 ? q1->p : NULL, r1 ? r1->p : NULL,
-                                         q2 ? q2->p : NULL));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* sumGroupsDev(N, mod, rows:handle[B*N u16], weights:handle[B u16]|null, offsets:handle[(G+1) i64]|null, K, G, B, out:handle[G*N u16]).
- * The offsets live on the device, so the handle sizes are checked against the B the caller states: offsets[G] <= B is the caller's
- * promise. */
-static napi_value SumGroupsDev(napi_env env, napi_callback_info info) {
-  ARGS(9)
-  int32_t N, mod, K, G, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[5], &K) || !get_i32(env, argv[6], &G) ||
-      !get_i32(env, argv[7], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
-  DEV(2, 2 * (size_t)N * (size_t)B, 0, rows) DEV(3, 2 * (size_t)B, 1, w) DEV(4, 8 * ((size_t)G + 1), 1, off) DEV(8, 2 * (size_t)N * (size_t)G, 0, out)
-  if (!off && !groups_fit(NULL, K, G, B)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_sum_groups_dev(g_engine, N, mod, rows->p, w ? w->p : NULL, off ? off->p : NULL, K, G, out->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* tallyDecryptBatchDev(N, q, p, f:handle[N i8], fp:handle[N u8], rows:handle, weights:handle|null, offsets:handle|null, K, G, B,
- *                      sum:handle[G*N u16], value:handle[G*N u8], quot1:handle|null, rem1:handle|null, quot2:handle|null) */
-static napi_value TallyDecryptBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(16)
-  int32_t N, q, p, K, G, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
-      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
-  const size_t gn = (size_t)N * (size_t)G;
-  DEV(3, (size_t)N, 0, f) DEV(4, (size_t)N, 0, fp) DEV(5, 2 * (size_t)N * (size_t)B, 0, rows) DEV(6, 2 * (size_t)B, 1, w)
-  DEV(7, 8 * ((size_t)G + 1), 1, off) DEV(11, 2 * gn, 0, sum) DEV(12, gn, 0, value) DEV(13, 2 * gn, 1, q1) DEV(14, 2 * gn, 1, r1) DEV(15, gn, 1, q2)
-  if (!off && !groups_fit(NULL, K, G, B)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_tally_decrypt_batch_dev(g_engine, N, q, p, f->p, fp->p, rows->p, w ? w->p : NULL, off ? off->p : NULL, K, G, sum->p,
-                                               value->p, q1 ? q1->p : NULL, r1 ? r1->p : NULL, q2 ? q2->p : NULL));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* encryptPeritemBatchDev(N, q, h:handle[B*N u16], r:handle[B*N u8], m:handle[B*N u8], B, e:handle[B*N u16], quotE:handle|null) */
-static napi_value EncryptPeritemBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(2, 2 * n, 0, h) DEV(3, n, 0, r) DEV(4, n, 0, m) DEV(6, 2 * n, 0, e) DEV(7, 2 * n, 1, quot)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_encrypt_peritem_batch_dev(g_engine, N, q, h->p, r->p, m->p, B, e->p, quot ? quot->p : NULL));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* decryptPeritemBatchDev(N, q, p, f:handle[B*N i8], fp:handle[B*N u8], e:handle[B*N u16], B, value:handle[B*N u8],
- *                        quot1:handle|null, rem1:handle|null, quot2:handle|null) */
-static napi_value DecryptPeritemBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(11)
-  int32_t N, q, p, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[6], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(3, n, 0, f) DEV(4, n, 0, fp) DEV(5, 2 * n, 0, e) DEV(7, n, 0, value) DEV(8, 2 * n, 1, q1) DEV(9, 2 * n, 1, r1) DEV(10, n, 1, q2)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_decrypt_peritem_batch_dev(g_engine, N, q, p, f->p, fp->p, e->p, B, value->p, q1 ? q1->p : NULL,
-                                                 r1 ? r1->p : NULL, q2 ? q2->p : NULL));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
 /* packBatchDev(maxVal, dataLen, data:handle, B, out:handle[B*outputSize*32 bytes], bytes:boolean)   bytes: data holds uint8 values */
 static napi_value PackBatchDev(napi_env env, napi_callback_info info) {
   ARGS(6)
-  int32_t max_val, data_len, B; bool is_bytes; int ok;
+  int32_t max_val, data_len, B; bool is_bytes; int ok_data, ok_out;
   if (!get_i32(env, argv[0], &max_val) || !get_i32(env, argv[1], &data_len) || !get_i32(env, argv[3], &B) || data_len < 0 || B < 0 ||
       napi_get_value_bool(env, argv[5], &is_bytes) != napi_ok) BAD_ARGS();
   int bits, per, al, os;
   if (ntru_pack_params(max_val, data_len, &bits, &per, &al, &os)) return throw_engine(env, NTRU_ERR_ARG);
-  DEV(2, (size_t)B * (size_t)data_len * (is_bytes ? 1 : 2), 0, data) DEV(4, (size_t)B * (size_t)os * 32, 0, out)
+  DevBuf *data = get_dev(env, argv[2], (size_t)B * (size_t)data_len * (is_bytes ? 1 : 2), 0, &ok_data);
+  DevBuf *out = get_dev(env, argv[4], (size_t)B * (size_t)os * 32, 0, &ok_out);
+  if (!ok_data || !ok_out) BAD_ARGS();
   if (!ensure_engine(env)) return NULL;
   int rc;
   ENGINE_CALL(rc, is_bytes ? ntru_pack_bytes_batch_dev(g_engine, max_val, data_len, data->p, B, out->p)
@@ -797,67 +399,7 @@ static napi_value PackBatchDev(napi_env env, napi_callback_info info) {
   return rc ? throw_engine(env, rc) : undefined(env);
 }
 
-/* verifyKeysBatchDev(N, q, p, f, g:handle[B*N i8], fq:handle[B*N u16], fp:handle[B*N u8], h:handle[B*N u16], B,
- *                    quotFq, remFq:handle[B*N u16], quotFp, remFp:handle[B*N u8], quotH, remH:handle[B*N u16], flags:handle[B]) */
-static napi_value VerifyKeysBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(16)
-  int32_t N, q, p, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(3, n, 0, f) DEV(4, n, 0, g) DEV(5, 2 * n, 0, fq) DEV(6, n, 0, fp) DEV(7, 2 * n, 0, h)
-  DEV(9, 2 * n, 0, o1) DEV(10, 2 * n, 0, o2) DEV(11, n, 0, o3) DEV(12, n, 0, o4) DEV(13, 2 * n, 0, o5) DEV(14, 2 * n, 0, o6)
-  DEV(15, (size_t)B, 0, fl)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_verify_keys_batch_dev(g_engine, N, q, p, f->p, g->p, fq->p, fp->p, h->p, B, o1->p, o2->p, o3->p, o4->p, o5->p,
-                                             o6->p, fl->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* invertKeyBatchDev(N, q, p, f:handle[B*N i8], B, fq:handle[B*N u16]|null, fp:handle[B*N u8]|null, flags:handle[B]) */
-static napi_value InvertKeyBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, p, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[4], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(3, n, 0, f) DEV(5, 2 * n, 1, fq) DEV(6, n, 1, fp) DEV(7, (size_t)B, 0, fl)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_invert_key_batch_dev(g_engine, N, q, p, f->p, B, fq ? fq->p : NULL, fp ? fp->p : NULL, fl->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* publicKeyBatchDev(N, q, p, fq:handle[B*N u16], g:handle[B*N i8], B, h:handle[B*N u16]) */
-static napi_value PublicKeyBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(7)
-  int32_t N, q, p, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[5], &B) ||
-      N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(3, 2 * n, 0, fq) DEV(4, n, 0, g) DEV(6, 2 * n, 0, h)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_public_key_batch_dev(g_engine, N, q, p, fq->p, g->p, B, h->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* polymulSplitDev(N, mod, a:handle[B*N u16], b:handle[B*N u16], B, quot:handle[B*N u16], rem:handle[B*N u16]) */
-static napi_value PolymulSplitDev(napi_env env, napi_callback_info info) {
-  ARGS(7)
-  int32_t N, mod, B; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &mod) || !get_i32(env, argv[4], &B) || N < 1 || B < 0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(2, 2 * n, 0, a) DEV(3, 2 * n, 0, b) DEV(5, 2 * n, 0, quot) DEV(6, 2 * n, 0, rem)
-  if (!ensure_engine(env)) return NULL;
-  int rc;
-  ENGINE_CALL(rc, ntru_polymul_split_dev(g_engine, N, mod, a->p, b->p, B, quot->p, rem->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* ---- key generation (ntru_keygen_batch): generatePrivateKeyF + generateNewPublicKeyGH for B items, non-units redrawn on the device.
- * keygenWorkspaceBytes(N, B) -> bytes of the workspace handle keygenBatchDev needs */
+/* keygenWorkspaceBytes(N, B) -> bytes of the workspace handle keygenBatchDev needs */
 static napi_value KeygenWorkspaceBytes(napi_env env, napi_callback_info info) {
   ARGS(2)
   int32_t N, B;
@@ -870,80 +412,290 @@ static napi_value KeygenWorkspaceBytes(napi_env env, napi_callback_info info) {
   return v;
 }
 
-/* The arguments shared by keygenBatch / keygenBatchAsync: (N, q, p, df, dg, key:Uint32Array[8], firstItem, maxTries, B,
- * f:Int8Array|null, g:Int8Array|null, fq:Uint16Array|null, fp:Uint8Array|null, h:Uint16Array|null, tries:Uint8Array|null,
- * flags:Uint8Array[B], packedH:BigUint64Array[B*outputSize*4]|null); ptr = key, f, g, fq, fp, h, tries, flags, packedH. */
-typedef struct { int32_t N, q, p, df, dg, max_tries, B; uint64_t first; void *ptr[9]; } KeygenArgs;
-static int keygen_args(napi_env env, napi_value *argv, KeygenArgs *a) {
-  double first;
-  if (!get_i32(env, argv[0], &a->N) || !get_i32(env, argv[1], &a->q) || !get_i32(env, argv[2], &a->p) || !get_i32(env, argv[3], &a->df) ||
-      !get_i32(env, argv[4], &a->dg) || napi_get_value_double(env, argv[6], &first) != napi_ok || !get_i32(env, argv[7], &a->max_tries) ||
-      !get_i32(env, argv[8], &a->B) || a->N < 1 || a->B < 0 || first < 0 || first > 9007199254740991.0) return 0;
-  a->first = (uint64_t)first;
-  const size_t n = (size_t)a->N * (size_t)a->B;
-  size_t need_packed = 0;
+/* ---- the batch calls.  Each engine operation is described ONCE, as a row of ops[] below: its JS arguments in order, and a run() that
+ *      spells the engine call from the parsed arguments.  The JS forms are derived from the row by parse_call and three entry points:
+ *        name(...)       on host TypedArrays;
+ *        nameDev(...)    on device-buffer handles: every BUF becomes a handle of at least the same BYTES (elements * element width),
+ *                        a HOSTBUF stays a TypedArray; checked before anything is launched;
+ *        nameAsync(...)  the host form on a libuv worker thread, -> Promise<undefined>.
+ *      A new call is one run function and one row. */
+#define MAX_ARGS 17
+#define MAX_BUFS 12
+
+typedef struct {
+  int32_t N, q, p, B, K, G, n1, n2, other, nq, np, df, dg, max_tries;   /* the int32 arguments, by name (a modulus of any name is q) */
+  uint64_t first;                                                      /* firstItem */
+  void *ptr[MAX_BUFS];                   /* the buffers in argument order: host pointers, device pointers in the Dev form; NULL = absent */
+} Args;
+
+enum { A_END, A_INT, A_FIRST, A_BUF };
+/* How many elements a buffer needs.  SZ_PACKED_*: B rows of packOutput field elements, four uint64 limbs each. */
+enum { SZ_N, SZ_B, SZ_NB, SZ_2NB, SZ_N1B, SZ_GN, SZ_G1, SZ_KEY, SZ_PACKED_Q, SZ_PACKED_PIPELINE, SZ_KEYGEN_WORK };
+enum { OPTIONAL = 1, HOST_ALWAYS = 2, OFFSETS = 4 };
+typedef struct { uint8_t kind, field, type, size, flags; } Arg;
+#define INT(f) {A_INT, offsetof(Args, f), 0, 0, 0}                /* int32 */
+#define FIRST {A_FIRST, 0, 0, 0, 0}                               /* Number, an integer 0 .. 2^53 - 1 */
+#define BUF(t, sz) {A_BUF, 0, t, sz, 0}
+#define OPT(t, sz) {A_BUF, 0, t, sz, OPTIONAL}                    /* may be null / undefined */
+#define HOSTBUF(t, sz) {A_BUF, 0, t, sz, HOST_ALWAYS}
+#define OFFS {A_BUF, 0, I64, SZ_G1, OPTIONAL | OFFSETS}           /* the offsets of a sum: groups_fit is applied after parsing */
+#define I8 napi_int8_array
+#define U8 napi_uint8_array
+#define U16 napi_uint16_array
+#define U32 napi_uint32_array
+#define I64 napi_bigint64_array
+#define U64 napi_biguint64_array
+
+typedef struct {
+  const char *name;                      /* of the host form; the others append Dev / Async */
+  int forms;
+  int (*run)(const Args *a, int dev);    /* called under g_lock, on the JS thread or on a worker */
+  Arg args[MAX_ARGS + 1];
+} Op;
+enum { HOST = 1, DEV = 2, ASYNC = 4 };
+
+/* The groups of a sum over B rows: offsets (BigInt64Array[G + 1], non-decreasing, 0 <= offsets[0], offsets[G] <= B) or uniform K with
+ * G * K == B.  Only what keeps the engine inside the arrays is checked here; the engine reports the rest. */
+static int groups_fit(const int64_t *off, int64_t K, int64_t G, int64_t B) {
+  if (G < 0 || B < 0) return 0;
+  if (!off) return K >= 1 && G <= B / K + 1 && G * K == B;
+  if (off[0] < 0) return 0;
+  for (int64_t g = 0; g < G; g++) if (off[g + 1] < off[g]) return 0;
+  return off[G] <= B;
+}
+
+static size_t packed_elems(int max_val, const Args *a) {           /* 0 where ntru_pack_params refuses: the engine call reports it */
   int bits, per, al, os;
-  if (ntru_pack_params(a->q - 1, a->N, &bits, &per, &al, &os) == 0) need_packed = (size_t)a->B * (size_t)os * 4;
-  return get_buf(env, argv[5], napi_uint32_array, 8, 0, &a->ptr[0]) && get_buf(env, argv[9], napi_int8_array, n, 1, &a->ptr[1]) &&
-         get_buf(env, argv[10], napi_int8_array, n, 1, &a->ptr[2]) && get_buf(env, argv[11], napi_uint16_array, n, 1, &a->ptr[3]) &&
-         get_buf(env, argv[12], napi_uint8_array, n, 1, &a->ptr[4]) && get_buf(env, argv[13], napi_uint16_array, n, 1, &a->ptr[5]) &&
-         get_buf(env, argv[14], napi_uint8_array, (size_t)a->B, 1, &a->ptr[6]) &&
-         get_buf(env, argv[15], napi_uint8_array, (size_t)a->B, 0, &a->ptr[7]) &&
-         get_buf(env, argv[16], napi_biguint64_array, need_packed, 1, &a->ptr[8]);
-}
-static int keygen_run(const KeygenArgs *a) {
-  return ntru_keygen_batch(g_engine, a->N, a->q, a->p, a->df, a->dg, a->ptr[0], a->first, a->max_tries, a->B, a->ptr[1], a->ptr[2],
-                           a->ptr[3], a->ptr[4], a->ptr[5], a->ptr[6], a->ptr[7], a->ptr[8]);
+  return ntru_pack_params(max_val, a->N, &bits, &per, &al, &os) == 0 ? (size_t)a->B * (size_t)os * 4 : 0;
 }
 
-/* keygenBatch(...the arguments above...): host arrays; returns when every asked-for array is filled */
-static napi_value KeygenBatch(napi_env env, napi_callback_info info) {
-  ARGS(17)
-  KeygenArgs a;
-  if (!keygen_args(env, argv, &a)) BAD_ARGS();
+/* Throws the engine's error and returns 0 where the keygen workspace has no size (N out of range). */
+static int elems(napi_env env, int rule, const Args *a, size_t *need) {
+  const size_t N = (size_t)a->N, B = (size_t)a->B, G = (size_t)a->G;
+  switch (rule) {
+    case SZ_N: *need = N; break;
+    case SZ_B: *need = B; break;
+    case SZ_NB: *need = N * B; break;
+    case SZ_2NB: *need = 2 * N * B; break;                        /* splitByI's dividends */
+    case SZ_N1B: *need = (N + 1) * B; break;                      /* witness rows with the trailing [N]-th coefficient */
+    case SZ_GN: *need = G * N; break;
+    case SZ_G1: *need = G + 1; break;
+    case SZ_KEY: *need = 8; break;
+    case SZ_PACKED_Q: *need = packed_elems(a->q - 1, a); break;
+    case SZ_PACKED_PIPELINE: *need = packed_elems(a->ptr[1] ? a->p - 1 : a->q - 1, a); break;   /* ptr[1] = f: value is packed, else e */
+    default: {                                                    /* SZ_KEYGEN_WORK, in bytes */
+      int rc = ntru_keygen_workspace_bytes(a->N, a->B, need);
+      if (rc) { throw_engine(env, rc); return 0; }
+    }
+  }
+  return 1;
+}
+
+/* Reads the arguments of a call as its row (the `data` of the property) describes them, into *a and argv[MAX_ARGS].  Validation first,
+ * then the engine must exist; on any refusal throws and returns NULL. */
+static const Op *parse_call(napi_env env, napi_callback_info info, int dev, Args *a, napi_value *argv) {
+  size_t argc = MAX_ARGS, nargs = 0;
+  void *data = NULL;
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, &data));
+  const Op *op = (const Op *)data;
+  while (op->args[nargs].kind != A_END) nargs++;
+  if (argc < nargs) { napi_throw_type_error(env, NULL, "too few arguments"); return NULL; }
+  memset(a, 0, sizeof *a);
+  for (size_t i = 0; i < nargs; i++) {                            /* the scalars first: the sizes of the buffers depend on them */
+    const Arg *g = &op->args[i];
+    double first;
+    if (g->kind == A_INT && !get_i32(env, argv[i], (int32_t *)((char *)a + g->field))) BAD_ARGS();
+    if (g->kind != A_FIRST) continue;
+    if (napi_get_value_double(env, argv[i], &first) != napi_ok || first < 0 || first > 9007199254740991.0) BAD_ARGS();
+    a->first = (uint64_t)first;
+  }
+  if (a->N < 1 || a->B < 0 || a->G < 0) BAD_ARGS();
+  int nbuf = 0, grouped = 0;
+  const void *offsets = NULL;
+  for (size_t i = 0; i < nargs; i++) {
+    const Arg *g = &op->args[i];
+    if (g->kind != A_BUF) continue;
+    const int optional = g->flags & OPTIONAL;
+    size_t need;
+    if (!elems(env, g->size, a, &need)) return NULL;
+    if (dev && !(g->flags & HOST_ALWAYS)) {
+      int ok;
+      DevBuf *b = get_dev(env, argv[i], need * elem_width[g->type], optional, &ok);
+      if (!ok) BAD_ARGS();
+      a->ptr[nbuf] = b ? b->p : NULL;
+    } else if (!get_buf(env, argv[i], (napi_typedarray_type)g->type, need, optional, &a->ptr[nbuf])) BAD_ARGS();
+    if (g->flags & OFFSETS) { grouped = 1; offsets = a->ptr[nbuf]; }
+    nbuf++;
+  }
+  /* offsets on the device cannot be read here: the handle sizes were checked against the B the caller states, offsets[G] <= B is the
+   * caller's promise */
+  if (grouped && !(dev && offsets) && !groups_fit((const int64_t *)offsets, a->K, a->G, a->B)) BAD_ARGS();
   if (!ensure_engine(env)) return NULL;
+  return op;
+}
+
+#define RUN(name) static int name(const Args *a, int dev)
+#define P(i) a->ptr[i]
+RUN(run_polymul_split) {
+  return dev ? ntru_polymul_split_dev(g_engine, a->N, a->q, P(0), P(1), a->B, P(2), P(3))
+             : ntru_polymul_split(g_engine, a->N, a->q, P(0), P(1), a->B, P(2), P(3));
+}
+RUN(run_split_by_I) { (void)dev; return ntru_split_by_I(g_engine, a->N, a->q, P(0), a->B, P(1), P(2)); }
+RUN(run_add) { (void)dev; return ntru_add_batch(g_engine, a->N, a->q, P(0), P(1), a->B, P(2)); }
+RUN(run_invert_key) {
+  return dev ? ntru_invert_key_batch_dev(g_engine, a->N, a->q, a->p, P(0), a->B, P(1), P(2), P(3))
+             : ntru_invert_key_batch(g_engine, a->N, a->q, a->p, P(0), a->B, P(1), P(2), P(3));
+}
+RUN(run_public_key) {
+  return dev ? ntru_public_key_batch_dev(g_engine, a->N, a->q, a->p, P(0), P(1), a->B, P(2))
+             : ntru_public_key_batch(g_engine, a->N, a->q, a->p, P(0), P(1), a->B, P(2));
+}
+/* useDevices([...]) shards the host forms of encrypt, decrypt and verifyKeys over its devices, synchronous or not */
+RUN(run_encrypt) {
+  if (dev) return ntru_encrypt_batch_dev(g_engine, a->N, a->q, P(0), P(1), P(2), a->B, P(3), P(4));
+  return g_multi ? ntru_multi_encrypt_batch(g_multi, a->N, a->q, P(0), P(1), P(2), a->B, P(3), P(4))
+                 : ntru_encrypt_batch(g_engine, a->N, a->q, P(0), P(1), P(2), a->B, P(3), P(4));
+}
+RUN(run_decrypt) {
+  if (dev) return ntru_decrypt_batch_dev(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), a->B, P(3), P(4), P(5), P(6));
+  return g_multi ? ntru_multi_decrypt_batch(g_multi, a->N, a->q, a->p, P(0), P(1), P(2), a->B, P(3), P(4), P(5), P(6))
+                 : ntru_decrypt_batch(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), a->B, P(3), P(4), P(5), P(6));
+}
+RUN(run_encrypt_peritem) {
+  return dev ? ntru_encrypt_peritem_batch_dev(g_engine, a->N, a->q, P(0), P(1), P(2), a->B, P(3), P(4))
+             : ntru_encrypt_peritem_batch(g_engine, a->N, a->q, P(0), P(1), P(2), a->B, P(3), P(4));
+}
+RUN(run_decrypt_peritem) {
+  return dev ? ntru_decrypt_peritem_batch_dev(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), a->B, P(3), P(4), P(5), P(6))
+             : ntru_decrypt_peritem_batch(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), a->B, P(3), P(4), P(5), P(6));
+}
+RUN(run_verify_keys) {
+  if (dev) return ntru_verify_keys_batch_dev(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), P(3), P(4), a->B, P(5), P(6), P(7), P(8), P(9), P(10), P(11));
+  return g_multi ? ntru_multi_verify_keys_batch(g_multi, a->N, a->q, a->p, P(0), P(1), P(2), P(3), P(4), a->B, P(5), P(6), P(7), P(8), P(9), P(10), P(11))
+                 : ntru_verify_keys_batch(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), P(3), P(4), a->B, P(5), P(6), P(7), P(8), P(9), P(10), P(11));
+}
+/* Witness checks: the signals in the order of the template's inputs (circuits/ntru.circom) */
+RUN(run_check_encrypt) { (void)dev; return ntru_check_encrypt_batch(g_engine, a->N, a->q, a->nq, P(0), P(1), P(2), P(3), P(4), a->B, P(5)); }
+RUN(run_check_decrypt) {
+  (void)dev;
+  return ntru_check_decrypt_batch(g_engine, a->N, a->q, a->nq, a->p, a->np, P(0), P(1), P(2), P(3), P(4), P(5), P(6), a->B, P(7));
+}
+RUN(run_check_inverse) { (void)dev; return ntru_check_inverse_batch(g_engine, a->N, a->q, a->nq, P(0), P(1), P(2), P(3), a->B, P(4)); }
+RUN(run_sample_ternary) {
+  return dev ? ntru_sample_ternary_dev(g_engine, a->N, a->n1, a->n2, a->other, P(0), a->first, a->B, P(1))
+             : ntru_sample_ternary(g_engine, a->N, a->n1, a->n2, a->other, P(0), a->first, a->B, P(1));
+}
+/* sampler -> encryptBits -> decryptBits -> packOutput on the GPU for a batch of host plaintexts */
+RUN(run_pipeline) {
+  (void)dev;
+  return ntru_pipeline_batch(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), P(3), a->first, a->n1, a->n2, P(4), P(5), a->B, P(6), P(7), P(8), P(9));
+}
+RUN(run_sum_groups) {
+  return dev ? ntru_sum_groups_dev(g_engine, a->N, a->q, P(0), P(1), P(2), a->K, a->G, P(3))
+             : ntru_sum_groups(g_engine, a->N, a->q, P(0), P(1), P(2), a->K, a->G, P(3));
+}
+RUN(run_tally_decrypt) {
+  return dev ? ntru_tally_decrypt_batch_dev(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), P(3), P(4), a->K, a->G, P(5), P(6), P(7), P(8), P(9))
+             : ntru_tally_decrypt_batch(g_engine, a->N, a->q, a->p, P(0), P(1), P(2), P(3), P(4), a->K, a->G, P(5), P(6), P(7), P(8), P(9));
+}
+/* generatePrivateKeyF + generateNewPublicKeyGH for B items, non-units redrawn on the device.  The Dev form has a list of its own: a
+ * workspace handle of keygenWorkspaceBytes(N, B), every output but tries needed, no packedH; it waits for the engine's stream once per
+ * call and once per redraw pass (a 4-byte count). */
+RUN(run_keygen) {
+  (void)dev;
+  return ntru_keygen_batch(g_engine, a->N, a->q, a->p, a->df, a->dg, P(0), a->first, a->max_tries, a->B, P(1), P(2), P(3), P(4), P(5), P(6), P(7), P(8));
+}
+RUN(run_keygen_dev) {
+  (void)dev;
+  return ntru_keygen_batch_dev(g_engine, a->N, a->q, a->p, a->df, a->dg, P(0), a->first, a->max_tries, a->B, P(1), P(2), P(3), P(4), P(5), P(6), P(7), P(8));
+}
+
+/* The JS argument lists.  Rows are [B][N] unless the size says otherwise; BUF / OPT name the element type of the host form. */
+static const Op ops[] = {
+  /* (N, mod, a, b, B, quot, rem) */
+  {"polymulSplit", HOST | DEV, run_polymul_split, {INT(N), INT(q), BUF(U16, SZ_NB), BUF(U16, SZ_NB), INT(B), BUF(U16, SZ_NB), BUF(U16, SZ_NB)}},
+  /* (N, mod, a[B][2N], B, quot, rem) */
+  {"splitByI", HOST, run_split_by_I, {INT(N), INT(q), BUF(U16, SZ_2NB), INT(B), BUF(U16, SZ_NB), BUF(U16, SZ_NB)}},
+  /* (N, mod, a, b, B, out) */
+  {"addBatch", HOST, run_add, {INT(N), INT(q), BUF(U16, SZ_NB), BUF(U16, SZ_NB), INT(B), BUF(U16, SZ_NB)}},
+  /* (N, q, p, f, B, fq|null, fp|null, flags[B]) */
+  {"invertKeyBatch", HOST | DEV, run_invert_key,
+   {INT(N), INT(q), INT(p), BUF(I8, SZ_NB), INT(B), OPT(U16, SZ_NB), OPT(U8, SZ_NB), BUF(U8, SZ_B)}},
+  /* (N, q, p, fq, g, B, h) */
+  {"publicKeyBatch", HOST | DEV, run_public_key, {INT(N), INT(q), INT(p), BUF(U16, SZ_NB), BUF(I8, SZ_NB), INT(B), BUF(U16, SZ_NB)}},
+  /* (N, q, h[N], r, m, B, e, quotE|null) */
+  {"encryptBatch", HOST | DEV | ASYNC, run_encrypt,
+   {INT(N), INT(q), BUF(U16, SZ_N), BUF(U8, SZ_NB), BUF(U8, SZ_NB), INT(B), BUF(U16, SZ_NB), OPT(U16, SZ_NB)}},
+  /* (N, q, p, f[N], fp[N], e, B, value, quot1|null, rem1|null, quot2|null) */
+  {"decryptBatch", HOST | DEV | ASYNC, run_decrypt,
+   {INT(N), INT(q), INT(p), BUF(I8, SZ_N), BUF(U8, SZ_N), BUF(U16, SZ_NB), INT(B), BUF(U8, SZ_NB), OPT(U16, SZ_NB), OPT(U16, SZ_NB), OPT(U8, SZ_NB)}},
+  /* the same two with row b under key b: h, f, fp are [B][N] */
+  {"encryptPeritemBatch", HOST | DEV, run_encrypt_peritem,
+   {INT(N), INT(q), BUF(U16, SZ_NB), BUF(U8, SZ_NB), BUF(U8, SZ_NB), INT(B), BUF(U16, SZ_NB), OPT(U16, SZ_NB)}},
+  {"decryptPeritemBatch", HOST | DEV, run_decrypt_peritem,
+   {INT(N), INT(q), INT(p), BUF(I8, SZ_NB), BUF(U8, SZ_NB), BUF(U16, SZ_NB), INT(B), BUF(U8, SZ_NB), OPT(U16, SZ_NB), OPT(U16, SZ_NB), OPT(U8, SZ_NB)}},
+  /* (N, q, p, f, g, fq, fp, h, B, quotFq, remFq, quotFp, remFp, quotH, remH, flags[B]) */
+  {"verifyKeysBatch", HOST | DEV, run_verify_keys,
+   {INT(N), INT(q), INT(p), BUF(I8, SZ_NB), BUF(I8, SZ_NB), BUF(U16, SZ_NB), BUF(U8, SZ_NB), BUF(U16, SZ_NB), INT(B), BUF(U16, SZ_NB), BUF(U16, SZ_NB),
+    BUF(U8, SZ_NB), BUF(U8, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U8, SZ_B)}},
+  /* (N, q, nq, r, m, h, quotientE[B][N+1], remainderE[B][N+1], B, flags[B]) */
+  {"checkEncryptBatch", HOST, run_check_encrypt,
+   {INT(N), INT(q), INT(nq), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_N1B), BUF(U16, SZ_N1B), INT(B), BUF(U8, SZ_B)}},
+  /* (N, q, nq, p, np, f, fp, e, quotient1, remainder1, quotient2, remainder2 (the last four [B][N+1]), B, flags[B]) */
+  {"checkDecryptBatch", HOST, run_check_decrypt,
+   {INT(N), INT(q), INT(nq), INT(p), INT(np), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_N1B), BUF(U16, SZ_N1B), BUF(U16, SZ_N1B),
+    BUF(U16, SZ_N1B), INT(B), BUF(U8, SZ_B)}},
+  /* (N, M, n, f, fq, quotientI[B][N+1], remainderI[B][N+1], B, flags[B]) */
+  {"checkInverseBatch", HOST, run_check_inverse,
+   {INT(N), INT(q), INT(nq), BUF(U16, SZ_NB), BUF(U16, SZ_NB), BUF(U16, SZ_N1B), BUF(U16, SZ_N1B), INT(B), BUF(U8, SZ_B)}},
+  /* (N, n1, n2, other, key:Uint32Array[8], firstItem, B, out) */
+  {"sampleTernary", HOST | DEV, run_sample_ternary,
+   {INT(N), INT(n1), INT(n2), INT(other), HOSTBUF(U32, SZ_KEY), FIRST, INT(B), BUF(U8, SZ_NB)}},
+  /* (N, q, p, h[N], f[N]|null, fp[N]|null, key[8]|null, firstItem, n1, n2, r|null, m, B, rOut|null, e|null, value|null,
+   *  packed:BigUint64Array[B][outputSize][4]|null) */
+  {"pipelineBatch", HOST | ASYNC, run_pipeline,
+   {INT(N), INT(q), INT(p), BUF(U16, SZ_N), OPT(I8, SZ_N), OPT(U8, SZ_N), OPT(U32, SZ_KEY), FIRST, INT(n1), INT(n2), OPT(U8, SZ_NB), BUF(U8, SZ_NB),
+    INT(B), OPT(U8, SZ_NB), OPT(U16, SZ_NB), OPT(U8, SZ_NB), OPT(U64, SZ_PACKED_PIPELINE)}},
+  /* (N, mod, rows, weights[B]|null, offsets:BigInt64Array[G+1]|null, K, G, B, out[G][N]) */
+  {"sumGroups", HOST | DEV, run_sum_groups,
+   {INT(N), INT(q), BUF(U16, SZ_NB), OPT(U16, SZ_B), OFFS, INT(K), INT(G), INT(B), BUF(U16, SZ_GN)}},
+  /* (N, q, p, f[N], fp[N], rows, weights[B]|null, offsets[G+1]|null, K, G, B, sum[G][N], value[G][N], quot1|null, rem1|null, quot2|null) */
+  {"tallyDecryptBatch", HOST | DEV | ASYNC, run_tally_decrypt,
+   {INT(N), INT(q), INT(p), BUF(I8, SZ_N), BUF(U8, SZ_N), BUF(U16, SZ_NB), OPT(U16, SZ_B), OFFS, INT(K), INT(G), INT(B), BUF(U16, SZ_GN),
+    BUF(U8, SZ_GN), OPT(U16, SZ_GN), OPT(U16, SZ_GN), OPT(U8, SZ_GN)}},
+  /* (N, q, p, df, dg, key[8], firstItem, maxTries, B, f|null, g|null, fq|null, fp|null, h|null, tries[B]|null, flags[B],
+   *  packedH:BigUint64Array[B][outputSize][4]|null) */
+  {"keygenBatch", HOST | ASYNC, run_keygen,
+   {INT(N), INT(q), INT(p), INT(df), INT(dg), BUF(U32, SZ_KEY), FIRST, INT(max_tries), INT(B), OPT(I8, SZ_NB), OPT(I8, SZ_NB), OPT(U16, SZ_NB),
+    OPT(U8, SZ_NB), OPT(U16, SZ_NB), OPT(U8, SZ_B), BUF(U8, SZ_B), OPT(U64, SZ_PACKED_Q)}},
+  /* keygenBatchDev(N, q, p, df, dg, key[8], firstItem, maxTries, B, work, f, g, fq, fp, h, tries[B]|null, flags[B]) */
+  {"keygenBatch", DEV, run_keygen_dev,
+   {INT(N), INT(q), INT(p), INT(df), INT(dg), HOSTBUF(U32, SZ_KEY), FIRST, INT(max_tries), INT(B), BUF(U8, SZ_KEYGEN_WORK), BUF(I8, SZ_NB),
+    BUF(I8, SZ_NB), BUF(U16, SZ_NB), BUF(U8, SZ_NB), BUF(U16, SZ_NB), OPT(U8, SZ_B), BUF(U8, SZ_B)}},
+};
+
+static napi_value call_sync(napi_env env, napi_callback_info info, int dev) {
+  napi_value argv[MAX_ARGS];
+  Args a;
+  const Op *op = parse_call(env, info, dev, &a, argv);
+  if (!op) return NULL;
   int rc;
-  ENGINE_CALL(rc, keygen_run(&a));
+  ENGINE_CALL(rc, op->run(&a, dev));
   return rc ? throw_engine(env, rc) : undefined(env);
 }
+static napi_value CallHost(napi_env env, napi_callback_info info) { return call_sync(env, info, 0); }
+static napi_value CallDev(napi_env env, napi_callback_info info) { return call_sync(env, info, 1); }
 
-/* keygenBatchDev(N, q, p, df, dg, key:Uint32Array[8], firstItem, maxTries, B, work:handle[keygenWorkspaceBytes(N, B)],
- *                f, g:handle[B*N i8], fq:handle[B*N u16], fp:handle[B*N u8], h:handle[B*N u16], tries:handle[B]|null, flags:handle[B])
- * Waits for the engine's stream once per call and once per redraw pass (a 4-byte count). */
-static napi_value KeygenBatchDev(napi_env env, napi_callback_info info) {
-  ARGS(17)
-  int32_t N, q, p, df, dg, max_tries, B; double first; void *key; int ok;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[3], &df) ||
-      !get_i32(env, argv[4], &dg) || napi_get_value_double(env, argv[6], &first) != napi_ok || !get_i32(env, argv[7], &max_tries) ||
-      !get_i32(env, argv[8], &B) || N < 1 || B < 0 || first < 0 || first > 9007199254740991.0 ||
-      !get_buf(env, argv[5], napi_uint32_array, 8, 0, &key)) BAD_ARGS();
-  size_t wbytes = 0;
-  int rc = ntru_keygen_workspace_bytes(N, B, &wbytes);
-  if (rc) return throw_engine(env, rc);
-  const size_t n = (size_t)N * (size_t)B;
-  DEV(9, wbytes, 0, work) DEV(10, n, 0, f) DEV(11, n, 0, g) DEV(12, 2 * n, 0, fq) DEV(13, n, 0, fp) DEV(14, 2 * n, 0, h)
-  DEV(15, (size_t)B, 1, tries) DEV(16, (size_t)B, 0, fl)
-  if (!ensure_engine(env)) return NULL;
-  ENGINE_CALL(rc, ntru_keygen_batch_dev(g_engine, N, q, p, df, dg, key, (uint64_t)first, max_tries, B, work->p, f->p, g->p, fq->p, fp->p,
-                                        h->p, tries ? tries->p : NULL, fl->p));
-  return rc ? throw_engine(env, rc) : undefined(env);
-}
-
-/* ---- asynchronous batch calls (additive; the reference API stays synchronous).  encryptBatchAsync / decryptBatchAsync take
- *      the arguments of their synchronous twins and return a Promise; the engine call runs on a libuv worker thread, so the
- *      event loop keeps turning while a 2^18-item batch (tens of milliseconds of PCIe) is in flight.  The typed arrays are
- *      pinned by references until the Promise settles; the caller must not touch the output arrays before that. */
+/* ---- the Async form (additive; the reference API stays synchronous): the engine call runs on a libuv worker thread, so the event loop
+ *      keeps turning while a 2^18-item batch (tens of milliseconds of PCIe) is in flight.  The typed arrays are pinned by references
+ *      until the Promise settles; the caller must not touch the output arrays before that. */
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
-  napi_ref keep[12];
+  napi_ref keep[MAX_ARGS];
   int n_keep;
-  int kind;                       /* 0 encrypt, 1 decrypt, 2 pipeline, 3 keygen, 4 tally */
-  int N, q, p, B, n1, n2;
-  int64_t K, G;                   /* tally */
-  uint64_t first;
-  void *ptr[12];
-  KeygenArgs keygen;
+  const Op *op;
+  Args a;
   int rc;
   char err[400];
 } AsyncJob;
@@ -953,25 +705,8 @@ static void async_execute(napi_env env, void *data) {
   AsyncJob *j = (AsyncJob *)data;
   pthread_mutex_lock(&g_lock);
   if (!g_engine) { j->rc = NTRU_ERR_ARG; snprintf(j->err, sizeof j->err, "ntru engine not created"); }
-  else {
-    if (j->kind == 0)
-      j->rc = g_multi ? ntru_multi_encrypt_batch(g_multi, j->N, j->q, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4])
-                      : ntru_encrypt_batch(g_engine, j->N, j->q, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4]);
-    else if (j->kind == 3)
-      j->rc = keygen_run(&j->keygen);
-    else if (j->kind == 4)
-      j->rc = ntru_tally_decrypt_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->ptr[3], j->ptr[4], j->K, j->G, j->ptr[5],
-                                       j->ptr[6], j->ptr[7], j->ptr[8], j->ptr[9]);
-    else if (j->kind == 2)
-      j->rc = ntru_pipeline_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->ptr[3], j->first, j->n1, j->n2, j->ptr[4],
-                                  j->ptr[5], j->B, j->ptr[6], j->ptr[7], j->ptr[8], j->ptr[9]);
-    else
-      j->rc = g_multi ? ntru_multi_decrypt_batch(g_multi, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3],
-                                                 j->ptr[4], j->ptr[5], j->ptr[6])
-                      : ntru_decrypt_batch(g_engine, j->N, j->q, j->p, j->ptr[0], j->ptr[1], j->ptr[2], j->B, j->ptr[3], j->ptr[4],
-                                           j->ptr[5], j->ptr[6]);
-    if (j->rc) snprintf(j->err, sizeof j->err, "ntru engine error %d: %s", j->rc, ntru_last_error());   /* per thread: read it here */
-  }
+  else if ((j->rc = j->op->run(&j->a, 0)) != 0)
+    snprintf(j->err, sizeof j->err, "ntru engine error %d: %s", j->rc, ntru_last_error());   /* per thread: read it here */
   pthread_mutex_unlock(&g_lock);
 }
 
@@ -992,14 +727,22 @@ static void async_complete(napi_env env, napi_status status, void *data) {
   free(j);
 }
 
-static napi_value async_start(napi_env env, AsyncJob *j, napi_value *hold, int n_hold, const char *name) {
-  napi_value promise, rname;
+static napi_value CallAsync(napi_env env, napi_callback_info info) {
+  napi_value argv[MAX_ARGS], promise, rname;
+  Args a;
+  const Op *op = parse_call(env, info, 0, &a, argv);
+  if (!op) return NULL;
+  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
+  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
+  j->op = op; j->a = a;
   if (napi_create_promise(env, &j->deferred, &promise) != napi_ok) { free(j); napi_throw_error(env, NULL, "napi_create_promise failed"); return NULL; }
-  for (int i = 0; i < n_hold; i++) {
+  for (int i = 0; i < MAX_ARGS; i++) {                            /* every argument that is an object: the arrays */
     napi_valuetype vt;
-    if (napi_typeof(env, hold[i], &vt) == napi_ok && vt == napi_object &&
-        napi_create_reference(env, hold[i], 1, &j->keep[j->n_keep]) == napi_ok) j->n_keep++;
+    if (napi_typeof(env, argv[i], &vt) == napi_ok && vt == napi_object &&
+        napi_create_reference(env, argv[i], 1, &j->keep[j->n_keep]) == napi_ok) j->n_keep++;
   }
+  char name[64];
+  snprintf(name, sizeof name, "ntru.%sAsync", op->name);
   napi_create_string_utf8(env, name, NAPI_AUTO_LENGTH, &rname);
   if (napi_create_async_work(env, NULL, rname, async_execute, async_complete, j, &j->work) != napi_ok ||
       napi_queue_async_work(env, j->work) != napi_ok) {
@@ -1011,166 +754,28 @@ static napi_value async_start(napi_env env, AsyncJob *j, napi_value *hold, int n
   return promise;
 }
 
-/* encryptBatchAsync(N, q, h, r, m, B, e, quotE|null) -> Promise<undefined> */
-static napi_value EncryptBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(8)
-  int32_t N, q, B; void *h, *r, *m, *e, *quot;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[5], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[2], napi_uint16_array, (size_t)N, 0, &h) || !get_buf(env, argv[3], napi_uint8_array, n, 0, &r) ||
-      !get_buf(env, argv[4], napi_uint8_array, n, 0, &m) || !get_buf(env, argv[6], napi_uint16_array, n, 0, &e) ||
-      !get_buf(env, argv[7], napi_uint16_array, n, 1, &quot)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
-  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  j->kind = 0; j->N = N; j->q = q; j->B = B;
-  j->ptr[0] = h; j->ptr[1] = r; j->ptr[2] = m; j->ptr[3] = e; j->ptr[4] = quot;
-  napi_value hold[5] = {argv[2], argv[3], argv[4], argv[6], argv[7]};
-  return async_start(env, j, hold, 5, "ntru.encryptBatchAsync");
-}
-
-/* decryptBatchAsync(N, q, p, f, fp, e, B, value, quot1|null, rem1|null, quot2|null) -> Promise<undefined> */
-static napi_value DecryptBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(11)
-  int32_t N, q, p, B; void *f, *fp, *e, *value, *q1, *r1, *q2;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      !get_i32(env, argv[6], &B) || N < 1 || B < 0) BAD_ARGS();
-  size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
-      !get_buf(env, argv[5], napi_uint16_array, n, 0, &e) || !get_buf(env, argv[7], napi_uint8_array, n, 0, &value) ||
-      !get_buf(env, argv[8], napi_uint16_array, n, 1, &q1) || !get_buf(env, argv[9], napi_uint16_array, n, 1, &r1) ||
-      !get_buf(env, argv[10], napi_uint8_array, n, 1, &q2)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
-  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  j->kind = 1; j->N = N; j->q = q; j->p = p; j->B = B;
-  j->ptr[0] = f; j->ptr[1] = fp; j->ptr[2] = e; j->ptr[3] = value; j->ptr[4] = q1; j->ptr[5] = r1; j->ptr[6] = q2;
-  napi_value hold[7] = {argv[3], argv[4], argv[5], argv[7], argv[8], argv[9], argv[10]};
-  return async_start(env, j, hold, 7, "ntru.decryptBatchAsync");
-}
-
-/* tallyDecryptBatchAsync(...the arguments of tallyDecryptBatch...) -> Promise<undefined> */
-static napi_value TallyDecryptBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(16)
-  int32_t N, q, p, K, G, B; void *f, *fp, *rows, *w, *off, *sum, *value, *q1, *r1, *q2;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) || !get_i32(env, argv[8], &K) ||
-      !get_i32(env, argv[9], &G) || !get_i32(env, argv[10], &B) || N < 1 || G < 0 || B < 0) BAD_ARGS();
-  const size_t gn = (size_t)N * (size_t)G;
-  if (!get_buf(env, argv[3], napi_int8_array, (size_t)N, 0, &f) || !get_buf(env, argv[4], napi_uint8_array, (size_t)N, 0, &fp) ||
-      !get_buf(env, argv[5], napi_uint16_array, (size_t)N * (size_t)B, 0, &rows) || !get_buf(env, argv[6], napi_uint16_array, (size_t)B, 1, &w) ||
-      !get_buf(env, argv[7], napi_bigint64_array, (size_t)G + 1, 1, &off) || !get_buf(env, argv[11], napi_uint16_array, gn, 0, &sum) ||
-      !get_buf(env, argv[12], napi_uint8_array, gn, 0, &value) || !get_buf(env, argv[13], napi_uint16_array, gn, 1, &q1) ||
-      !get_buf(env, argv[14], napi_uint16_array, gn, 1, &r1) || !get_buf(env, argv[15], napi_uint8_array, gn, 1, &q2)) BAD_ARGS();
-  if (!groups_fit((const int64_t *)off, K, G, B)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
-  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  j->kind = 4; j->N = N; j->q = q; j->p = p; j->B = B; j->K = K; j->G = G;
-  j->ptr[0] = f; j->ptr[1] = fp; j->ptr[2] = rows; j->ptr[3] = w; j->ptr[4] = off; j->ptr[5] = sum; j->ptr[6] = value; j->ptr[7] = q1;
-  j->ptr[8] = r1; j->ptr[9] = q2;
-  napi_value hold[10] = {argv[3], argv[4], argv[5], argv[6], argv[7], argv[11], argv[12], argv[13], argv[14], argv[15]};
-  return async_start(env, j, hold, 10, "ntru.tallyBatchAsync");
-}
-
-/* pipelineBatchAsync(...the arguments of pipelineBatch...) -> Promise<undefined> */
-static napi_value PipelineBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(17)
-  int32_t N, q, p, n1, n2, B; double first; void *h, *f, *fp, *key, *r, *m, *r_out, *e, *value, *packed;
-  if (!get_i32(env, argv[0], &N) || !get_i32(env, argv[1], &q) || !get_i32(env, argv[2], &p) ||
-      napi_get_value_double(env, argv[7], &first) != napi_ok || !get_i32(env, argv[8], &n1) || !get_i32(env, argv[9], &n2) ||
-      !get_i32(env, argv[12], &B) || N < 1 || B < 0 || first < 0 || first > 9007199254740991.0) BAD_ARGS();
-  const size_t n = (size_t)N * (size_t)B;
-  if (!get_buf(env, argv[3], napi_uint16_array, (size_t)N, 0, &h) || !get_buf(env, argv[4], napi_int8_array, (size_t)N, 1, &f) ||
-      !get_buf(env, argv[5], napi_uint8_array, (size_t)N, 1, &fp) || !get_buf(env, argv[6], napi_uint32_array, 8, 1, &key) ||
-      !get_buf(env, argv[10], napi_uint8_array, n, 1, &r) || !get_buf(env, argv[11], napi_uint8_array, n, 0, &m) ||
-      !get_buf(env, argv[13], napi_uint8_array, n, 1, &r_out) || !get_buf(env, argv[14], napi_uint16_array, n, 1, &e) ||
-      !get_buf(env, argv[15], napi_uint8_array, n, 1, &value)) BAD_ARGS();
-  size_t need_packed = 0;
-  {
-    int bits, per, al, os;
-    if (ntru_pack_params(f ? p - 1 : q - 1, N, &bits, &per, &al, &os) == 0) need_packed = (size_t)B * (size_t)os * 4;
-  }
-  if (!get_buf(env, argv[16], napi_biguint64_array, need_packed, 1, &packed)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
-  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  j->kind = 2; j->N = N; j->q = q; j->p = p; j->B = B; j->n1 = n1; j->n2 = n2; j->first = (uint64_t)first;
-  void *ptrs[10] = {h, f, fp, key, r, m, r_out, e, value, packed};
-  memcpy(j->ptr, ptrs, sizeof ptrs);
-  napi_value hold[10] = {argv[3], argv[4], argv[5], argv[6], argv[10], argv[11], argv[13], argv[14], argv[15], argv[16]};
-  return async_start(env, j, hold, 10, "ntru.pipelineAsync");
-}
-
-/* keygenBatchAsync(...the arguments of keygenBatch...) -> Promise<undefined> */
-static napi_value KeygenBatchAsync(napi_env env, napi_callback_info info) {
-  ARGS(17)
-  KeygenArgs a;
-  if (!keygen_args(env, argv, &a)) BAD_ARGS();
-  if (!ensure_engine(env)) return NULL;
-  AsyncJob *j = (AsyncJob *)calloc(1, sizeof *j);
-  if (!j) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
-  j->kind = 3; j->keygen = a;
-  napi_value hold[9] = {argv[5], argv[9], argv[10], argv[11], argv[12], argv[13], argv[14], argv[15], argv[16]};
-  return async_start(env, j, hold, 9, "ntru.keygenBatchAsync");
-}
-
 static napi_value Init(napi_env env, napi_value exports) {
-  napi_property_descriptor props[] = {
-    {"deviceCount", NULL, DeviceCount, NULL, NULL, NULL, napi_default, NULL},
-    {"create", NULL, Create, NULL, NULL, NULL, napi_default, NULL},
-    {"destroy", NULL, Destroy, NULL, NULL, NULL, napi_default, NULL},
-    {"useDevices", NULL, UseDevices, NULL, NULL, NULL, napi_default, NULL},
-    {"supports", NULL, Supports, NULL, NULL, NULL, napi_default, NULL},
-    {"setSamplerRounds", NULL, SetSamplerRounds, NULL, NULL, NULL, napi_default, NULL},
-    {"polymulSplit", NULL, PolymulSplit, NULL, NULL, NULL, napi_default, NULL},
-    {"splitByI", NULL, SplitByI, NULL, NULL, NULL, napi_default, NULL},
-    {"addBatch", NULL, AddBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"sumGroups", NULL, SumGroups, NULL, NULL, NULL, napi_default, NULL},
-    {"tallyDecryptBatch", NULL, TallyDecryptBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"tallyDecryptBatchAsync", NULL, TallyDecryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
-    {"sumGroupsDev", NULL, SumGroupsDev, NULL, NULL, NULL, napi_default, NULL},
-    {"tallyDecryptBatchDev", NULL, TallyDecryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"encryptBatch", NULL, EncryptBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"decryptBatch", NULL, DecryptBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"encryptPeritemBatch", NULL, EncryptPeritemBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"decryptPeritemBatch", NULL, DecryptPeritemBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"verifyKeysBatch", NULL, VerifyKeysBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"checkEncryptBatch", NULL, CheckEncryptBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"checkDecryptBatch", NULL, CheckDecryptBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"checkInverseBatch", NULL, CheckInverseBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"publicKeyBatch", NULL, PublicKeyBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"invertKeyBatch", NULL, InvertKeyBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"sampleTernary", NULL, SampleTernary, NULL, NULL, NULL, napi_default, NULL},
-    {"packParams", NULL, PackParams, NULL, NULL, NULL, napi_default, NULL},
-    {"packBatch", NULL, PackBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"unpackBatch", NULL, UnpackBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"allocPinned", NULL, AllocPinned, NULL, NULL, NULL, napi_default, NULL},
-    {"genericCapacity", NULL, GenericCapacity, NULL, NULL, NULL, napi_default, NULL},
-    {"genericOp", NULL, GenericOp, NULL, NULL, NULL, napi_default, NULL},
-    {"pipelineBatch", NULL, PipelineBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"pipelineBatchAsync", NULL, PipelineBatchAsync, NULL, NULL, NULL, napi_default, NULL},
-    {"devAlloc", NULL, DevAlloc, NULL, NULL, NULL, napi_default, NULL},
-    {"devFree", NULL, DevFree, NULL, NULL, NULL, napi_default, NULL},
-    {"devUpload", NULL, DevUpload, NULL, NULL, NULL, napi_default, NULL},
-    {"devDownload", NULL, DevDownload, NULL, NULL, NULL, napi_default, NULL},
-    {"sampleTernaryDev", NULL, SampleTernaryDev, NULL, NULL, NULL, napi_default, NULL},
-    {"encryptBatchDev", NULL, EncryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"decryptBatchDev", NULL, DecryptBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"encryptPeritemBatchDev", NULL, EncryptPeritemBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"decryptPeritemBatchDev", NULL, DecryptPeritemBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"packBatchDev", NULL, PackBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"encryptBatchAsync", NULL, EncryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
-    {"decryptBatchAsync", NULL, DecryptBatchAsync, NULL, NULL, NULL, napi_default, NULL},
-    {"verifyKeysBatchDev", NULL, VerifyKeysBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"invertKeyBatchDev", NULL, InvertKeyBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"publicKeyBatchDev", NULL, PublicKeyBatchDev, NULL, NULL, NULL, napi_default, NULL},
-    {"polymulSplitDev", NULL, PolymulSplitDev, NULL, NULL, NULL, napi_default, NULL},
-    {"keygenWorkspaceBytes", NULL, KeygenWorkspaceBytes, NULL, NULL, NULL, napi_default, NULL},
-    {"keygenBatch", NULL, KeygenBatch, NULL, NULL, NULL, napi_default, NULL},
-    {"keygenBatchAsync", NULL, KeygenBatchAsync, NULL, NULL, NULL, napi_default, NULL},
-    {"keygenBatchDev", NULL, KeygenBatchDev, NULL, NULL, NULL, napi_default, NULL},
+  static const struct { const char *name; napi_callback fn; } by_hand[] = {
+    {"deviceCount", DeviceCount}, {"create", Create}, {"destroy", Destroy}, {"useDevices", UseDevices}, {"supports", Supports},
+    {"setSamplerRounds", SetSamplerRounds}, {"packParams", PackParams}, {"packBatch", PackBatch}, {"unpackBatch", UnpackBatch},
+    {"packBatchDev", PackBatchDev}, {"allocPinned", AllocPinned}, {"genericCapacity", GenericCapacity}, {"genericOp", GenericOp},
+    {"devAlloc", DevAlloc}, {"devFree", DevFree}, {"devUpload", DevUpload}, {"devDownload", DevDownload},
+    {"keygenWorkspaceBytes", KeygenWorkspaceBytes},
   };
-  if (napi_define_properties(env, exports, sizeof props / sizeof props[0], props) != napi_ok) return NULL;
+  static const struct { int form; const char *suffix; napi_callback fn; } forms[] = {{HOST, "", CallHost}, {DEV, "Dev", CallDev}, {ASYNC, "Async", CallAsync}};
+  enum { N_HAND = sizeof by_hand / sizeof by_hand[0], N_OPS = sizeof ops / sizeof ops[0] };
+  napi_property_descriptor props[N_HAND + 3 * N_OPS];
+  char names[3 * N_OPS][48];
+  size_t n = 0, m = 0;
+  for (size_t i = 0; i < N_HAND; i++)
+    props[n++] = (napi_property_descriptor){by_hand[i].name, NULL, by_hand[i].fn, NULL, NULL, NULL, napi_default, NULL};
+  for (size_t i = 0; i < N_OPS; i++)
+    for (size_t k = 0; k < 3; k++) {
+      if (!(ops[i].forms & forms[k].form)) continue;
+      snprintf(names[m], sizeof names[m], "%s%s", ops[i].name, forms[k].suffix);
+      props[n++] = (napi_property_descriptor){names[m++], NULL, forms[k].fn, NULL, NULL, NULL, napi_default, (void *)&ops[i]};
+    }
+  if (napi_define_properties(env, exports, n, props) != napi_ok) return NULL;
   return exports;
 }
 
