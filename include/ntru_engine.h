@@ -215,7 +215,50 @@ int ntru_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t
                            const uint16_t *d_e, int64_t B, uint8_t *d_value, uint16_t *d_quot1,
                            uint16_t *d_rem1, uint8_t *d_quot2);
 
-/* ---- the same two operations with a SEPARATE key pair for every item (one ciphertext per recipient, one decryption per key
+/* ---- byte messages as packed bits: encryptStr / decryptStr (index.js:80-86) and the stringToBits / bitsToString under them
+ *      (index.js:538-556) on the device, for messages of any length and with one BIT per plaintext bit across the bus.
+ *      A message block is nbytes whole bytes, 1 <= nbytes <= N / 8 (integer division), 8 <= N <= NTRU_MAX_N; the caller cuts a longer
+ *      message into blocks (the reference cannot: "Max N bits since there's no provision to split into words", index.js:81).
+ *      Bit order is stringToBits' (index.js:542): coefficient 8 i + j of row b is (bytes[b][i] >> (7 - j)) & 1, most significant bit
+ *      first; the coefficients 8 nbytes .. N - 1 are the pad.  Byte arrays are dense [B][nbytes], coefficient rows dense [B][N]
+ *      uint8_t, flags [B]; pointers may have any alignment.  Anything outside the domain is NTRU_ERR_ARG before any launch; B == 0
+ *      launches nothing.
+ *   ntru_bytes_to_rows     stringToBits (index.js:538-546) of every block, the pad written as 0: every byte of m is defined.
+ *   ntru_rows_to_bytes     bitsToString (index.js:548-556) of every row for value in {0, 1}: bit = value & 1.  flags[b] (flags may be
+ *                          NULL) is 0 or the OR of the two bits below -- what the reference can only show as a garbled string
+ *                          (test/reference.test.js:15-25, :46-61): a wrong key, a decryption failure, a sum of plaintexts.
+ *   ntru_encrypt_bytes_batch   = ntru_encrypt_batch (index.js:87-110) on the rows of ntru_bytes_to_rows: encryptStr (index.js:80-83) per
+ *                          block with r given; bit-identical e and quotE (quotE may be NULL).
+ *   ntru_decrypt_bytes_batch   = value-only ntru_decrypt_batch (index.js:111-140), then ntru_rows_to_bytes: decryptStr (index.js:84-86)
+ *                          per block, without its trimming (the caller's length frames the message).
+ *   The _dev forms do not synchronise and allocate nothing per call: the intermediate rows (m, value) live in the engine-owned scratch
+ *   buffer, in passes of at most 65536 rows, so its size is bounded in B.  The host forms run the chunked pipeline.
+ *   Kernels: k_bytes_to_rows, k_rows_to_bytes (message_bytes.hip); the scheme kernels are the ones ntru_encrypt_batch_dev /
+ *   ntru_decrypt_batch_dev pick. */
+#define NTRU_FLAG_NOT_BITS 32    /* some coefficient k < 8 nbytes of the row is above 1 */
+#define NTRU_FLAG_PAD_NONZERO 64 /* some coefficient 8 nbytes <= k < N of the row is not 0 */
+int ntru_bytes_to_rows(ntru_engine_t *eng, int N, int nbytes, const uint8_t *bytes, int64_t B, uint8_t *m);
+int ntru_bytes_to_rows_dev(ntru_engine_t *eng, int N, int nbytes, const uint8_t *d_bytes, int64_t B, uint8_t *d_m);
+int ntru_rows_to_bytes(ntru_engine_t *eng, int N, int nbytes, const uint8_t *value, int64_t B, uint8_t *bytes, uint8_t *flags);
+int ntru_rows_to_bytes_dev(ntru_engine_t *eng, int N, int nbytes, const uint8_t *d_value, int64_t B, uint8_t *d_bytes,
+                           uint8_t *d_flags);
+int ntru_encrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int nbytes, const uint16_t *h, const uint8_t *r, const uint8_t *bytes,
+                             int64_t B, uint16_t *e, uint16_t *quotE);
+int ntru_encrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int nbytes, const uint16_t *d_h, const uint8_t *d_r,
+                                 const uint8_t *d_bytes, int64_t B, uint16_t *d_e, uint16_t *d_quotE);
+int ntru_decrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp,
+                             const uint16_t *e, int64_t B, uint8_t *bytes, uint8_t *flags);
+int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *d_f, const uint8_t *d_fp,
+                                 const uint16_t *d_e, int64_t B, uint8_t *d_bytes, uint8_t *d_flags);
+/* ntru_pipeline_batch (above) with the plaintext as bytes at both ends: msg [B][nbytes] in place of m; msg_out [B][nbytes] and flags [B]
+ * (what ntru_decrypt_bytes_batch returns for the fresh ciphertexts) in place of value -- both need the decrypt stage (f, fp).  m and
+ * value are device-only rows of a chunk and never cross the bus.  Either a sampler key or r is given; r_out and e are optional; at
+ * least one output.  Argument checks as ntru_pipeline_batch. */
+int ntru_pipeline_bytes_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const int8_t *f, const uint8_t *fp,
+                              const uint32_t *key, uint64_t first_item, int n1, int n2, const uint8_t *r, int nbytes,
+                              const uint8_t *msg, int64_t B, uint8_t *r_out, uint16_t *e, uint8_t *msg_out, uint8_t *flags);
+
+/* ---- encryptBits and decryptBits with a SEPARATE key pair for every item (one ciphertext per recipient, one decryption per key
  *      holder): h, f and fp are [B][N] batch arrays with the types and layout of ntru_keygen_batch's outputs, so its device arrays
  *      feed straight in.  Row b of every result is exactly what ntru_encrypt_batch / ntru_decrypt_batch return for item b's input
  *      under item b's key: every witness array, the centred lift, the symbol preconditions, any byte of m added mod q.  The witness

@@ -11,6 +11,8 @@
 //   witness_check.hip        witness checks against the Verify* circuits (kernels, *_dev and host-pointer entry points)
 //   keygen_batch.hip         batched key generation with on-device redraws (kernels, *_dev and host-pointer entry points)
 //   ciphertext_sum.hip       segmented, weighted sums of ciphertext rows + tally decrypt (kernels, *_dev and host-pointer entry points)
+//   message_bytes.hip        byte messages as packed bits: bytes <-> coefficient rows, encrypt / decrypt / pipeline on bytes (kernels, *_dev
+//                            and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

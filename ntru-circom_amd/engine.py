@@ -10,6 +10,8 @@ _LIB = None
 ERR_NAMES = {1: "NTRU_ERR_NO_DEVICE", 2: "NTRU_ERR_ARG", 3: "NTRU_ERR_UNSUPPORTED", 4: "NTRU_ERR_HIP"}
 FLAG_INVALID_FQ, FLAG_INVALID_FP, FLAG_INVALID_H = 1, 2, 4
 FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP = 8, 16
+# bits of the per-block flags of rows_to_bytes / decrypt_bytes_batch (include/ntru_engine.h)
+FLAG_NOT_BITS, FLAG_PAD_NONZERO = 32, 64
 # bits of the witness-check flags (include/ntru_engine.h NTRU_CHECK_*); VerifyDecrypt's second stage is shifted left by 3
 CHECK_EQ, CHECK_TAIL, CHECK_RANGE = 1, 2, 4
 # status codes of the generic family = the errors the reference throws (include/ntru_engine.h NTRU_GENERIC_*)
@@ -92,6 +94,12 @@ for _sfx in ("", "_dev"):
 for _sfx in ("", "_dev"):
     _SIGS["ntru_sum_groups" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp])
     _SIGS["ntru_tally_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _i64] + [_vp] * 5)
+for _sfx in ("", "_dev"):
+    _SIGS["ntru_bytes_to_rows" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp])
+    _SIGS["ntru_rows_to_bytes" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp, _vp])
+    _SIGS["ntru_encrypt_bytes_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
+    _SIGS["ntru_decrypt_bytes_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
+_SIGS["ntru_pipeline_bytes_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp])
 _SIGS["ntru_keygen_workspace_bytes"] = (C.c_int, [_i, _i64, C.POINTER(C.c_size_t)])
 _SIGS["ntru_keygen_batch_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
 _SIGS["ntru_keygen_batch"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
@@ -368,6 +376,75 @@ class Engine:
         self._chk(self._lib.ntru_decrypt_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(value),
                                                _ptr(q1), _ptr(r1), _ptr(q2)))
         return value, q1, r1, q2
+
+    # ---- byte messages as packed bits (include/ntru_engine.h "byte messages"): blocks of nbytes <= N // 8 bytes, bit 7 first
+    @staticmethod
+    def _blocks(a, nbytes):
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(bytes(a), np.uint8)
+        return _np(a, np.uint8).reshape(-1, nbytes)
+
+    def bytes_to_rows(self, N, nbytes, data):
+        """[B][nbytes] message bytes -> [B][N] coefficient rows (stringToBits per block, zero pad)."""
+        data = self._blocks(data, nbytes)
+        B = data.shape[0]
+        m = np.empty((B, N), np.uint8)
+        self._chk(self._lib.ntru_bytes_to_rows(self._h, N, nbytes, _ptr(data), B, _ptr(m)))
+        return m
+
+    def rows_to_bytes(self, N, nbytes, value, want_flags=True):
+        """[B][N] rows -> ([B][nbytes] bytes of the low bits, [B] flags: FLAG_NOT_BITS | FLAG_PAD_NONZERO, or None)."""
+        value = _np(value, np.uint8).reshape(-1, N)
+        B = value.shape[0]
+        out = np.empty((B, nbytes), np.uint8)
+        flags = np.empty(B, np.uint8) if want_flags else None
+        self._chk(self._lib.ntru_rows_to_bytes(self._h, N, nbytes, _ptr(value), B, _ptr(out), _ptr(flags)))
+        return out, flags
+
+    def encrypt_bytes_batch(self, N, q, nbytes, h, r, data, want_quot=True):
+        """encrypt_batch on the rows of bytes_to_rows(data); only nbytes per block go up."""
+        h = _np(h, np.uint16, (N,))
+        r, data = _np(r, np.uint8).reshape(-1, N), self._blocks(data, nbytes)
+        B = r.shape[0]
+        if data.shape[0] != B:
+            raise ValueError("encrypt_bytes_batch: %d rows of r for %d blocks" % (B, data.shape[0]))
+        e = np.empty((B, N), np.uint16)
+        quot = np.empty((B, N), np.uint16) if want_quot else None
+        self._chk(self._lib.ntru_encrypt_bytes_batch(self._h, N, q, nbytes, _ptr(h), _ptr(r), _ptr(data), B, _ptr(e), _ptr(quot)))
+        return e, quot
+
+    def decrypt_bytes_batch(self, N, q, p, nbytes, f, fp, e, want_flags=True):
+        """rows_to_bytes of the value-only decrypt_batch; only nbytes (+ 1 flag byte) per block come down.  Returns (bytes, flags)."""
+        f, fp = _np(f, np.int8, (N,)), _np(fp, np.uint8, (N,))
+        e = _np(e, np.uint16).reshape(-1, N)
+        B = e.shape[0]
+        out = np.empty((B, nbytes), np.uint8)
+        flags = np.empty(B, np.uint8) if want_flags else None
+        self._chk(self._lib.ntru_decrypt_bytes_batch(self._h, N, q, p, nbytes, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(out), _ptr(flags)))
+        return out, flags
+
+    def pipeline_bytes_batch(self, N, q, p, nbytes, h, msg, f=None, fp=None, key=None, first_item=0, n1=0, n2=0, r=None,
+                             want_r=False, want_e=False, want_msg=False, want_flags=False, out=None):
+        """ntru_pipeline_bytes_batch: pipeline_batch with msg [B][nbytes] in place of m and msg_out / flags in place of value.
+        `out` may hold preallocated arrays (e.g. pinned_empty) under "r", "e", "msg", "flags".  Returns a dict of the outputs."""
+        h = _np(h, np.uint16, (N,))
+        msg = self._blocks(msg, nbytes)
+        B = msg.shape[0]
+        f = None if f is None else _np(f, np.int8, (N,))
+        fp = None if fp is None else _np(fp, np.uint8, (N,))
+        key = None if key is None else _np(key, np.uint32, (8,))
+        r = None if r is None else _np(r, np.uint8).reshape(-1, N)
+        out = dict(out or {})
+        for name, want, shape, dt in (("r", want_r, (B, N), np.uint8), ("e", want_e, (B, N), np.uint16),
+                                      ("msg", want_msg, (B, nbytes), np.uint8), ("flags", want_flags, (B,), np.uint8)):
+            if want and name not in out:
+                out[name] = np.empty(shape, dt)
+            if name in out and (out[name].shape != shape or out[name].dtype != dt or not out[name].flags.c_contiguous):
+                raise ValueError("pipeline_bytes_batch: out[%r] must be a contiguous %s array of shape %r" % (name, np.dtype(dt).name, shape))
+        self._chk(self._lib.ntru_pipeline_bytes_batch(self._h, N, q, p, _ptr(h), _ptr(f), _ptr(fp), _ptr(key), int(first_item), int(n1),
+                                                      int(n2), _ptr(r), nbytes, _ptr(msg), B, _ptr(out.get("r")), _ptr(out.get("e")),
+                                                      _ptr(out.get("msg")), _ptr(out.get("flags"))))
+        return out
 
     def encrypt_peritem_batch(self, N, q, h, r, m, want_quot=True):
         """encrypt_batch with a separate public key per item: h, r, m are [B][N]; row b of e / quotE is encrypt_batch of row b
@@ -647,6 +724,24 @@ class Engine:
             self._chk(self._lib.ntru_decrypt_batch_pitched_dev(self._h, N, q, p, int(ld), dp(d_f), dp(d_fp), dp(d_e), B,
                                                                dp(d_value), dp(d_quot1), dp(d_rem1), dp(d_quot2)))
         self._note(N, B, (3 + (2 if d_quot1 else 0) + (2 if d_rem1 else 0) + (1 if d_quot2 else 0)) * N)
+
+    def bytes_to_rows_dev(self, N, nbytes, d_bytes, B, d_m):
+        dp = self._dp
+        self._chk(self._lib.ntru_bytes_to_rows_dev(self._h, N, nbytes, dp(d_bytes), B, dp(d_m)))
+        self._note(N, B, N + nbytes)
+
+    def rows_to_bytes_dev(self, N, nbytes, d_value, B, d_bytes, d_flags=None):
+        dp = self._dp
+        self._chk(self._lib.ntru_rows_to_bytes_dev(self._h, N, nbytes, dp(d_value), B, dp(d_bytes), dp(d_flags)))
+        self._note(N, B, N + nbytes + (1 if d_flags else 0))
+
+    def encrypt_bytes_batch_dev(self, N, q, nbytes, d_h, d_r, d_bytes, B, d_e, d_quotE=None):
+        dp = self._dp
+        self._chk(self._lib.ntru_encrypt_bytes_batch_dev(self._h, N, q, nbytes, dp(d_h), dp(d_r), dp(d_bytes), B, dp(d_e), dp(d_quotE)))
+
+    def decrypt_bytes_batch_dev(self, N, q, p, nbytes, d_f, d_fp, d_e, B, d_bytes, d_flags=None):
+        dp = self._dp
+        self._chk(self._lib.ntru_decrypt_bytes_batch_dev(self._h, N, q, p, nbytes, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_bytes), dp(d_flags)))
 
     def encrypt_peritem_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_quotE=None):
         """d_h: [B][N] public keys, one per item."""

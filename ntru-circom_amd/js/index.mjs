@@ -678,6 +678,82 @@ export default class NTRU {
       Uint8Array.from(expandArray(this.fp, N, 0)), e, B, value, q1, r1, q2)
       .then(() => ({ value, quotient1: q1, remainder1: r1, quotient2: q2 }));
   }
+
+  // ---- byte messages of any length (additive; the reference's encryptStr takes at most N bits, index.js:81).  Same framing and results
+  // as the Python NTRU.encryptBytes / decryptBytes: blocks of W = bytesPerBlock bytes, the last one zero padded, bit 7 of a byte first
+  // (index.js:542), every block encrypted as encryptStr encrypts it.  Here the bits are expanded and collected in JavaScript around
+  // encryptBatch / decryptBatch; the engine's ntru_encrypt_bytes_batch / ntru_decrypt_bytes_batch have no native Node path yet.
+  get bytesPerBlock() { return Math.floor(this.N / 8); }
+
+  // data: Uint8Array / Buffer, or a latin-1 string -> { m: Uint8Array[blocks*N], blocks }
+  _bytesToRows(data) {
+    const { N } = this, W = this.bytesPerBlock;
+    if (W < 1) throw new Error(`encryptBytes: N = ${N} holds no whole byte`);
+    if (typeof data === 'string') {
+      const s = data;
+      data = new Uint8Array(s.length);
+      for (let i = 0; i < s.length; i++) {
+        const c = s.charCodeAt(i);
+        if (c > 255) throw new Error('encryptBytes: a string must be latin-1 (char codes below 256); encode it to bytes first');
+        data[i] = c;
+      }
+    }
+    const blocks = Math.ceil(data.length / W), m = new Uint8Array(blocks * N);
+    for (let i = 0; i < data.length; i++) {
+      const at = Math.floor(i / W) * N + 8 * (i % W), x = data[i];
+      for (let j = 0; j < 8; j++) m[at + j] = (x >> (7 - j)) & 1;
+    }
+    return { m, blocks };
+  }
+
+  // r: Uint8Array[blocks*N] in {0, 1, p-1} or an array of signed ternary rows; drawn per block like encryptBits' when null
+  _bytesR(r, blocks) {
+    const { N, p } = this;
+    if (r === null || r === undefined) r = Array.from({ length: blocks }, () => generateCustomArray(N, this.dr, this.dr));
+    const flat = ArrayBuffer.isView(r) ? r : r.flat();
+    if (flat.length !== blocks * N) throw new Error(`encryptBytes: ${flat.length / N} rows of r for ${blocks} blocks`);
+    return Uint8Array.from(flat, x => (x === -1 ? p - 1 : x));                 // index.js:89
+  }
+
+  _rowsToBytes(value, blocks, length) {
+    const { N } = this, W = this.bytesPerBlock, msg = 8 * W;
+    const all = new Uint8Array(blocks * W), flags = new Uint8Array(blocks);
+    for (let b = 0; b < blocks; b++) {
+      let f = 0;
+      for (let k = 0; k < N; k++) {
+        const v = value[b * N + k];
+        if (k < msg) { if (v > 1) f |= 32; all[b * W + (k >> 3)] |= (v & 1) << (7 - (k & 7)); } else if (v !== 0) f |= 64;
+      }
+      flags[b] = f;                                                           // NTRU_FLAG_NOT_BITS 32, NTRU_FLAG_PAD_NONZERO 64
+    }
+    let n = all.length;
+    if (length === null || length === undefined) while (n > 0 && all[n - 1] === 0) n--;   // decryptStr's trimPolynomial
+    else if (!(length >= 0 && length <= n)) throw new Error(`decryptBytes: length ${length} is outside the ${n} bytes of ${blocks} blocks`);
+    else n = length;
+    return { data: all.slice(0, n), flags };
+  }
+
+  // -> Uint16Array[blocks*N], the ciphertext of every block
+  encryptBytes(data, r = null) {
+    const { m, blocks } = this._bytesToRows(data);
+    if (blocks === 0) return new Uint16Array(0);
+    return this.encryptBatch(this._bytesR(r, blocks), m, blocks, false).e;
+  }
+  encryptBytesAsync(data, r = null) {
+    const { m, blocks } = this._bytesToRows(data);
+    if (blocks === 0) return Promise.resolve(new Uint16Array(0));
+    return this.encryptBatchAsync(this._bytesR(r, blocks), m, blocks, false).then(o => o.e);
+  }
+
+  // e: Uint16Array[blocks*N] -> { data: Uint8Array (cut to `length`, or trailing zero bytes stripped), flags: Uint8Array[blocks] }
+  decryptBytes(e, blocks, length = null) {
+    if (blocks === 0) return this._rowsToBytes(new Uint8Array(0), 0, length);
+    return this._rowsToBytes(this.decryptBatch(e, blocks, false).value, blocks, length);
+  }
+  decryptBytesAsync(e, blocks, length = null) {
+    if (blocks === 0) return Promise.resolve(this._rowsToBytes(new Uint8Array(0), 0, length));
+    return this.decryptBatchAsync(e, blocks, false).then(o => this._rowsToBytes(o.value, blocks, length));
+  }
 }
 
 // ---- witness checks: does a witness satisfy VerifyEncrypt / VerifyDecrypt / VerifyInverse (circuits/ntru.circom)? ----------------

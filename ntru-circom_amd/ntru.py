@@ -512,6 +512,53 @@ class NTRU:
                                           key=key, first_item=first, n1=self.dr, n2=self.dr, r=r, want_r="r" in want and key is not None,
                                           want_e="e" in want, want_value="value" in want, want_packed=pack)
 
+    # -- byte messages of any length, as packed bits (the reference's encryptStr takes at most N bits, index.js:81) ------------------
+    @property
+    def bytesPerBlock(self):
+        return self.N // 8
+
+    def encryptBytes(self, data, r=None):
+        """`data` (bytes, or a latin-1 str: stringToBits, index.js:538-546, misaligns for char codes above 255 and that artefact is not
+        reproduced) is cut into ceil(len / W) blocks of W = bytesPerBlock bytes, the last one zero padded, and every block encrypted as
+        encryptStr encrypts it (index.js:80-83); the bits are expanded on the device.  r: [blocks][N], signed ternary or mapped to
+        {0, 1, p-1}; drawn per block like encryptBits' by default.  Returns the [blocks][N] uint16 ciphertext array."""
+        if isinstance(data, str):
+            try:
+                data = data.encode("latin-1")
+            except UnicodeEncodeError:
+                raise ValueError("encryptBytes: a str must be latin-1 (char codes below 256); encode it to bytes first") from None
+        data = bytes(data)
+        N, p, W = self.N, self.p, self.bytesPerBlock
+        if W < 1:
+            raise ValueError("encryptBytes: N = %d holds no whole byte" % N)
+        blocks = -(-len(data) // W)
+        if r is None:
+            r = [generateCustomArray(N, self.dr, self.dr) for _ in range(blocks)]
+        r = np.asarray(r, dtype=np.int64).reshape(-1, N)
+        if r.shape[0] != blocks:
+            raise ValueError("encryptBytes: %d rows of r for %d blocks" % (r.shape[0], blocks))
+        r = np.where(r == -1, p - 1, r).astype(np.uint8)                            # index.js:89
+        padded = np.frombuffer(data + bytes(blocks * W - len(data)), np.uint8).reshape(blocks, W)
+        e, _ = self.engine.encrypt_bytes_batch(N, self.q, W, expandArray(self.h, N), r, padded, want_quot=False)
+        return e
+
+    def decryptBytes(self, e, length=None):
+        """decryptStr (index.js:84-86) of every block of e [blocks][N], the bits collected on the device.  Returns (data, flags): data is
+        cut to `length` bytes when given, else its trailing zero bytes are stripped (what decryptStr does through trimPolynomial);
+        flags [blocks] is 0 for a block that decrypted to bits with an empty pad, else FLAG_NOT_BITS | FLAG_PAD_NONZERO of the engine:
+        a wrong key or a decryption failure, which the reference can only show as a garbled string."""
+        N, W = self.N, self.bytesPerBlock
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")                  # what index.js:112 does
+        e = np.asarray(e, dtype=np.uint16).reshape(-1, N)
+        out, flags = self.engine.decrypt_bytes_batch(N, self.q, self.p, W, expandArray(self.f, N), expandArray(self.fp, N), e)
+        data = out.tobytes()
+        if length is None:
+            return data.rstrip(b"\x00"), flags
+        if not 0 <= length <= len(data):
+            raise ValueError("decryptBytes: length %d is outside the %d bytes of %d blocks" % (length, len(data), e.shape[0]))
+        return data[:length], flags
+
     def encryptStr(self, inputPlain):
         return self.encryptBits(stringToBits(inputPlain))["value"]
 
