@@ -6,10 +6,19 @@ tests/test_kernel_variants_gpu.py (each row's calls against the oracle, and the 
 A row:
   kernel  the demangled instantiation as `c++filt` prints it, return type and argument list dropped ("k_decrypt_s<11, 11, true>")
   entry   the C-ABI entry point whose launcher selects it (the name without the ntru_ prefix and the _batch[_dev] suffix)
-  shapes  calls that select it: dicts of N, q, p, path (ntru_engine_set_kernel_path) and B.  The first has the smallest N that
+  shapes  calls that select it: dicts of N, q, p, path (ntru_engine_set_kernel_path), B and extra.  The first has the smallest N that
           selects the kernel; a second, larger N follows where the selection rule spans a wide range.  For the entry points
-          without a scheme modulus, q is the modulus (add, split_by_I, polymul_split), the largest value (pack, pack_bytes, unpack)
-          or 2^20 (generic_multiply); p is the sampler's rounds (sample_ternary) and 0 elsewhere.
+          without a scheme modulus, q is the modulus (add, split_by_I, polymul_split, sum_groups: `mod`), the largest value (pack,
+          pack_bytes, unpack), 2^20 (generic_multiply) or 0 (bytes_to_rows, rows_to_bytes); p is the sampler's rounds
+          (sample_ternary) and 0 elsewhere.  `extra` holds what else the call takes (empty for most entries):
+            sum_groups                    B = the number of rows; K = rows per uniform group, or csr = True for the offsets form
+                                          (empty groups first, last and in the middle); weights = True / False where the row fixes it
+            bytes_to_rows, rows_to_bytes  nbytes = message bytes per row (1 <= nbytes <= N / 8)
+            check_*                       q, p are the circuit's moduli, the bit counts are calculateNq / calculateNp of them (at N = 2
+                                          they accept an honest VerifyDecrypt witness only for q <= 47: q = 32); B = the accepted
+                                          witnesses of a call (the mutated ones come on top)
+            keygen                        df, dg of a parameter set whose first draws hold non-units, and first = a first_item at which
+                                          the B items from first, first - 1 and first - 2 on hold one (item 316 at N = 17)
   last    what ntru_engine_last_kernel() returns after the call
   rule    where the launcher writes a coarse name or none: the selection rule the shapes satisfy (nw = (N + 32) / 32 etc.)
   unreachable  set instead of shapes when no call the ABI accepts selects the instantiation, with the reason
@@ -20,7 +29,7 @@ ROWS = []
 
 def _row(kernel, entry, shapes, last=None, rule=None, unreachable=None):
     ROWS.append({"kernel": kernel, "entry": entry,
-                 "shapes": [dict(N=N, q=q, p=p, path=path, B=B) for (N, q, p, path, B) in shapes],
+                 "shapes": [dict(N=t[0], q=t[1], p=t[2], path=t[3], B=t[4], extra=dict(t[5]) if len(t) > 5 else {}) for t in shapes],
                  "last": last, "rule": rule, "unreachable": unreachable})
 
 
@@ -160,7 +169,52 @@ _row("k_add_mod", "add", [(1, 2, 0, 0, 1), (821, 2048, 0, 0, 9)], None, "B N not
 _row("k_split_by_I", "split_by_I", [(1, 2, 0, 0, 1), (821, 4096, 0, 0, 9)], None, "every ntru_split_by_I_dev call")
 _row("(anonymous namespace)::k_generic", "generic_multiply", [(1, 1 << 20, 0, 0, 1), (300, 1 << 20, 0, 0, 5)], "k_generic")
 
+# ---- one key pair per item (matrix_peritem_scheme.hip) ----------------------------------------------------------------------------
+_row("k_encrypt_pi_m<true>", "encrypt_peritem", [(64, 256, 0, 4, 7), (128, 32, 0, 0, 7)], "k_encrypt_pi_m", "q <= 256")
+_row("k_encrypt_pi_m<false>", "encrypt_peritem", [(128, 512, 0, 0, 7), (1024, 8192, 0, 0, 7)], "k_encrypt_pi_m", "512 <= q <= 8192")
+_row("k_decrypt_pi_m<true>", "decrypt_peritem", [(64, 256, 3, 4, 7), (128, 32, 3, 0, 7)], "k_decrypt_pi_m", "q <= 256, p == 3")
+_row("k_decrypt_pi_m<false>", "decrypt_peritem", [(128, 512, 3, 0, 7), (1024, 8192, 3, 0, 7)], "k_decrypt_pi_m",
+     "512 <= q <= 8192, p == 3")
+# the composed path: N below the matrix range, q above it, a kernel path without the matrix kernels, p != 3 (decrypt)
+_COMPOSED = [(2, 2048, 3, 0, 7), (127, 2048, 3, 0, 7), (128, 16384, 3, 0, 7), (128, 2048, 3, 1, 7)]
+for _k in ("k_pi_widen", "k_pi_add_bytes"):
+    _row(_k, "encrypt_peritem", [(N, q, 0, path, B) for (N, q, _p, path, B) in _COMPOSED], "peritem_composed(k_polymul_split<1>)",
+         "composed encrypt")
+for _k in ("k_pi_signed_modq", "k_pi_lift", "k_pi_narrow"):
+    _row(_k, "decrypt_peritem", _COMPOSED + [(128, 2048, 5, 0, 7)], "peritem_composed(k_polymul_split<1>)", "composed decrypt")
+
+# ---- segmented sums (ciphertext_sum.hip) ----------------------------------------------------------------------------------------
+_NS = "(anonymous namespace)::"
+for _P2, _mod in ((True, 2048), (False, 65521)):
+    for _WT in (False, True):
+        _row(_NS + "k_sum_groups<%s, %s>" % (str(_P2).lower(), str(_WT).lower()), "sum_groups",
+             [(2, _mod, 0, 0, 6, dict(K=3, weights=_WT)), (513, _mod, 0, 0, 80, dict(K=40, weights=_WT))],
+             "k_sum_groups<%d,%d>" % (_P2, _WT), "power-of-two mod: %s, weights: %s; N = 513 is two column tiles" % (_P2, _WT))
+    # uniform: the block count is clamped to the row count, so one group of 3 rows crosses two boundaries and one of 40 walks the
+    # 32-slice loop twice; offsets form: 4100 rows at N = 17 give blocks of more than one row
+    _row(_NS + "k_sum_groups_finish<%s>" % str(_P2).lower(), "sum_groups",
+         [(2, _mod, 0, 0, 3, dict(K=3)), (513, _mod, 0, 0, 40, dict(K=40)), (17, _mod, 0, 0, 4100, dict(csr=True))], None,
+         "a group crossing a row-block boundary, power-of-two mod: %s" % _P2)
+
+# ---- byte messages (message_bytes.hip) ------------------------------------------------------------------------------------------------
+_BYTES = [(8, 0, 0, 0, 5, dict(nbytes=1)), (821, 0, 0, 0, 5, dict(nbytes=102)), (1920, 0, 0, 0, 5, dict(nbytes=1))]
+_row(_NS + "k_bytes_to_rows", "bytes_to_rows", _BYTES, "k_bytes_to_rows", "every ntru_bytes_to_rows_dev call")
+_row(_NS + "k_rows_to_bytes", "rows_to_bytes", _BYTES, "k_rows_to_bytes", "every ntru_rows_to_bytes_dev call")
+
+# ---- witness checks (witness_check.hip) -------------------------------------------------------------------------------------------------
+for _t in ("encrypt", "decrypt", "inverse"):
+    _row(_NS + "k_check_" + _t, "check_" + _t, [(2, 32, 3, 0, 3), (821, 4096, 3, 0, 3)], "k_check_" + _t,
+         "every ntru_check_%s_batch_dev call" % _t)
+
+# ---- key generation (keygen_batch.hip): the redraw kernels run only when a first draw is a non-unit -----------------------------------
+_KEYGEN = [(7, 32, 3, 0, 16, dict(df=2, dg=2, first=125)), (17, 32, 3, 0, 8, dict(df=3, dg=2, first=311))]
+for _k in ("k_sample_ternary_listed", "k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
+    _row(_NS + _k, "keygen", _KEYGEN, "k_keygen", "ntru_keygen_batch_dev with a non-unit among the first draws")
+
 BY_KERNEL = {r["kernel"]: r for r in ROWS}
 assert len(BY_KERNEL) == len(ROWS), "duplicate row"
-# every string ntru_engine_last_kernel() may return after a call of the scheme entry points
-LAST_KERNELS = {r["last"] for r in ROWS if r["last"]} | {"k_invert_key", "k_sample_ternary", "k_encrypt_wp"}
+# every string ntru_engine_last_kernel() may return after a call of the scheme entry points: the rows of these entries only (the
+# dispatch sweep and the p sweeps assert membership, so the set must not grow with the table)
+SCHEME_ENTRIES = ("encrypt", "decrypt", "decrypt_pack", "verify_keys", "polymul_split", "public_key", "generic_multiply")
+LAST_KERNELS = {r["last"] for r in ROWS if r["last"] and r["entry"] in SCHEME_ENTRIES} | {"k_invert_key", "k_sample_ternary", "k_encrypt_wp"}
+assert len(LAST_KERNELS) == 84, len(LAST_KERNELS)

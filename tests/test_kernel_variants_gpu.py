@@ -1,11 +1,18 @@
 """Every compiled kernel instantiation (tests/kernel_variants.py) launched through its entry point and compared bit for bit with the
 CPU oracle, on the operand values and batch sizes where kernels go wrong; p != 3 on every kernel that takes p; and a dispatch sweep
-over every N of kernel paths 0-3, so that a launcher cannot ask for an instantiation that does not exist."""
+over every N of kernel paths 0-3, so that a launcher cannot ask for an instantiation that does not exist.  The rows of the per-item
+scheme, the segmented sums, the byte codec, the witness checks and key generation run against the references their own test modules
+use (tests/peritem_ref.py, ciphertext_sum_ref.py, message_bytes_ref.py, witness_circuit.py, keygen_ref.py)."""
 import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import ciphertext_sum_ref as sum_ref
 import kernel_variants as kv
+import keygen_ref
+import message_bytes_ref as bytes_ref
+import peritem_ref
+import witness_circuit as wc
 from oracle import ntru_keygen as kg
 from oracle import ntru_oracle as orc
 
@@ -14,6 +21,7 @@ pkg = ge.load_package()
 
 WAVES_PER_BLOCK = 4
 P3_ONLY = ("k_decrypt_s", "k_decrypt_t", "k_decrypt_m", "k_verify_keys_t", "k_verify_keys_m")
+GUARD = 16                       # bytes on either side of a guarded output that must stay FILL
 FILL = 0xA5                      # output buffers start as this byte: an element the kernel should write and does not shows up
 
 
@@ -38,16 +46,26 @@ class Dev:
         for p in self.ptrs:
             self.eng.dev_free(p)
 
-    def up(self, arr):
+    def up(self, arr, shift=0):
+        """arr on the device, `shift` bytes into its allocation."""
         arr = np.ascontiguousarray(arr)
-        p = self.eng.dev_alloc(max(arr.nbytes, 16))
+        p = self.eng.dev_alloc(max(arr.nbytes, 16) + shift)
         self.ptrs.append(p)
         if arr.nbytes:
-            self.eng.dev_upload(p, arr)
-        return p
+            self.eng.dev_upload(p + shift, arr)
+        return p + shift
 
-    def out(self, shape, dtype):
-        return self.up(np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, FILL, np.uint8))
+    def out(self, shape, dtype, shift=0):
+        return self.up(np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, FILL, np.uint8), shift)
+
+    def guarded(self, nbytes, shift=0):
+        """nbytes of FILL, `shift` bytes off a 16-byte boundary, with GUARD bytes of FILL on either side; the pointer to the payload."""
+        return self.up(np.full(nbytes + 2 * GUARD, FILL, np.uint8), shift) + GUARD
+
+    def get_guarded(self, p, nbytes):
+        """[payload, the guard bytes in front, the guard bytes behind]"""
+        raw = self.eng.dev_download(p - GUARD, (nbytes + 2 * GUARD,), np.uint8)
+        return [raw[GUARD:GUARD + nbytes], raw[:GUARD], raw[GUARD + nbytes:]]
 
     def get(self, p, shape, dtype):
         return self.eng.dev_download(p, shape, dtype)
@@ -67,9 +85,21 @@ def items_per_group(kernel, N):
     return 64 // (-(-N // (2 * K)))
 
 
+PERITEM_B = (1, 2, 3, 5)          # PI_WAVES = 2: a lone wave, a full workgroup, a partial last one, an item the grid-stride loop prefetches
+
+
 def batch_sizes(kernel, shape):
     """B = 1, the row's own B, and the sizes that leave a partial last group / row block."""
     N, B = shape["N"], shape["B"]
+    entry = kv.BY_KERNEL[kernel]["entry"]
+    if entry in ("encrypt_peritem", "decrypt_peritem"):
+        return sorted({B, *PERITEM_B})
+    if entry in ("bytes_to_rows", "rows_to_bytes"):
+        return sorted({1, 3, B})
+    if entry == "sum_groups":
+        return [B]                                   # the group layouts are the runner's
+    if entry.startswith("check_") or entry == "keygen":
+        return sorted({1, B})
     out = {1, B}
     G = items_per_group(kernel, N)
     if G:
@@ -303,8 +333,195 @@ def run_generic_multiply(eng, N, mod, B, rng, variant):
     return [got], [[kg._multiply(a[i], b_[i], mod).tolist() for i in range(B)]]
 
 
+
+# ---- the five newer kernel files ------------------------------------------------------------------------------------------------------
+
+def run_encrypt_peritem(eng, N, q, B, rng, variant):
+    h, r, m = peritem_ref.encrypt_operands(rng, N, q, B, variant)
+    witness = variant != 1
+    with Dev(eng) as d:
+        de, dq = d.out((B, N), np.uint16), (d.out((B, N), np.uint16) if witness else None)
+        eng.encrypt_peritem_batch_dev(N, q, d.up(h), d.up(r), d.up(m), B, de, dq)
+        got = [d.get(de, (B, N), np.uint16)] + ([d.get(dq, (B, N), np.uint16)] if witness else [])
+    e, quot = peritem_ref.oracle_encrypt(N, q, h, r, m)
+    return got, [e] + ([quot] if witness else [])
+
+
+PI_OUT = (np.uint8, np.uint16, np.uint16, np.uint8)           # value, quot1, rem1, quot2
+
+
+def decrypt_peritem_call(eng, N, q, p, f, fp, e, witness=True):
+    B = f.shape[0]
+    with Dev(eng) as d:
+        outs = [d.out((B, N), dt) for dt in PI_OUT]
+        if not witness:
+            outs[1:] = [None] * 3
+        eng.decrypt_peritem_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, *outs)
+        return [d.get(o, (B, N), dt) for o, dt in zip(outs, PI_OUT) if o]
+
+
+def run_decrypt_peritem(eng, N, q, p, B, rng, variant):
+    f, fp, e = peritem_ref.decrypt_operands(rng, N, q, p, B, variant)
+    witness = variant != 1
+    want = peritem_ref.oracle_decrypt(N, q, p, f, fp, e)
+    peritem_ref.assert_lift_edges_met(N, q, f, want[2])
+    return decrypt_peritem_call(eng, N, q, p, f, fp, e, witness), list(want if witness else want[:1])
+
+
+def csr_offsets(B):
+    """Empty groups first, last and in the middle, a single row, one group over most of the rows; rows behind the last offset."""
+    a, b = min(5, B // 2), B - min(2, B // 3)
+    return np.array([0, 0, a, a, a, min(a + 1, b), b, b], np.int64)
+
+
+def run_sum_groups(eng, N, mod, B, rng, variant, extra):
+    """The row's own layout, uniform groups of K = 1, 3, 40 (one group and two), and the offsets form with empty groups; variant:
+    the weights (all mod - 1, zero, random) and, at 2, every row and output pointer 2 bytes off 4-byte alignment."""
+    weighted = extra.get("weights", variant != 1)
+    layouts = [(B, extra.get("K"), csr_offsets(B) if extra.get("csr") else None)]
+    layouts += [(K * G, K, None) for K in (1, 3, 40) for G in (1, 2)] + [(47, None, csr_offsets(47))]
+    shift = 2 if variant == 2 else 0
+    got, want = [], []
+    for nrows, K, off in layouts:
+        rows = peritem_ref.rows_cycle(nrows + variant, [lambda b: np.full(N, mod - 1), lambda b: rng.integers(0, mod, N)])[variant:]
+        rows = rows.astype(np.uint16)
+        w = None
+        if weighted:
+            w = [np.full(nrows, mod - 1), np.zeros(nrows), rng.integers(0, mod, nrows)][variant].astype(np.uint16)
+        G = nrows // K if off is None else len(off) - 1
+        with Dev(eng) as d:
+            do = d.out((G, N), np.uint16, shift)
+            eng.sum_groups_dev(N, mod, d.up(rows, shift), do, G, d_offsets=None if off is None else d.up(off), K=K,
+                               d_weights=None if w is None else d.up(w, shift))
+            got.append(d.get(do, (G, N), np.uint16))
+        assert eng.last_kernel() == "k_sum_groups<%d,%d>" % (mod & (mod - 1) == 0, weighted), eng.last_kernel()
+        want.append(sum_ref.np_sum(rows, mod, offsets=off, K=K, weights=w).astype(np.uint16))
+    return got, want
+
+
+def message_bytes(rng, nbytes, B):
+    return peritem_ref.rows_cycle(B, [lambda b: np.full(nbytes, 0x00), lambda b: np.full(nbytes, 0xFF), lambda b: np.full(nbytes, 0x80),
+                                      lambda b: np.full(nbytes, 0x01), lambda b: rng.integers(0, 256, nbytes)]).astype(np.uint8)
+
+
+BYTE_SHIFTS = (0, 1, 15)          # the output pointer's offset from a 16-byte boundary, by variant
+GUARDS = [np.full(GUARD, FILL, np.uint8)] * 2
+
+
+def run_bytes_to_rows(eng, N, nbytes, B, rng, variant):
+    data = np.roll(message_bytes(rng, nbytes, B + variant), -variant, axis=0)[:B]
+    with Dev(eng) as d:
+        out = d.guarded(B * N, BYTE_SHIFTS[variant])
+        eng.bytes_to_rows_dev(N, nbytes, d.up(data, variant), B, out)
+        got = d.get_guarded(out, B * N)
+    return got, [bytes_ref.np_bytes_to_rows(data, N).reshape(-1)] + GUARDS
+
+
+def run_rows_to_bytes(eng, N, nbytes, B, rng, variant):
+    """Rows of bits; at variant 2 a 2 in the first message coefficient of row 0 and, where the row has a pad, a 1 in the last
+    coefficient of the last row (both flagged); at variant 1 without the flags array."""
+    rows = bytes_ref.np_bytes_to_rows(np.roll(message_bytes(rng, nbytes, B + variant), -variant, axis=0)[:B], N)
+    if variant == 2:
+        rows[0, 0] = 2
+        if 8 * nbytes < N:
+            rows[B - 1, N - 1] = 1
+    want, want_flags = bytes_ref.np_rows_to_bytes(rows, nbytes)
+    if variant == 2:
+        assert want_flags[0] & bytes_ref.FLAG_NOT_BITS and (8 * nbytes == N or want_flags[B - 1] & bytes_ref.FLAG_PAD_NONZERO)
+    with Dev(eng) as d:
+        out = d.guarded(B * nbytes, BYTE_SHIFTS[variant])
+        fl = None if variant == 1 else d.guarded(B, BYTE_SHIFTS[variant])
+        eng.rows_to_bytes_dev(N, nbytes, d.up(rows, variant), B, out, fl)
+        got = d.get_guarded(out, B * nbytes) + (d.get_guarded(fl, B) if fl else [])
+    return got, [want.reshape(-1)] + GUARDS + ([want_flags] + GUARDS if variant != 1 else [])
+
+
+CHECK_TEMPLATE = {"check_encrypt": "VerifyEncrypt", "check_decrypt": "VerifyDecrypt", "check_inverse": "VerifyInverse"}
+
+
+def run_check(eng, entry, N, q, p, B, rng, variant):
+    """B accepted witnesses (operands at their extremes in item 0 of variant 0), then item 0 again with a single coefficient off by
+    one: at index 0 and at the last index of each array in turn.  Flags against the closed-form evaluator."""
+    template = CHECK_TEMPLATE[entry]
+    nq, np_ = wc.calc_nbits(q, N), wc.calc_nbits(p, N)
+    tern = lambda: rng.choice([0, 1, q - 1], (B, N))
+    if entry == "check_encrypt":
+        params, r, m, h = (q, nq, N), rng.integers(0, 3, (B, N)), rng.integers(0, 3, (B, N)), rng.integers(0, q, (B, N))
+        r[0, 0], h[0, 0] = 1, 1                                   # item 0 is mutated below: no operand row of it is zero
+        if variant == 0:
+            r[0], m[0], h[0] = 2, 2, q - 1
+        arrays = wc.honest_encrypt(q, N, r, m, h)
+    elif entry == "check_decrypt":
+        params, f, fp, e = (q, nq, p, np_, N), tern(), rng.integers(0, p, (B, N)), rng.integers(0, q, (B, N))
+        f[0, 0], fp[0, 0], e[0, 0] = 1, 1, 1
+        if variant == 0:
+            f[0], fp[0], e[0] = q - 1, p - 1, q - 1
+        arrays = wc.honest_decrypt(q, p, N, f, fp, e)
+    else:
+        params, f, fq = (q, nq, N), tern(), rng.integers(0, q, (B, N))
+        f[0, 0], fq[0, 0] = 1, 1
+        if variant == 0:
+            f[0], fq[0] = q - 1, q - 1
+        arrays = wc.honest_inverse(q, N, f, fq)
+    arrays = [np.asarray(a, np.int64) for a in arrays]
+    spots = [(j, idx) for j, a in enumerate(arrays) for idx in (0, a.shape[1] - 1)]
+    arrays = [np.concatenate([a, np.repeat(a[:1], len(spots), axis=0)]) for a in arrays]
+    for k, (j, idx) in enumerate(spots):
+        arrays[j][B + k, idx] += 1
+    total = B + len(spots)
+    want = wc.numpy_check(template, params, arrays)
+    assert not want[:B].any() and want[B:].any(), (entry, want.tolist())            # accepted witnesses, then flagged ones
+    with Dev(eng) as d:
+        fl = d.out((total,), np.uint8)
+        ptrs = [d.up(a.astype(np.uint16)) for a in arrays]
+        if entry == "check_encrypt":
+            eng.check_encrypt_batch_dev(N, q, nq, *ptrs, total, fl)
+        elif entry == "check_decrypt":
+            eng.check_decrypt_batch_dev(N, q, nq, p, np_, *ptrs, total, fl)
+        else:
+            eng.check_inverse_batch_dev(N, q, nq, *ptrs, total, fl)
+        got = [d.get(fl, (total,), np.uint8)]
+    return got, [want]
+
+
+KEYGEN_KEY = np.array([0x9E3779B9 * (i + 1) & 0xFFFFFFFF for i in range(8)], np.uint32)
+KEYGEN_OUT = (("f", np.int8), ("g", np.int8), ("fq", np.uint16), ("fp", np.uint8), ("h", np.uint16))
+_keygen_want = {}                 # the CPU replay of a call, computed once and shared by the four rows
+
+
+def run_keygen(eng, N, q, B, rng, variant, extra):
+    df, dg = extra["df"], extra["dg"]
+    first = extra["first"] - variant
+    args = (N, q, df, dg, first, B)
+    if args not in _keygen_want:
+        _keygen_want[args] = keygen_ref.key_pairs(N, q, df, dg, KEYGEN_KEY, first, B, 100)
+    want = _keygen_want[args]
+    if B > 1:
+        assert (want["tries"] > 1).any() and not want["flags"].any(), args       # the call does redraw, and every item ends as a unit
+    with Dev(eng) as d:
+        outs = [d.out((B, N), dt) for _, dt in KEYGEN_OUT] + [d.out((B,), np.uint8), d.out((B,), np.uint8)]
+        work = d.out((eng.keygen_workspace_bytes(N, B),), np.uint8)
+        eng.keygen_batch_dev(N, q, 3, df, dg, KEYGEN_KEY, first, 100, B, work, *outs)
+        got = [d.get(o, (B, N), dt) for o, (_, dt) in zip(outs, KEYGEN_OUT)] + [d.get(o, (B,), np.uint8) for o in outs[5:]]
+    return got, [want[k] for k, _ in KEYGEN_OUT] + [want["tries"], want["flags"]]
+
+
 def run_shape(eng, entry, s, B, rng, variant):
     N, q, p = s["N"], s["q"], s["p"]
+    if entry == "encrypt_peritem":
+        return run_encrypt_peritem(eng, N, q, B, rng, variant)
+    if entry == "decrypt_peritem":
+        return run_decrypt_peritem(eng, N, q, p, B, rng, variant)
+    if entry == "sum_groups":
+        return run_sum_groups(eng, N, q, B, rng, variant, s["extra"])
+    if entry == "bytes_to_rows":
+        return run_bytes_to_rows(eng, N, s["extra"]["nbytes"], B, rng, variant)
+    if entry == "rows_to_bytes":
+        return run_rows_to_bytes(eng, N, s["extra"]["nbytes"], B, rng, variant)
+    if entry in CHECK_TEMPLATE:
+        return run_check(eng, entry, N, q, p, B, rng, variant)
+    if entry == "keygen":
+        return run_keygen(eng, N, q, B, rng, variant, s["extra"])
     if entry == "encrypt":
         return run_encrypt(eng, N, q, B, rng, variant, witness=variant != 1)
     if entry == "decrypt":
@@ -369,6 +586,7 @@ def test_variant_row_equals_oracle(eng, row):
                     assert_equal(got, want, ctx)
     finally:
         eng.set_kernel_path(0)
+        eng.set_sampler_rounds(20)
 
 
 # ---- p != 3 ------------------------------------------------------------------------------------------------------------------------
@@ -393,6 +611,48 @@ def test_decrypt_and_verify_keys_p_sweep(eng, p):
             got, want = run_verify_keys(eng, N, q, p, 7, rng, 0)
             _not_p3_only(eng, ("verify_keys", N, q, p))
             assert_equal(got, want, ("verify_keys", N, q, p))
+
+
+@pytest.mark.parametrize("p", sorted(P_MAX_N))
+def test_decrypt_peritem_p_sweep(eng, p):
+    """p != 3 with one key pair per item: the composed path, whatever N and q, on the edge operands of the per-row cases."""
+    rng = np.random.default_rng(200 + p)
+    for N in (17, P_MAX_N[p]):
+        for q in (2048, 8192, 65536):
+            for variant in range(3):
+                got, want = run_decrypt_peritem(eng, N, q, p, 3, rng, variant)
+                lk, ctx = eng.last_kernel(), ("decrypt_peritem", N, q, p, variant)
+                assert lk.startswith("peritem_composed(") and lk.endswith(")"), (ctx, lk)
+                inner = lk[len("peritem_composed("):-1]
+                assert not inner.startswith(P3_ONLY) and inner in kv.LAST_KERNELS, (ctx, lk)
+                assert_equal(got, want, ctx)
+
+
+@pytest.mark.parametrize("N", [128, 1024])
+def test_decrypt_peritem_unreduced_fp(eng, N):
+    """fp bytes of 3, 128 and 255 in one item, inside one lane's 16-byte chunk: the ABI asks for fp in [0, p), and k_decrypt_pi_m
+    carries a wave-wide branch that reduces such bytes.  Pinned: the result is that of fp % 3, and that of the composed path (kernel
+    path 1) on the same bytes."""
+    q, B = 2048, 5
+    rng = np.random.default_rng(N)
+    f, fp, e = peritem_ref.decrypt_operands(rng, N, q, 3, B, 2)
+    fp[2] = rng.integers(0, 3, N)
+    chunk = 16 * (N // 16 - 3)
+    fp[2, chunk + 1], fp[2, chunk + 7], fp[2, chunk + 15] = 3, 128, 255
+    assert (fp >= 3).sum() == 3
+    want = list(peritem_ref.oracle_decrypt(N, q, 3, f, fp % 3, e))
+    try:
+        got = decrypt_peritem_call(eng, N, q, 3, f, fp, e)
+        assert eng.last_kernel() == "k_decrypt_pi_m"
+        reduced = decrypt_peritem_call(eng, N, q, 3, f, fp % 3, e)
+        eng.set_kernel_path(1)
+        composed = decrypt_peritem_call(eng, N, q, 3, f, fp, e)
+        assert eng.last_kernel().startswith("peritem_composed("), eng.last_kernel()
+    finally:
+        eng.set_kernel_path(0)
+    assert_equal(reduced, want, ("fp % 3", N))
+    assert_equal(got, want, ("fp >= 3 on the matrix kernel", N))
+    assert_equal(composed, want, ("fp >= 3 on the composed path", N))
 
 
 @pytest.mark.parametrize("p", [1, 2, 4, 5, 7, 8])

@@ -8,6 +8,7 @@ import pytest
 import __graft_entry__ as ge
 from oracle import ntru_keygen as kg
 from oracle import ntru_oracle as orc
+from keygen_ref import replay
 
 pytestmark = pytest.mark.gpu
 pkg = ge.load_package()
@@ -40,22 +41,6 @@ def ge_golden(name):
     import json
     with open(os.path.join(ge.ROOT, "tests", "golden", "scheme_%s.json" % name)) as fh:
         return json.load(fh)
-
-
-def replay(N, df, dg, key, first, B, max_tries):
-    """The contract, item by item, on the CPU: (f, g, tries, flags)."""
-    g = orc.sample_ternary_batch(N, dg, dg, 255, key, (1 << 40) + first, B).view(np.int8)
-    f = orc.sample_ternary_batch(N, df, df - 1, 255, key, first, B).view(np.int8).copy()
-    tries = np.zeros(B, np.uint8)
-    flags = np.zeros(B, np.uint8)
-    for b in range(B):
-        for t in range(max_tries):
-            row = f[b] if t == 0 else orc.sample_ternary_batch(N, df, df - 1, 255, key, (t << 44) + first + b, 1).view(np.int8)[0]
-            fl = (0 if kg.is_unit(row, N, 2) else 8) | (0 if kg.is_unit(row, N, 3) else 16)
-            f[b], tries[b], flags[b] = row, t + 1, fl
-            if not fl:
-                break
-    return f, g, tries, flags
 
 
 def check_against_replay(N, q, out, want):

@@ -1,6 +1,6 @@
 """ntru_encrypt_peritem_batch[_dev] / ntru_decrypt_peritem_batch[_dev] on the GPU: every row against a per-item oracle built from
 oracle.ntru_oracle.polymul_split_batch, against the shared-key oracle with B = 1 per key, across the parameter domain and the kernel
-paths, on ragged and offset batches, against the shared-key calls when every key is the same, and at full size on keys generated on
+paths, at every N of the matrix kernels on edge operands, on ragged and offset batches, against the shared-key calls when every key is the same, and at full size on keys generated on
 the device."""
 import ctypes as C
 import json
@@ -11,6 +11,7 @@ import pytest
 
 import __graft_entry__ as ge
 from oracle import ntru_oracle as orc
+from peritem_ref import decrypt_operands, encrypt_operands, oracle_decrypt, oracle_encrypt
 
 pytestmark = pytest.mark.gpu
 pkg = ge.load_package()
@@ -46,21 +47,6 @@ def inputs(N, q, p, B, seed):
             "fp": g.integers(0, p, (B, N), dtype=np.uint8), "e": g.integers(0, q, (B, N), dtype=np.uint16)}
 
 
-def oracle_encrypt(N, q, h, r, m):
-    """r * h split by 1 - x^N modulo q, m added to the remainder (index.js:90-92)."""
-    quot, rem = orc.polymul_split_batch(N, q, r.astype(np.uint16), h)
-    return ((rem.astype(np.int64) + m) % q).astype(np.uint16), quot
-
-
-def oracle_decrypt(N, q, p, f, fp, e):
-    """f * e modulo q, the centred lift of index.js:117, then fp * a modulo p."""
-    q1, r1 = orc.polymul_split_batch(N, q, (f.astype(np.int64) % q).astype(np.uint16), e)
-    x = r1.astype(np.int64)
-    a = np.where(2 * x > q, (x + 1) % p, x % p).astype(np.uint16)
-    q2, r2 = orc.polymul_split_batch(N, p, fp.astype(np.uint16), a)
-    return r2.astype(np.uint8), q1, r1, q2.astype(np.uint8)
-
-
 def matrix_expected(path, N, q, p=3):
     return path in (0, 4) and q <= 8192 and N <= 1024 and N >= (64 if path == 4 else 128) and p == 3
 
@@ -91,6 +77,53 @@ def test_sweep_against_the_oracle(eng, N, q):
             assert "k_encrypt_pi_m" not in lk
             check_rows(got, oracle_decrypt(N, q, p, xp["f"], xp["fp"], xp["e"]), ("value", "quot1", "rem1", "quot2"))
     eng.set_kernel_path(0)
+
+
+# ---- every N of the matrix kernels: NT = ceil(N / 32), the column mask at N mod 16, the split diagonal -------------------------------
+EVERY_N = [r.tolist() for r in np.array_split(np.arange(64, 1025), 20)]
+FILL = 0xA5
+
+
+@pytest.mark.parametrize("ns", EVERY_N, ids=["%d-%d" % (r[0], r[-1]) for r in EVERY_N])
+def test_peritem_every_n(eng, ns):
+    """Every N from 64 to 1024 at kernel path 4 and from 128 at path 0, q = 256 (one digit plane) and 8192 (two), B = 3: row 0 the
+    extremes, row 1 f = x^(N-1) against an e row of 0, q/2, q/2 + 1, q - 1 (rem1 is its rotation: the strict `>` of the lift at q/2),
+    row 2 random.  Encrypt and decrypt with every witness, every output bit against the oracle; outputs start as FILL bytes."""
+    B, NMAX = 3, 1024
+    rng = np.random.default_rng(ns[0])
+    bufs = [eng.dev_alloc(B * NMAX * 2) for _ in range(7)]                   # device buffers of the whole sweep, sized for N = 1024
+    fill = np.full(B * NMAX * 2, FILL, np.uint8)
+
+    def call(fn, head, ins, out_dts):
+        N = ins[0].shape[1]
+        outs = bufs[len(ins):len(ins) + len(out_dts)]
+        for ptr, a in zip(bufs, ins):
+            eng.dev_upload(ptr, np.ascontiguousarray(a))
+        for ptr, dt in zip(outs, out_dts):
+            eng.dev_upload(ptr, fill[:B * N * np.dtype(dt).itemsize])
+        fn(*head, *bufs[:len(ins)], B, *outs)
+        return [eng.dev_download(ptr, (B, N), dt) for ptr, dt in zip(outs, out_dts)]
+
+    try:
+        for N in ns:
+            for path in ((4, 0) if N >= 128 else (4,)):
+                eng.set_kernel_path(path)
+                for q in (256, 8192):
+                    h, r, m = encrypt_operands(rng, N, q, B)
+                    got = call(eng.encrypt_peritem_batch_dev, (N, q), (h, r, m), (np.uint16, np.uint16))
+                    assert eng.last_kernel() == "k_encrypt_pi_m", (N, q, path, eng.last_kernel())
+                    check_rows(got, oracle_encrypt(N, q, h, r, m), [(name, N, q, path) for name in ("e", "quotE")])
+                    f, fp, e = decrypt_operands(rng, N, q, 3, B)
+                    want = oracle_decrypt(N, q, 3, f, fp, e)
+                    assert (want[2][1] == q // 2).any() and (want[2][1] == q // 2 + 1).any(), (N, q)     # row 1: the lift's edge
+                    got = call(eng.decrypt_peritem_batch_dev, (N, q, 3), (f, fp, e), (np.uint8, np.uint16, np.uint16, np.uint8))
+                    assert eng.last_kernel() == "k_decrypt_pi_m", (N, q, path, eng.last_kernel())
+                    check_rows(got, want, [(name, N, q, path) for name in ("value", "quot1", "rem1", "quot2")])
+    finally:
+        eng.set_kernel_path(0)
+        eng.synchronize()
+        for ptr in bufs:
+            eng.dev_free(ptr)
 
 
 @pytest.mark.parametrize("name", ["n17_q32", "n167_q128", "n509_q2048", "n821_q4096", "n701_q8192"])
