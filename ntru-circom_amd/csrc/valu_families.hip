@@ -345,14 +345,19 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_polymul_split(Geom g, u32 mod
 //
 // Every product on the hot path has one TERNARY operand (r, f, g, the lifted message), and on gfx950 every packed /
 // multiply VALU op issues at 4 cycles per wave while a plain v_add_u32 issues at 2 (profiles/archive/r01_microbench_valu_lds.txt).
-// So the ternary operand becomes the stepping operand: it is turned into 2-bit codes (0 skip, 1 "+w into S1",
-// 2 "+w into S2"; the other symbol c = 2 or -1 is applied once at the end, T = S1 + c*S2), the codes of one block of
-// 2K steps live in one wave-uniform dword, zero steps are skipped by a scalar branch, and the windowed operand is
+// So the ternary operand becomes the stepping operand: each coefficient is one step (0 skip, 1 "+w into S1", otherwise
+// "+w into S2"; the other symbol c = 2 or -1 is applied once at the end, T = S1 + c*S2), the step bits of one block of
+// 2K steps live in wave-uniform scalar words, zero steps are skipped by a scalar branch, and the windowed operand is
 // accumulated with v_add_u32 on two packed 16-bit fields.  A field may only hold `limit` additions of values < q on
-// top of a masked value before it could carry into its neighbour; popcounts of the code word keep that budget and
-// the accumulators are masked (mod q is free: q | 2^16) only when the next K steps could exceed it.
-// Needs one item per wave (nl > 32), K <= 7 (2K codes in a dword) and (K+1)*(q-1) <= 65535; otherwise the MAC
-// kernels above are used.
+// top of a masked value before it could carry into its neighbour, so the accumulators are masked (mod q is free:
+// q | 2^16) every ME steps, ME <= limit chosen by the launcher; products with exact small sums never mask (ME = 0).
+//
+// Two families use this machinery, written once below (TernOps, add_steps, add_core, add_product_split) over the
+// policy types PerItemWin / SharedWin, which state what differs between them:
+//   per-item stepping (k_encrypt_t, k_decrypt_t, k_verify_keys_t): the stepping operand belongs to the item; one item
+//     per wave (nl > 32), K <= 7 (2K step bits in half a dword) and (K+1)*(q-1) <= 65535;
+//   shared-key stepping (k_decrypt_s): every wave steps over the same key; two items per wave, K = 9 / 11 / 13.
+// Otherwise the MAC kernels above are used.
 // ================================================================================================================
 
 // bit j: step j adds into S1 (value 1); bit 16+j: step j adds into S2 (the other non-zero symbol).  Written with
@@ -378,238 +383,104 @@ static __device__ __forceinline__ void snapshot_if(bool take, u32 (&L1)[K], u32 
   }
 }
 
+// TernOps<K>::step<B1, B2>: bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.
+// Wave-uniform scalar tests, exactly one taken branch per step, in-place full-rate adds.  One asm block per K (the
+// operand lists must be spelled out), all seven generated from the one definition below: TERN_Rk(M) repeats M(i) for
+// i = 1 .. k-1; element 0 is written out so that every further list element can carry its leading comma.
 template <int K> struct TernOps;
-template <>
-struct TernOps<1> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[1], u32 (&S2)[1], const u32 (&W)[1], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [b0] "+v"(S2[0])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0])
-                 : "scc");
+#define TERN_R1(M)
+#define TERN_R3(M) M(1) M(2)
+#define TERN_R5(M) TERN_R3(M) M(3) M(4)
+#define TERN_R7(M) TERN_R5(M) M(5) M(6)
+#define TERN_R9(M) TERN_R7(M) M(7) M(8)
+#define TERN_R11(M) TERN_R9(M) M(9) M(10)
+#define TERN_R13(M) TERN_R11(M) M(11) M(12)
+#define TERN_ADD_A(i) "v_add_u32 %[a" #i "], %[a" #i "], %[w" #i "]\n\t"
+#define TERN_ADD_B(i) "v_add_u32 %[b" #i "], %[b" #i "], %[w" #i "]\n\t"
+#define TERN_ACC_A(i) , [a##i] "+v"(S1[i])
+#define TERN_ACC_B(i) , [b##i] "+v"(S2[i])
+#define TERN_WIN(i) , [w##i] "v"(W[i])
+#define TERN_OPS(K)                                                                                                  \
+  template <>                                                                                                        \
+  struct TernOps<K> {                                                                                                \
+    template <int B1, int B2>                                                                                        \
+    static __device__ __forceinline__ void step(u32 (&S1)[K], u32 (&S2)[K], const u32 (&W)[K], u32 w1, u32 w2) {     \
+      asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"                                                               \
+                   "s_cbranch_scc1 2f\n\t"                                                                           \
+                   "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"                                                               \
+                   "s_cbranch_scc0 3f\n\t"                                                                           \
+                   TERN_ADD_B(0) TERN_R##K(TERN_ADD_B)                                                               \
+                   "s_branch 3f\n"                                                                                   \
+                   "2:\n\t"                                                                                          \
+                   TERN_ADD_A(0) TERN_R##K(TERN_ADD_A)                                                               \
+                   "3:\n"                                                                                            \
+                   : [a0] "+v"(S1[0]) TERN_R##K(TERN_ACC_A), [b0] "+v"(S2[0]) TERN_R##K(TERN_ACC_B)                  \
+                   : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]) TERN_R##K(TERN_WIN) \
+                   : "scc");                                                                                         \
+    }                                                                                                                \
+  };
+TERN_OPS(1)
+TERN_OPS(3)
+TERN_OPS(5)
+TERN_OPS(7)
+TERN_OPS(9)
+TERN_OPS(11)
+TERN_OPS(13)
+#undef TERN_OPS
+
+static __device__ __forceinline__ u32 odd_pair(u32 e_u, u32 e_um1) { return __builtin_amdgcn_alignbit(e_u, e_um1, 16); }
+
+// ---- the two add-path families ------------------------------------------------------------------------------------
+// Per-item stepping (k_encrypt_t, k_decrypt_t, k_verify_keys_t) and shared-key stepping (k_decrypt_s, described at
+// build_cyclic_pairs below) run the same steps, block loop and finish.  Everything in which they differ is stated by
+// these two policy types:
+//   1. step bits (Code, bit2, hold, fetch): one code dword per block, step j tests its bits j and 16+j -- against two
+//      mask words per block (x: "into S1", y: "into S2") that each use bit j.  The block loop holds the current block's
+//      Code and looks one block ahead; each family keeps its own order of loads and readfirstlanes: the dword is made
+//      scalar when it becomes the held one -- against the held uint2 staying in VGPRs until its block begins.
+//   2. window (Entry, even, odd, extra, stored_odd): LDS entries {E[u], O[u]} -- against entries E[u] alone with
+//      O[u] = odd_pair(E[u], E[u-1]), so that the refill of one block needs K + 1 next-window entries, not K.
+//   3. remainder (masks_rem): a power-of-two remainder is left to the caller, who adds to it first and then masks --
+//      against masked in the finish.  (Small moduli are reduced exactly in both.)
+struct PerItemWin {
+  using Entry = uint2;
+  using Code = u32;
+  static constexpr int extra = 0;                       // next-window entries a block pre-loads beyond K
+  static constexpr bool stored_odd = true;              // O[0] = (b[-1], b[0]) is stored: the linear product cuts b[-1]
+  static constexpr bool masks_rem = false;
+  static constexpr int bit2(int J) { return 16 + J; }
+  static __device__ __forceinline__ u32 even(Entry v) { return v.x; }
+  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return v.y; }
+  static __device__ __forceinline__ Code hold(Code c) { return __builtin_amdgcn_readfirstlane(c); }
+  // the held block's two step words, and the look-ahead load of block m + 1's Code (clamped at the last block)
+  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
+    w1 = held; w2 = held;
+    return codes[m + 1 < nblk ? m + 1 : m];
   }
 };
-template <>
-struct TernOps<3> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[3], u32 (&S2)[3], const u32 (&W)[3], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2])
-                 : "scc");
-  }
-};
-template <>
-struct TernOps<5> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[5], u32 (&S2)[5], const u32 (&W)[5], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "v_add_u32 %[b3], %[b3], %[w3]\n\t"
-                 "v_add_u32 %[b4], %[b4], %[w4]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "v_add_u32 %[a3], %[a3], %[w3]\n\t"
-                 "v_add_u32 %[a4], %[a4], %[w4]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [a3] "+v"(S1[3]), [a4] "+v"(S1[4]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2]), [b3] "+v"(S2[3]), [b4] "+v"(S2[4])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2]), [w3] "v"(W[3]), [w4] "v"(W[4])
-                 : "scc");
-  }
-};
-template <>
-struct TernOps<7> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[7], u32 (&S2)[7], const u32 (&W)[7], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "v_add_u32 %[b3], %[b3], %[w3]\n\t"
-                 "v_add_u32 %[b4], %[b4], %[w4]\n\t"
-                 "v_add_u32 %[b5], %[b5], %[w5]\n\t"
-                 "v_add_u32 %[b6], %[b6], %[w6]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "v_add_u32 %[a3], %[a3], %[w3]\n\t"
-                 "v_add_u32 %[a4], %[a4], %[w4]\n\t"
-                 "v_add_u32 %[a5], %[a5], %[w5]\n\t"
-                 "v_add_u32 %[a6], %[a6], %[w6]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [a3] "+v"(S1[3]), [a4] "+v"(S1[4]), [a5] "+v"(S1[5]), [a6] "+v"(S1[6]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2]), [b3] "+v"(S2[3]), [b4] "+v"(S2[4]), [b5] "+v"(S2[5]), [b6] "+v"(S2[6])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2]), [w3] "v"(W[3]), [w4] "v"(W[4]), [w5] "v"(W[5]), [w6] "v"(W[6])
-                 : "scc");
-  }
-};
-template <>
-struct TernOps<9> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[9], u32 (&S2)[9], const u32 (&W)[9], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "v_add_u32 %[b3], %[b3], %[w3]\n\t"
-                 "v_add_u32 %[b4], %[b4], %[w4]\n\t"
-                 "v_add_u32 %[b5], %[b5], %[w5]\n\t"
-                 "v_add_u32 %[b6], %[b6], %[w6]\n\t"
-                 "v_add_u32 %[b7], %[b7], %[w7]\n\t"
-                 "v_add_u32 %[b8], %[b8], %[w8]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "v_add_u32 %[a3], %[a3], %[w3]\n\t"
-                 "v_add_u32 %[a4], %[a4], %[w4]\n\t"
-                 "v_add_u32 %[a5], %[a5], %[w5]\n\t"
-                 "v_add_u32 %[a6], %[a6], %[w6]\n\t"
-                 "v_add_u32 %[a7], %[a7], %[w7]\n\t"
-                 "v_add_u32 %[a8], %[a8], %[w8]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [a3] "+v"(S1[3]), [a4] "+v"(S1[4]), [a5] "+v"(S1[5]), [a6] "+v"(S1[6]), [a7] "+v"(S1[7]), [a8] "+v"(S1[8]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2]), [b3] "+v"(S2[3]), [b4] "+v"(S2[4]), [b5] "+v"(S2[5]), [b6] "+v"(S2[6]), [b7] "+v"(S2[7]), [b8] "+v"(S2[8])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2]), [w3] "v"(W[3]), [w4] "v"(W[4]), [w5] "v"(W[5]), [w6] "v"(W[6]), [w7] "v"(W[7]), [w8] "v"(W[8])
-                 : "scc");
-  }
-};
-template <>
-struct TernOps<11> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[11], u32 (&S2)[11], const u32 (&W)[11], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "v_add_u32 %[b3], %[b3], %[w3]\n\t"
-                 "v_add_u32 %[b4], %[b4], %[w4]\n\t"
-                 "v_add_u32 %[b5], %[b5], %[w5]\n\t"
-                 "v_add_u32 %[b6], %[b6], %[w6]\n\t"
-                 "v_add_u32 %[b7], %[b7], %[w7]\n\t"
-                 "v_add_u32 %[b8], %[b8], %[w8]\n\t"
-                 "v_add_u32 %[b9], %[b9], %[w9]\n\t"
-                 "v_add_u32 %[b10], %[b10], %[w10]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "v_add_u32 %[a3], %[a3], %[w3]\n\t"
-                 "v_add_u32 %[a4], %[a4], %[w4]\n\t"
-                 "v_add_u32 %[a5], %[a5], %[w5]\n\t"
-                 "v_add_u32 %[a6], %[a6], %[w6]\n\t"
-                 "v_add_u32 %[a7], %[a7], %[w7]\n\t"
-                 "v_add_u32 %[a8], %[a8], %[w8]\n\t"
-                 "v_add_u32 %[a9], %[a9], %[w9]\n\t"
-                 "v_add_u32 %[a10], %[a10], %[w10]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [a3] "+v"(S1[3]), [a4] "+v"(S1[4]), [a5] "+v"(S1[5]), [a6] "+v"(S1[6]), [a7] "+v"(S1[7]), [a8] "+v"(S1[8]), [a9] "+v"(S1[9]), [a10] "+v"(S1[10]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2]), [b3] "+v"(S2[3]), [b4] "+v"(S2[4]), [b5] "+v"(S2[5]), [b6] "+v"(S2[6]), [b7] "+v"(S2[7]), [b8] "+v"(S2[8]), [b9] "+v"(S2[9]), [b10] "+v"(S2[10])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2]), [w3] "v"(W[3]), [w4] "v"(W[4]), [w5] "v"(W[5]), [w6] "v"(W[6]), [w7] "v"(W[7]), [w8] "v"(W[8]), [w9] "v"(W[9]), [w10] "v"(W[10])
-                 : "scc");
-  }
-};
-template <>
-struct TernOps<13> {
-  // bit B1 of w1 set: S1[t] += W[t]; else bit B2 of w2 set: S2[t] += W[t]; else nothing.  Wave-uniform scalar tests,
-  // exactly one taken branch per step, in-place full-rate adds.
-  template <int B1, int B2>
-  static __device__ __forceinline__ void step(u32 (&S1)[13], u32 (&S2)[13], const u32 (&W)[13], u32 w1, u32 w2) {
-    asm volatile("s_bitcmp1_b32 %[wd1], %[bit1]\n\t"
-                 "s_cbranch_scc1 2f\n\t"
-                 "s_bitcmp1_b32 %[wd2], %[bit2]\n\t"
-                 "s_cbranch_scc0 3f\n\t"
-                 "v_add_u32 %[b0], %[b0], %[w0]\n\t"
-                 "v_add_u32 %[b1], %[b1], %[w1]\n\t"
-                 "v_add_u32 %[b2], %[b2], %[w2]\n\t"
-                 "v_add_u32 %[b3], %[b3], %[w3]\n\t"
-                 "v_add_u32 %[b4], %[b4], %[w4]\n\t"
-                 "v_add_u32 %[b5], %[b5], %[w5]\n\t"
-                 "v_add_u32 %[b6], %[b6], %[w6]\n\t"
-                 "v_add_u32 %[b7], %[b7], %[w7]\n\t"
-                 "v_add_u32 %[b8], %[b8], %[w8]\n\t"
-                 "v_add_u32 %[b9], %[b9], %[w9]\n\t"
-                 "v_add_u32 %[b10], %[b10], %[w10]\n\t"
-                 "v_add_u32 %[b11], %[b11], %[w11]\n\t"
-                 "v_add_u32 %[b12], %[b12], %[w12]\n\t"
-                 "s_branch 3f\n"
-                 "2:\n\t"
-                 "v_add_u32 %[a0], %[a0], %[w0]\n\t"
-                 "v_add_u32 %[a1], %[a1], %[w1]\n\t"
-                 "v_add_u32 %[a2], %[a2], %[w2]\n\t"
-                 "v_add_u32 %[a3], %[a3], %[w3]\n\t"
-                 "v_add_u32 %[a4], %[a4], %[w4]\n\t"
-                 "v_add_u32 %[a5], %[a5], %[w5]\n\t"
-                 "v_add_u32 %[a6], %[a6], %[w6]\n\t"
-                 "v_add_u32 %[a7], %[a7], %[w7]\n\t"
-                 "v_add_u32 %[a8], %[a8], %[w8]\n\t"
-                 "v_add_u32 %[a9], %[a9], %[w9]\n\t"
-                 "v_add_u32 %[a10], %[a10], %[w10]\n\t"
-                 "v_add_u32 %[a11], %[a11], %[w11]\n\t"
-                 "v_add_u32 %[a12], %[a12], %[w12]\n\t"
-                 "3:\n"
-                 : [a0] "+v"(S1[0]), [a1] "+v"(S1[1]), [a2] "+v"(S1[2]), [a3] "+v"(S1[3]), [a4] "+v"(S1[4]), [a5] "+v"(S1[5]), [a6] "+v"(S1[6]), [a7] "+v"(S1[7]), [a8] "+v"(S1[8]), [a9] "+v"(S1[9]), [a10] "+v"(S1[10]), [a11] "+v"(S1[11]), [a12] "+v"(S1[12]), [b0] "+v"(S2[0]), [b1] "+v"(S2[1]), [b2] "+v"(S2[2]), [b3] "+v"(S2[3]), [b4] "+v"(S2[4]), [b5] "+v"(S2[5]), [b6] "+v"(S2[6]), [b7] "+v"(S2[7]), [b8] "+v"(S2[8]), [b9] "+v"(S2[9]), [b10] "+v"(S2[10]), [b11] "+v"(S2[11]), [b12] "+v"(S2[12])
-                 : [wd1] "s"(w1), [wd2] "s"(w2), [bit1] "i"(B1), [bit2] "i"(B2), [w0] "v"(W[0]), [w1] "v"(W[1]), [w2] "v"(W[2]), [w3] "v"(W[3]), [w4] "v"(W[4]), [w5] "v"(W[5]), [w6] "v"(W[6]), [w7] "v"(W[7]), [w8] "v"(W[8]), [w9] "v"(W[9]), [w10] "v"(W[10]), [w11] "v"(W[11]), [w12] "v"(W[12])
-                 : "scc");
+struct SharedWin {
+  using Entry = u32;
+  using Code = uint2;
+  static constexpr int extra = 1;
+  static constexpr bool stored_odd = false;             // derived from the entry before; none before index 0
+  static constexpr bool masks_rem = true;
+  static constexpr int bit2(int J) { return J; }
+  static __device__ __forceinline__ u32 even(Entry v) { return v; }
+  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return odd_pair(v, before); }
+  static __device__ __forceinline__ Code hold(Code c) { return c; }
+  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
+    w1 = __builtin_amdgcn_readfirstlane(held.x); w2 = __builtin_amdgcn_readfirstlane(held.y);
+    return codes[m + 1 < nblk ? m + 1 : m];
   }
 };
 
 // Steps J .. 2K-1 of one block (compile-time recursion so every bit index / register index is an immediate).
-// word: bit j = "step j adds into S1", bit 16+j = "step j adds into S2".  ME: mask both sets every ME steps
-// (0 = never: exact small sums).  At most ME additions of values < q land on a masked field between masks.
-template <int K, int ME, int J>
-static __device__ __forceinline__ void tern_steps(u32 (&S1)[K], u32 (&S2)[K], u32 (&WE)[K], u32 (&WO)[K],
-                                                  const uint2 (&nw)[K], u32 word, u32 fmask) {
+// Step j adds into S1 if bit j of w1 is set, else into S2 if bit Win::bit2(j) of w2 is.  ME: mask both sets every ME
+// steps (0 = never: exact small sums).  At most ME additions of values < q land on a masked field between masks.
+template <class Win, int K, int ME, int J>
+static __device__ __forceinline__ void add_steps(u32 (&S1)[K], u32 (&S2)[K], u32 (&WE)[K], u32 (&WO)[K],
+                                                 const typename Win::Entry (&nw)[K + Win::extra], u32 w1, u32 w2,
+                                                 u32 fmask) {
   if constexpr (J < 2 * K) {
     if constexpr (ME > 0 && J % (ME > 0 ? ME : 1) == 0) {
 #pragma unroll
@@ -619,32 +490,38 @@ static __device__ __forceinline__ void tern_steps(u32 (&S1)[K], u32 (&S2)[K], u3
     u32 W[K];
 #pragma unroll
     for (int t = 0; t < K; t++) W[t] = (J & 1) ? WO[(t - s + K) % K] : WE[(t - s + K) % K];
-    TernOps<K>::template step<J, 16 + J>(S1, S2, W, word, word);
-    if constexpr ((J & 1) != 0) { WE[K - 1 - s] = nw[s].x; WO[K - 1 - s] = nw[s].y; }
-    tern_steps<K, ME, J + 1>(S1, S2, WE, WO, nw, word, fmask);
+    TernOps<K>::template step<J, Win::bit2(J)>(S1, S2, W, w1, w2);
+    if constexpr ((J & 1) != 0) { WE[K - 1 - s] = Win::even(nw[s]); WO[K - 1 - s] = Win::odd(nw[s], nw[s + Win::extra]); }
+    add_steps<Win, K, ME, J + 1>(S1, S2, WE, WO, nw, w1, w2, fmask);
   }
 }
 
-template <int K, int ME, bool WL>
-static __device__ __forceinline__ void tern_core(const uint2 *__restrict__ eo, const u32 *__restrict__ codes,
-                                                 const Geom &g, int sub, u32 fmask,
-                                                 u32 (&S1)[K], u32 (&S2)[K], u32 (&L1)[K], u32 (&L2)[K]) {
+// The block loop.  win: the item's window array in LDS, codes: one Win::Code per block of 2K steps, sub: the lane's
+// index in the item.  WL: snapshot the accumulators before the lane's own block (the low half, for the quotient).
+template <class Win, int K, int ME, bool WL>
+static __device__ __forceinline__ void add_core(const typename Win::Entry *__restrict__ win,
+                                                const typename Win::Code *__restrict__ codes, const Geom &g, int sub,
+                                                u32 fmask, u32 (&S1)[K], u32 (&S2)[K], u32 (&L1)[K], u32 (&L2)[K]) {
   u32 WE[K], WO[K];
-  const uint2 *nb = eo + (K * sub + g.off);
+  const typename Win::Entry *nb = win + (K * sub + g.off);
+  {
+    typename Win::Entry prev = nb[-1];
 #pragma unroll
-  for (int x = 0; x < K; x++) { uint2 v = nb[x]; WE[x] = v.x; WO[x] = v.y; }
+    for (int x = 0; x < K; x++) { const typename Win::Entry v = nb[x]; WE[x] = Win::even(v); WO[x] = Win::odd(v, prev); prev = v; }
+  }
 #pragma unroll
   for (int t = 0; t < K; t++) { S1[t] = 0; S2[t] = 0; L1[t] = 0; L2[t] = 0; }
   const int nblk = g.nl;
-  u32 word = __builtin_amdgcn_readfirstlane(codes[0]);
+  typename Win::Code held = Win::hold(codes[0]);
   for (int m = 0; m < nblk; m++) {
-    const u32 next_raw = codes[m + 1 < nblk ? m + 1 : m];
+    u32 w1 = 0, w2 = 0;
+    const typename Win::Code next = Win::fetch(codes, m, nblk, held, w1, w2);
     if constexpr (WL) snapshot_if<K>(m == sub, L1, L2, S1, S2);
-    uint2 nw[K];
+    typename Win::Entry nw[K + Win::extra];
 #pragma unroll
-    for (int s = 0; s < K; s++) nw[s] = nb[-1 - s];
-    tern_steps<K, ME, 0>(S1, S2, WE, WO, nw, word, fmask);
-    word = __builtin_amdgcn_readfirstlane(next_raw);
+    for (int s = 0; s < K + Win::extra; s++) nw[s] = nb[-1 - s];
+    add_steps<Win, K, ME, 0>(S1, S2, WE, WO, nw, w1, w2, fmask);
+    held = Win::hold(next);
     nb -= K;
   }
 }
@@ -659,8 +536,6 @@ static __device__ __forceinline__ u16x2 tern_combine(u32 s1, u32 s2, u32 fmask, 
   else return as_pair(s1) + as_pair(s2) + as_pair(s2);
 }
 
-// Finish one ternary-stepped product: remainder / quotient pairs like product_split.
-//   av: the lane's own 2K stepping-operand values (numeric, as u16 pairs) for the in-block triangle.
 // Which lanes may store a whole block of 2K outputs without bounds checks, and which one holds the row's tail.
 struct StorePlan {
   bool full, tail; int nv;      // nv: number of valid outputs in the tail lane (wave-uniform)
@@ -684,25 +559,34 @@ static __device__ __forceinline__ void store_pair(OutT *lane_row, const StorePla
   }
 }
 
-// Runs one per-item-stepped product and hands each finished pair to `emit(t, rem_pair, quot_pair)` right away.
+// Runs one stepped product and hands each finished pair to `emit(t, rem_pair, quot_pair)` right away (so no result
+// arrays stay live: register pressure is what limits k_decrypt_s's occupancy).  Remainder / quotient as product_split.
 // av(s): the lane's s-th pair of the stepping operand (numeric), only evaluated for the triangle after the main loop.
-template <int K, int ME, bool NEG, class AV, class Emit>
-static __device__ __forceinline__ void tern_product_split(const uint2 *eo, const u32 *codes, AV av,
-                                                          const Geom &g, int sub, bool want_quot, u32 mod, Emit emit) {
+// The per-item kernels call this with PerItemWin themselves: a forwarding tern_product_split in between changes the
+// register allocation of k_decrypt_t and k_verify_keys_t.  k_decrypt_s goes through shared_product_split below.
+template <class Win, int K, int ME, bool NEG, class AV, class Emit>
+static __device__ __forceinline__ void add_product_split(const typename Win::Entry *win, const typename Win::Code *codes,
+                                                         AV av, const Geom &g, int sub, bool want_quot, u32 mod,
+                                                         Emit emit) {
   constexpr bool POW2 = ME > 0;
   const u32 fmask = POW2 ? (mod - 1) * 0x00010001u : 0xFFFFFFFFu;
   const u32 qq = mod * 0x00010001u;
   u32 S1[K], S2[K], L1[K], L2[K];
-  if (want_quot) tern_core<K, ME, true>(eo, codes, g, sub, fmask, S1, S2, L1, L2);
-  else tern_core<K, ME, false>(eo, codes, g, sub, fmask, S1, S2, L1, L2);
+  if (want_quot) add_core<Win, K, ME, true>(win, codes, g, sub, fmask, S1, S2, L1, L2);
+  else add_core<Win, K, ME, false>(win, codes, g, sub, fmask, S1, S2, L1, L2);
+  // fold the snapshots into "low" right away (frees L2), then add the in-block triangle
   u16x2 low[K];
 #pragma unroll
   for (int t = 0; t < K; t++) low[t] = tern_combine<NEG>(L1[t], L2[t], fmask, qq);
-  if (want_quot) {                                   // in-block triangle
+  if (want_quot) {
     u32 ZE[K], ZO[K];
+    typename Win::Entry prev = {};                   // the linear product has no coefficient before index 0
 #pragma unroll
-    for (int x = 0; x < K; x++) { uint2 v = eo[g.off + x]; ZE[x] = v.x; ZO[x] = v.y; }
-    ZO[0] &= 0xFFFF0000u;
+    for (int x = 0; x < K; x++) {
+      const typename Win::Entry v = win[g.off + x];
+      ZE[x] = Win::even(v); ZO[x] = Win::odd(v, prev); prev = v;
+    }
+    if constexpr (Win::stored_odd) ZO[0] &= 0xFFFF0000u;
 #pragma unroll
     for (int s = 0; s < K; s++) {
       const u16x2 ap = as_pair(av(s));
@@ -726,10 +610,12 @@ static __device__ __forceinline__ void tern_product_split(const uint2 *eo, const
         qv = (u16x2){(u16)(h0 ? mod - h0 : 0), (u16)(h1 ? mod - h1 : 0)};
       }
     }
-    const u16x2 rv = POW2 ? T : (u16x2){(u16)mod_small(T.x, mod), (u16)mod_small(T.y, mod)};   // POW2: caller masks
+    const u16x2 rv = POW2 ? (Win::masks_rem ? (T & (u16)(mod - 1)) : T)
+                          : (u16x2){(u16)mod_small(T.x, mod), (u16)mod_small(T.y, mod)};
     emit(t, rv, qv);
   }
 }
+
 
 // Load the lane's block of the stepping operand: numeric u16 pairs for the triangle + the block's code word.
 template <int K, class F>
@@ -780,7 +666,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 7) void k_encrypt_t(Geom g, u32 q, c
       const u32 v0 = k < N ? rr[k0] : 0u, v1 = k + 1 < N ? rr[k1] : 0u;
       return v0 | (v1 << 16);
     };
-    tern_product_split<K, ME, false>(eo_h, codes, r_pair, g, sub, want_quot, q, [&](int t, u16x2 rv, u16x2 qv) {
+    add_product_split<PerItemWin, K, ME, false>(eo_h, codes, r_pair, g, sub, want_quot, q, [&](int t, u16x2 rv, u16x2 qv) {
       int sub2 = sub;
       asm volatile("" : "+v"(sub2));
       const StorePlan sp = store_plan<K>(g, sub2, L.active);
@@ -829,7 +715,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
     const long lane0 = row + 2 * K * L.sub;
     u32 av_b[K], wb = 0;
     // remainder1 / quotient1 stored pair by pair; centred lift, index.js:117 verbatim -> second stepping operand
-    tern_product_split<K, ME, true>(eo_e, codes_f, [&](int t) { return av_f[t]; }, g, L.sub, want_q1, q, [&](int t, u16x2 rv, u16x2 qv) {
+    add_product_split<PerItemWin, K, ME, true>(eo_e, codes_f, [&](int t) { return av_f[t]; }, g, L.sub, want_q1, q, [&](int t, u16x2 rv, u16x2 qv) {
       rv = rv & (u16)(q - 1);
       if (rem1) store_pair(rem1 + lane0, sp, t, rv);
       if (want_q1) store_pair(quot1 + lane0, sp, t, qv);
@@ -842,7 +728,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
     });
     if (L.active) codes_b[L.sub] = wb;
     wave_lds_fence();
-    tern_product_split<K, 0, false>(eo_fp, codes_b, [&](int t) { return av_b[t]; }, g, L.sub, want_q2, p, [&](int t, u16x2 rv, u16x2 qv) {
+    add_product_split<PerItemWin, K, 0, false>(eo_fp, codes_b, [&](int t) { return av_b[t]; }, g, L.sub, want_q2, p, [&](int t, u16x2 rv, u16x2 qv) {
       store_pair(value + lane0, sp, t, rv);
       if (want_q2) store_pair(quot2 + lane0, sp, t, qv);
     });
@@ -859,8 +745,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
 // in LDS as ONE cyclic array of aligned pairs E[u] = (bc[2u], bc[2u+1]); the odd-aligned pairs are derived on the fly,
 // O[u] = alignbit(E[u], E[u-1], 16).  N must be odd (so that the cyclic wrap turns aligned pairs into odd-aligned ones).
 // ================================================================================================================
-
-static __device__ __forceinline__ u32 odd_pair(u32 e_u, u32 e_um1) { return __builtin_amdgcn_alignbit(e_u, e_um1, 16); }
 
 // Fill this item's cyclic pair array from the K aligned pairs P[t] = (x[2v], x[(2v+1) mod N]), v = K*sub + t, held in
 // registers by the item's lanes.  E points at logical entry u = -off (one spare entry sits in front of it, one dummy
@@ -894,99 +778,12 @@ static __device__ __forceinline__ void build_cyclic_pairs(u32 *E, const Geom &g,
   wave_lds_fence();
 }
 
-template <int K, int ME, int J>
-static __device__ __forceinline__ void shared_steps(u32 (&S1)[K], u32 (&S2)[K], u32 (&WE)[K], u32 (&WO)[K],
-                                                    const u32 (&nw)[K + 1], u32 ones, u32 twos, u32 fmask) {
-  if constexpr (J < 2 * K) {
-    if constexpr (ME > 0 && J % (ME > 0 ? ME : 1) == 0) {
-#pragma unroll
-      for (int t = 0; t < K; t++) { S1[t] &= fmask; S2[t] &= fmask; }
-    }
-    constexpr int s = J >> 1;
-    u32 W[K];
-#pragma unroll
-    for (int t = 0; t < K; t++) W[t] = (J & 1) ? WO[(t - s + K) % K] : WE[(t - s + K) % K];
-    TernOps<K>::template step<J, J>(S1, S2, W, ones, twos);
-    if constexpr ((J & 1) != 0) { WE[K - 1 - s] = nw[s]; WO[K - 1 - s] = odd_pair(nw[s], nw[s + 1]); }
-    shared_steps<K, ME, J + 1>(S1, S2, WE, WO, nw, ones, twos, fmask);
-  }
-}
-
-// masks: one uint2 per block (x: steps adding into S1, y: steps adding into S2), identical for every item.
-template <int K, int ME, bool WL>
-static __device__ __forceinline__ void shared_core(const u32 *__restrict__ E, const uint2 *__restrict__ masks,
-                                                   const Geom &g, int sub, u32 fmask,
-                                                   u32 (&S1)[K], u32 (&S2)[K], u32 (&L1)[K], u32 (&L2)[K]) {
-  u32 WE[K], WO[K];
-  const u32 *nb = E + (K * sub + g.off);
-  {
-    u32 prev = nb[-1];
-#pragma unroll
-    for (int x = 0; x < K; x++) { const u32 v = nb[x]; WE[x] = v; WO[x] = odd_pair(v, prev); prev = v; }
-  }
-#pragma unroll
-  for (int t = 0; t < K; t++) { S1[t] = 0; S2[t] = 0; L1[t] = 0; L2[t] = 0; }
-  const int nblk = g.nl;
-  uint2 mk = masks[0];
-  for (int m = 0; m < nblk; m++) {
-    const u32 ones = __builtin_amdgcn_readfirstlane(mk.x), twos = __builtin_amdgcn_readfirstlane(mk.y);
-    mk = masks[m + 1 < nblk ? m + 1 : m];
-    if constexpr (WL) snapshot_if<K>(m == sub, L1, L2, S1, S2);
-    u32 nw[K + 1];
-#pragma unroll
-    for (int s = 0; s <= K; s++) nw[s] = nb[-1 - s];
-    shared_steps<K, ME, 0>(S1, S2, WE, WO, nw, ones, twos, fmask);
-    nb -= K;
-  }
-}
-
-// Finish a shared-stepped product (same contract as tern_product_split; av = the lane's block of the stepping operand).
-// Runs one shared-stepped product and hands each finished pair to `emit(t, rem_pair, quot_pair)` right away (so no
-// result arrays stay live: register pressure is what limits this kernel's occupancy).
+// add_product_split for shared-key stepping: E is the item's cyclic pair array, masks one uint2 per block (x: steps
+// adding into S1, y: steps adding into S2), identical for every item; av the lane's block of the stepping operand.
 template <int K, int ME, bool NEG, class Emit>
 static __device__ __forceinline__ void shared_product_split(const u32 *E, const uint2 *masks, const u32 *av,
                                                             const Geom &g, int sub, bool want_quot, u32 mod, Emit emit) {
-  constexpr bool POW2 = ME > 0;
-  const u32 fmask = POW2 ? (mod - 1) * 0x00010001u : 0xFFFFFFFFu;
-  const u32 qq = mod * 0x00010001u;
-  u32 S1[K], S2[K], L1[K], L2[K];
-  if (want_quot) shared_core<K, ME, true>(E, masks, g, sub, fmask, S1, S2, L1, L2);
-  else shared_core<K, ME, false>(E, masks, g, sub, fmask, S1, S2, L1, L2);
-  // fold the snapshots into "low" right away (frees L2), then add the in-block triangle
-  u16x2 low[K];
-#pragma unroll
-  for (int t = 0; t < K; t++) low[t] = tern_combine<NEG>(L1[t], L2[t], fmask, qq);
-  if (want_quot) {
-    u32 ZE[K], ZO[K];
-    u32 prev = 0;                                    // the linear product has no coefficient before index 0
-#pragma unroll
-    for (int x = 0; x < K; x++) { const u32 v = E[g.off + x]; ZE[x] = v; ZO[x] = odd_pair(v, prev); prev = v; }
-#pragma unroll
-    for (int s = 0; s < K; s++) {
-      const u16x2 ap = as_pair(av[s]);
-#pragma unroll
-      for (int t = s; t < K; t++) {
-        low[t] = ap.xx * as_pair(ZE[t - s]) + low[t];
-        low[t] = ap.yy * as_pair(ZO[t - s]) + low[t];
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < K; t++) {
-    const u16x2 T = tern_combine<NEG>(S1[t], S2[t], fmask, qq);
-    u16x2 qv = (u16x2){0, 0};
-    if (want_quot) {
-      const u16x2 hi = T - low[t];
-      if (POW2) {
-        qv = ((u16x2){0, 0} - hi) & (u16)(mod - 1);
-      } else {
-        const u32 h0 = mod_small(hi.x, mod), h1 = mod_small(hi.y, mod);
-        qv = (u16x2){(u16)(h0 ? mod - h0 : 0), (u16)(h1 ? mod - h1 : 0)};
-      }
-    }
-    const u16x2 rv = POW2 ? (T & (u16)(mod - 1)) : (u16x2){(u16)mod_small(T.x, mod), (u16)mod_small(T.y, mod)};
-    emit(t, rv, qv);
-  }
+  add_product_split<SharedWin, K, ME, NEG>(E, masks, [&](int s) { return av[s]; }, g, sub, want_quot, mod, emit);
 }
 
 
@@ -1386,7 +1183,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
     };
     // ---- fq * f mod q
     product(ValU16{fq + row}, f, q - 1,
-            [&](auto s_pair, auto emit) { tern_product_split<K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
+            [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
             [&](int t, u16x2 rv, u16x2 qv) {
               int sub2 = sub; asm volatile("" : "+v"(sub2));
               rv = rv & (u16)(q - 1);
@@ -1400,7 +1197,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
     // ---- fp * f mod p
     nz_hi = false; first_not_one = false;
     product(ValU8{fp + row}, f, p - 1,
-            [&](auto s_pair, auto emit) { tern_product_split<K, 0, false>(eo, codes, s_pair, g, sub, true, p, emit); },
+            [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, 0, false>(eo, codes, s_pair, g, sub, true, p, emit); },
             [&](int t, u16x2 rv, u16x2 qv) {
               int sub2 = sub; asm volatile("" : "+v"(sub2));
               const StorePlan sp = store_plan<K>(g, sub2, L.active);
@@ -1429,7 +1226,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
     }
     bool bad = false;
     product(ValU16x3m{fq + row, p, q - 1}, gg, q - 1,
-            [&](auto s_pair, auto emit) { tern_product_split<K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
+            [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
             [&](int t, u16x2 rv, u16x2 qv) {
               int sub2 = sub; asm volatile("" : "+v"(sub2));
               rv = rv & (u16)(q - 1);
@@ -1484,22 +1281,22 @@ static int plan(const ntru_engine *eng, int N, long B, int shared_eo, bool per_i
 }
 
 // The add path needs one item per wave, 2K step bits in half a dword (K <= 7) and at least K values below q fitting
-// a 16-bit field on top of a masked one.  Returns the mask interval ME (2K: once per block, K: twice) or 0.
-static int add_path_me(const ntru_engine *eng, int N, int q) {
+// a 16-bit field on top of a masked one.  Returns the mask interval ME (2K: once per block, K: twice) or 0.  Leaves
+// the launch geometry in L->K and L->g: the caller sizes its LDS from it and hands the byte counts to plan_add().
+static int add_path_me(const ntru_engine *eng, int N, int q, Launch *L) {
   if (eng->path == 1) return 0;
   int K = pick_K(N);
   if (!K || K > 7) return 0;
-  Geom g = make_geom(N, K);
-  if (g.G != 1) return 0;
+  L->K = K;
+  L->g = make_geom(N, K);
+  if (L->g.G != 1) return 0;
   long limit = 65535 / (q - 1) - 1;          // additions of values < q allowed on a masked field
   if (limit >= 2 * K) return 2 * K;
   if (limit >= K) return K;
   return 0;
 }
 
-static int plan_add(const ntru_engine *eng, int N, long B, size_t shared_bytes, size_t per_wave_bytes, Launch *L) {
-  L->K = pick_K(N);
-  L->g = make_geom(N, L->K);
+static int plan_add(long B, size_t shared_bytes, size_t per_wave_bytes, Launch *L) {
   L->lds = shared_bytes + WAVES_PER_BLOCK * per_wave_bytes;
   if (L->lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "parameter set needs more than 160 KiB of LDS");
   L->blocks = (B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
@@ -1561,9 +1358,8 @@ static int shared_path_K(const ntru_engine *eng, int N, int q, int p, int *me) {
 int ntru_launch_encrypt_valu(ntru_engine *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint8_t *d_m, int64_t B,
                              uint16_t *d_e, uint16_t *d_quotE) {
   Launch L;
-  if (const int me = add_path_me(eng, N, q)) {
-    Geom g0 = make_geom(N, pick_K(N));
-    if (int rc = plan_add(eng, N, B, (size_t)g0.eo_len * 8, (size_t)g0.nl * 4, &L)) return rc;
+  if (const int me = add_path_me(eng, N, q, &L)) {
+    if (int rc = plan_add(B, (size_t)L.g.eo_len * 8, (size_t)L.g.nl * 4, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
       note_kernel(eng, "k_encrypt_t", KK, MM);
       return launch_resident(eng, k_encrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
@@ -1599,10 +1395,9 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
       });
     }
   }
-  if (const int me = (p == 3 && eng->path == 2) ? add_path_me(eng, N, q) : 0) {   // per-item stepping: only when forced
-    Geom g0 = make_geom(N, pick_K(N));
-    if (int rc = plan_add(eng, N, B, (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4,
-                          (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4, &L)) return rc;
+  if (const int me = (p == 3 && eng->path == 2) ? add_path_me(eng, N, q, &L) : 0) {   // per-item stepping: only when forced
+    if (int rc = plan_add(B, (size_t)L.g.eo_len * 8 + (size_t)L.g.nl * 4,
+                          (size_t)L.g.eo_len * 8 + (size_t)L.g.nl * 4, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
       note_kernel(eng, "k_decrypt_t", KK, MM);
       return launch_resident(eng, k_decrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
@@ -1643,10 +1438,9 @@ int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int p, const in
                                  const uint8_t *d_fp, const uint16_t *d_h, int64_t B, uint16_t *d_quot_fq, uint16_t *d_rem_fq,
                                  uint8_t *d_quot_fp, uint8_t *d_rem_fp, uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags) {
   Launch L;
-  if (const int me = p == 3 ? add_path_me(eng, N, q) : 0) {
-    Geom g0 = make_geom(N, pick_K(N));
+  if (const int me = p == 3 ? add_path_me(eng, N, q, &L) : 0) {
     const size_t raw_len = ((size_t)N + 1) & ~(size_t)1;
-    if (int rc = plan_add(eng, N, B, 0, (size_t)g0.eo_len * 8 + (size_t)g0.nl * 4 + raw_len * 2, &L)) return rc;
+    if (int rc = plan_add(B, 0, (size_t)L.g.eo_len * 8 + (size_t)L.g.nl * 4 + raw_len * 2, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
       note_kernel(eng, "k_verify_keys_t", KK, MM);
       return launch_resident(eng, k_verify_keys_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_g, d_fq, d_fp, d_h,
