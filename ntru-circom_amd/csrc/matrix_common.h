@@ -33,8 +33,10 @@ struct MGeom {
 };
 
 // M_DEC1: product 1 of decrypt, the 64 f plane derived from the f fragment; M_DEC1T: the same product with the 64 f plane read
-// from a reversed key array of its own (tb1), as M_ENC reads its second plane.
-enum { M_ENC = 0, M_DEC1 = 1, M_DEC2 = 2, M_DEC1T = 3 };
+// from a reversed key array of its own (tb1), as M_ENC reads its second plane.  M_DEC2P: product 2 of decrypt with the batch operand
+// read from the 2-bit packed image [row group][column] (4 rows per byte) instead of a byte stage: st0 = this lane's row group
+// (+ 16 bytes for the upper half-wave; the four lanes of a row group read one address), ash = 2 (row & 3) picks the lane's field.
+enum { M_ENC = 0, M_DEC1 = 1, M_DEC2 = 2, M_DEC1T = 3, M_DEC2P = 4 };
 
 // -DNTRU_STAMPS: diagnostic build that records s_memtime at the phase boundaries of the matrix-core kernels for the
 // first row blocks of each workgroup (tools/phase_stamps.py reads them back); no stamp executes in the shipped library.
@@ -98,8 +100,8 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
                                                       const u32 *__restrict__ tb0, const u32 *__restrict__ tb1,
                                                       const MGeom &g, int kb0, const u32 (&mlow)[4], Epi epi,
                                                       int stamp_iter = 0, int stamp_base = 0, int pause_ib = 0x7fffffff,
-                                                      Pause pause = Pause(), Diag diag = Diag()) {
-  constexpr bool TWO = MODE != M_DEC2;
+                                                      Pause pause = Pause(), Diag diag = Diag(), int ash = 0) {
+  constexpr bool TWO = MODE != M_DEC2 && MODE != M_DEC2P;
   // The accumulators are never zeroed: the first matrix instruction of each takes the inline constant 0 as its C operand
   // (accL: contraction step 0, peeled below; accH: its own diagonal sub-step) -- 2 x 16 x NT_S moves per strip less.
   v16i accL[NT_S], accH[NT_S];
@@ -128,6 +130,15 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
       a1 = a0;
     }
   };
+  // M_DEC2P: what load_a returned is still packed; the field is taken out when the fragment becomes the current one, so that the
+  // read has a step's matrix instructions to land behind
+  auto unpack_a = [&](v4i &a0, v4i &a1) {
+    if (MODE == M_DEC2P) {
+#pragma unroll
+      for (int c = 0; c < 4; c++) a0[c] = (int)(((u32)a0[c] >> ash) & 0x03030303u);
+      a1 = a0;
+    }
+  };
   auto mm = [&](v16i &acc, v4i a0, v4i a1, v4i w0, v4i w1) {
     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, w0, acc, 0, 0, 0);
     if (TWO) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, w1, acc, 0, 0, 0);
@@ -148,6 +159,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
   for (int c = 0; c < 4; c++) mhigh[c] = ~mlow[c];
   v4i a0, a1;
   load_a(0, a0, a1);
+  unpack_a(a0, a1);
   // kind: 0 = all tiles low, 1 = all high, 2 = the strip's own (diagonal) steps
   auto block = [&](int ib, auto kind) {
 #pragma unroll
@@ -171,6 +183,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
       load_w(kb0 - (ib + u + 1), W0[(NT_S - 1 - u) % NT_S], W1[(NT_S - 1 - u) % NT_S]);
       if (decltype(kind)::value == 2) diag(u);
       a0 = n0; a1 = n1;
+      unpack_a(a0, a1);
     }
   };
   auto single = [&](int ib, v16i (&acc)[NT_S]) {
@@ -182,11 +195,12 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
     for (int t = NT_S - 1; t > 0; t--) { W0[t] = W0[t - 1]; W1[t] = W1[t - 1]; }
     load_w(kb0 - (ib + 1), W0[0], W1[0]);
     a0 = n0; a1 = n1;
+    unpack_a(a0, a1);
   };
   int ib = 0;
   bool paused = false;
   if (kb0 > 0 && g.NT > 0) {                              // contraction step 0: the first term of every `low`
-    if (!std::is_same<Pause, NoPause>::value && pause_ib <= 0) { pause(); paused = true; load_a(0, a0, a1); }
+    if (!std::is_same<Pause, NoPause>::value && pause_ib <= 0) { pause(); paused = true; load_a(0, a0, a1); unpack_a(a0, a1); }
     v4i n0, n1;
     load_a(1, n0, n1);
 #pragma unroll
@@ -195,6 +209,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
     for (int t = NT_S - 1; t > 0; t--) { W0[t] = W0[t - 1]; W1[t] = W1[t - 1]; }
     load_w(kb0 - 1, W0[0], W1[0]);
     a0 = n0; a1 = n1;
+    unpack_a(a0, a1);
     ib = 1;
   } else {                                               // the diagonal block comes first (or a timing-only build)
 #pragma unroll
@@ -209,6 +224,7 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
       __builtin_amdgcn_s_setprio(3);
       paused = true;
       load_a(first, a0, a1);                             // it was requested before the pause: read it again
+      unpack_a(a0, a1);
     }
   };
   __builtin_amdgcn_s_setprio(3);       // the partner wave on this SIMD is usually in a VALU phase: decrypt -3 %

@@ -6,15 +6,21 @@
 
 // decryptBits on the matrix cores.  Product 1: a = f * e, e = lo7 + 128 hi (both digits non-negative, q <= 8192), planes
 // [e_lo | 2 e_hi] x [f ; 64 f]; centred lift (index.js:117 verbatim); product 2: c = fp * lifted, one plane.  The lifted
-// message goes from the accumulator layout (column per lane) to the operand stage (row per lane) through a 2-bit packed
-// LDS image [column][8 bytes] and one expansion pass.
-// GROUPS = 1: one workgroup = four waves = one row block at a time, two workgroups per CU (k_decrypt_m).
+// message goes from the accumulator layout (column per lane) to the operand layout (row per lane) through a 2-bit packed
+// LDS image [8 row groups][columns] (4 rows per byte).
+// GROUPS = 1: one workgroup = four waves = one row block at a time, two workgroups per CU (k_decrypt_m); one pass expands the
+// image into the byte stage that product 2 reads.
 // GROUPS = 2 (k_decrypt_m8): ONE workgroup of eight waves per CU = two groups of four, each with its own row blocks, stages and
 // packed image, sharing the key arrays, the lift table and the mod-p tables.  Every matrix loop and every epilogue is a PHASE between two
 // workgroup barriers, and group 1 runs one phase behind group 0: while one group's waves are in their matrix loops, the
 // other group's waves (their partners on the SIMDs) are in an epilogue / staging phase, by construction instead of by
-// luck.  Phases per row block: stage, then (loop, epilogue) per strip and product, with the image expansion between the
-// products: 10 at N = 821 -- an even number, so the two groups stay in opposite phases.
+// luck.  Product 2 reads its batch operand from the packed image itself (M_DEC2P: the 2-bit field is shifted out in the loop), so
+// there is no expansion phase.  Phases per row block: stage, then (loop, epilogue) per strip and product:
+//     S  L E  L E  L E  L E      (9 at N = 821; S L E L E where a product is one round of strips)
+// An odd period whose phases alternate between a loop and something else: with group 1 one phase behind, every slot pairs a loop
+// of one group with an epilogue or the staging of the other, except the one slot (S, E) per period in which neither is in a loop.
+// (Staging the NEXT row block during product 2 removes that slot too and measured slower: EXPERIMENTS.md, "Lock-step decrypt:
+// product 2 from the packed image".)
 // PACK (k_decrypt_mp): packOutput(p - 1, N, value) (index.js:572-596: 2 bits per value, 126 values per 252-bit field element, four
 // little-endian 64-bit limbs per element) comes out of the same kernel: product 2's epilogue drops its values into a 2-bit packed
 // LDS image [8 row groups][columns] (4 rows per byte -- the layout product 1 uses for the lifted message: one ds_write_b8 per four
@@ -241,7 +247,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
     STAMP(8);
     if (PACK) pack_wipe();
     if (GROUPS == 1) build_m3(tid0, BLOCK_THREADS, N);     // the e stages are dead: the tables go over the e_hi stage
-    {   // packed image -> byte stage: all of a wave's reads in flight before the first write (as a read-write loop this
+    if (GROUPS == 1) {   // packed image -> byte stage: all of a wave's reads in flight before the first write (as a read-write loop this
         // pass was one LDS round trip per dword: 7 k cycles per row block in the phase stamps)
       constexpr int RPW = 32 / WAVES_PER_BLOCK;
       u32 pv[RPW][4];
@@ -261,9 +267,14 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
       }
     }
     STAMP(9);
-    __syncthreads();
+    if (GROUPS == 1) __syncthreads();
     STAMP(10);
     // ---- product 2: c = fp * lifted mod p
+    // GROUPS = 2 reads the batch operand straight from the packed image: lane (row, half) reads the 16 columns of its row group
+    // (one 16-byte aligned address in the four lanes of a row group: an LDS broadcast) and shifts its own 2-bit field out.
+    constexpr int P2 = GROUPS == 2 ? M_DEC2P : M_DEC2;
+    const unsigned char *a2 = GROUPS == 2 ? blp + ((lane & 31) >> 2) * 32 * g.NT + 16 * (lane >> 5) : st0;
+    const int ash = 2 * (lane & 3);
     sidx = 0;
     for_each_strip<4>(g.NT, GROUPS == 2 ? wave ^ (2 * group) ^ (2 * blockIdx.x >= gridDim.x ? 2 : 0) : wave, [&](int kb0, int nt) {
       auto epi = [&](auto &lo, auto &hi) {
@@ -314,10 +325,10 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
       };
       switch (nt) {
         case 0: phase(); break;                          // no strip this round: keep the phases in step
-        case 1: toeplitz_strip<M_DEC2, 1>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
-        case 2: toeplitz_strip<M_DEC2, 2>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
-        case 3: toeplitz_strip<M_DEC2, 3>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
-        default: toeplitz_strip<M_DEC2, 4>(st0, st0, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx); break;
+        case 1: toeplitz_strip<P2, 1>(a2, a2, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx, 0x7fffffff, NoPause(), NoDiag(), ash); break;
+        case 2: toeplitz_strip<P2, 2>(a2, a2, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx, 0x7fffffff, NoPause(), NoDiag(), ash); break;
+        case 3: toeplitz_strip<P2, 3>(a2, a2, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx, 0x7fffffff, NoPause(), NoDiag(), ash); break;
+        default: toeplitz_strip<P2, 4>(a2, a2, tbp, tbp, g, kb0, mlow, epi, stamp_iter, 11 + 2 * sidx, 0x7fffffff, NoPause(), NoDiag(), ash); break;
       }
       sidx++;
       if (sidx < rounds) phase();                        // epilogue | next matrix loop

@@ -67,8 +67,9 @@ eng.set_kernel_path(5)
 for _ in range(2):
     eng.decrypt_batch_dev(N, q, 3, f.data_ptr(), fp.data_ptr(), e.data_ptr(), B, v.data_ptr(), q1.data_ptr(), r1.data_ptr(), q2.data_ptr())
 st = read("dec")
+# (no expansion phase: product 2 reads the packed image)
 lab8 = [(0, 1, "wait b1"), (1, 2, "stage"), (2, 3, "wait b2"), (3, 4, "P1 loops s1"), (4, 5, "P1 (phase barrier) epi s1"), (5, 6, "(barrier) P1 loops s2"),
-        (6, 7, "P1 (barrier) epi s2"), (7, 8, "wait b3"), (8, 9, "expand"), (9, 10, "wait b4"), (10, 11, "P2 loops s1"), (11, 12, "P2 (barrier) epi s1"),
+        (6, 7, "P1 (barrier) epi s2"), (7, 8, "wait b3"), (10, 11, "P2 loops s1"), (11, 12, "P2 (barrier) epi s1"),
         (12, 13, "(barrier) P2 loops s2"), (13, 14, "P2 (barrier) epi s2")]
 report("k_decrypt_m8 group 0", st, lab8, 256, slice(0, 4))
 report("k_decrypt_m8 group 1", st, lab8, 256, slice(4, 8))
