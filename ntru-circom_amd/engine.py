@@ -1,5 +1,7 @@
 """ctypes binding of include/ntru_engine.h (the engine's C ABI).  No computation happens here."""
+import collections
 import ctypes as C
+import linecache
 import os
 
 import numpy as np
@@ -30,81 +32,168 @@ def library_path():
     return os.environ.get("NTRU_ENGINE_LIB") or os.path.join(_HERE, "lib", "libntru_engine.so")
 
 
-_vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
+# ---- the C prototypes, one letter per argument in the header's order: the whole ctypes vocabulary of this file --------------
+_vp = C.c_void_p
+_CT = {"p": _vp, "i": C.c_int, "l": C.c_int64, "u": C.c_uint64, "z": C.c_size_t, "s": C.c_char_p, "-": None,
+       "P": C.POINTER(_vp), "I": C.POINTER(C.c_int), "Z": C.POINTER(C.c_size_t)}
+
+
+def _sig(args, res="i"):
+    """(restype, argtypes) of a prototype: p pointer (engine handles included), i int, l int64_t, u uint64_t, z size_t,
+    s const char *, P / I / Z pointer to void * / int / size_t, - void; blanks only group."""
+    return _CT[res], [_CT[c] for c in args.replace(" ", "")]
+
+
+def _both(name, args):
+    """The host-pointer and the _dev form of one prototype."""
+    return {name: _sig(args), name + "_dev": _sig(args)}
+
+
+# the calls that are written out by hand below
 _SIGS = {
-    "ntru_engine_device_count": (C.c_int, []),
-    "ntru_engine_create": (C.c_int, [_i, C.POINTER(_vp)]),
-    "ntru_engine_destroy": (None, [_vp]),
-    "ntru_engine_set_stream": (C.c_int, [_vp, _vp]),
-    "ntru_engine_synchronize": (C.c_int, [_vp]),
-    "ntru_engine_set_kernel_path": (C.c_int, [_vp, _i]),
-    "ntru_engine_last_kernel": (C.c_char_p, [_vp]),
-    "ntru_last_error": (C.c_char_p, []),
-    "ntru_engine_supports": (C.c_int, [_i, _i]),
+    "ntru_engine_device_count": _sig(""),
+    "ntru_engine_create": _sig("i P"),
+    "ntru_engine_destroy": _sig("p", "-"),
+    "ntru_engine_set_stream": _sig("p p"),
+    "ntru_engine_synchronize": _sig("p"),
+    "ntru_engine_set_kernel_path": _sig("p i"),
+    "ntru_engine_last_kernel": _sig("p", "s"),
+    "ntru_last_error": _sig("", "s"),
+    "ntru_engine_supports": _sig("i i"),
+    "ntru_engine_set_sampler_rounds": _sig("p i"),
+    "ntru_engine_get_sampler_rounds": _sig("p"),
+    **_both("ntru_sample_ternary", "p iiii p u l p"),
+    "ntru_pack_params": _sig("i i IIII"),
+    **_both("ntru_pack_batch", "p ii p l p"),
+    **_both("ntru_unpack_batch", "p ii p i l p"),
+    "ntru_pack_bytes_batch_dev": _sig("p ii p l p"),
+    "ntru_pipeline_batch": _sig("p iii pppp u ii pp l pppp"),
+    "ntru_pipeline_bytes_batch": _sig("p iii pppp u ii p i p l pppp"),
+    "ntru_dev_alloc": _sig("p z P"),
+    "ntru_dev_free": _sig("p p"),
+    "ntru_dev_upload": _sig("p p p z"),
+    "ntru_dev_download": _sig("p p p z"),
+    "ntru_host_alloc": _sig("z", "p"),
+    "ntru_host_free": _sig("p", "-"),
+    "ntru_generic_capacity": _sig("i i"),
+    "ntru_generic_multiply": _sig("p ii l pp l pp"),
+    "ntru_generic_divide": _sig("p ii l pp l ppppp"),
+    "ntru_generic_eea": _sig("p ii l pp l ppppp"),
+    "ntru_generic_poly_inv": _sig("p ii l pp l ppp"),
+    "ntru_multi_create": _sig("p i P"),
+    "ntru_multi_destroy": _sig("p", "-"),
+    "ntru_multi_engines": _sig("p"),
+    **_both("ntru_sum_groups", "p ii ppp ll p"),
+    **_both("ntru_tally_decrypt_batch", "p iii ppppp ll ppppp"),
+    "ntru_keygen_workspace_bytes": _sig("i l Z"),
+    **_both("ntru_keygen_batch", "p iiiii p u i l pppppppp"),
 }
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_public_key_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp])
-    _SIGS["ntru_invert_key_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp])
-_SIGS["ntru_engine_set_sampler_rounds"] = (C.c_int, [_vp, _i])
-_SIGS["ntru_engine_get_sampler_rounds"] = (C.c_int, [_vp])
-_SIGS["ntru_sample_ternary"] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, C.c_uint64, _i64, _vp])
-_SIGS["ntru_sample_ternary_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, C.c_uint64, _i64, _vp])
-_ip = C.POINTER(C.c_int)
-_SIGS["ntru_pack_params"] = (C.c_int, [_i, _i, _ip, _ip, _ip, _ip])
-_SIGS["ntru_decrypt_pack_batch_dev"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_encrypt_pack_batch_dev"] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_pack_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp])
-    _SIGS["ntru_unpack_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i, _i64, _vp])
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_polymul_split" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_split_by_I" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_add_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _i64, _vp])
-    _SIGS["ntru_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
-    _SIGS["ntru_encrypt_peritem_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_decrypt_peritem_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
-    _SIGS["ntru_verify_keys_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64] + [_vp] * 7)
-_SIGS["ntru_pack_bytes_batch_dev"] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp])
-_SIGS["ntru_pipeline_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
-_SIGS["ntru_dev_alloc"] = (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)])
-_SIGS["ntru_dev_free"] = (C.c_int, [_vp, _vp])
-_SIGS["ntru_dev_upload"] = (C.c_int, [_vp, _vp, _vp, C.c_size_t])
-_SIGS["ntru_dev_download"] = (C.c_int, [_vp, _vp, _vp, C.c_size_t])
-_SIGS["ntru_host_alloc"] = (C.c_void_p, [C.c_size_t])
-_SIGS["ntru_host_free"] = (None, [_vp])
-_SIGS["ntru_generic_capacity"] = (C.c_int, [_i, _i])
-_SIGS["ntru_generic_multiply"] = (C.c_int, [_vp, _i, _i, _i64, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_generic_divide"] = (C.c_int, [_vp, _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp])
-_SIGS["ntru_generic_eea"] = (C.c_int, [_vp, _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp])
-_SIGS["ntru_generic_poly_inv"] = (C.c_int, [_vp, _i, _i, _i64, _vp, _vp, _i64, _vp, _vp, _vp])
-_SIGS["ntru_multi_create"] = (C.c_int, [_vp, _i, C.POINTER(_vp)])
-_SIGS["ntru_multi_destroy"] = (None, [_vp])
-_SIGS["ntru_multi_engines"] = (C.c_int, [_vp])
-_SIGS["ntru_multi_encrypt_batch"] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_multi_decrypt_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
-_SIGS["ntru_multi_verify_keys_batch"] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64] + [_vp] * 7)
-_SIGS["ntru_multi_polymul_split"] = (C.c_int, [_vp, _i, _i, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_multi_invert_key_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _i64, _vp, _vp, _vp])
-_SIGS["ntru_multi_public_key_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp])
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_check_encrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _vp])
-    _SIGS["ntru_check_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _i] + [_vp] * 7 + [_i64, _vp])
-    _SIGS["ntru_check_inverse_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 4 + [_i64, _vp])
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_sum_groups" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _i64, _i64, _vp])
-    _SIGS["ntru_tally_decrypt_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i] + [_vp] * 5 + [_i64, _i64] + [_vp] * 5)
-for _sfx in ("", "_dev"):
-    _SIGS["ntru_bytes_to_rows" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp])
-    _SIGS["ntru_rows_to_bytes" + _sfx] = (C.c_int, [_vp, _i, _i, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_encrypt_bytes_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-    _SIGS["ntru_decrypt_bytes_batch" + _sfx] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_pipeline_bytes_batch"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp])
-_SIGS["ntru_keygen_workspace_bytes"] = (C.c_int, [_i, _i64, C.POINTER(C.c_size_t)])
-_SIGS["ntru_keygen_batch_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
-_SIGS["ntru_keygen_batch"] = (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, C.c_uint64, _i, _i64] + [_vp] * 8)
-_SIGS["ntru_encrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp])
-_SIGS["ntru_decrypt_batch_pitched_dev"] = (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp])
+
+# ---- the regular batch calls, one row each ---------------------------------------------------------------------------------
+# A regular call is  ntru_<name>(engine, scalars..., arrays with the batch count B among them).  From its row come the prototypes
+# of its forms (_SIGS), the Engine host method (numpy arrays in and out), the Engine <name>_dev method (device pointers, plus
+# its launch-log record) and the MultiEngine method (the ntru_multi_ symbol).  _derive() compiles them once, at import; print
+# _host_source(row, "ntru_") / _dev_source(row) to read a method.
+_Arr = collections.namedtuple("_Arr", "role name dt n want host blocks")
+_Call = collections.namedtuple("_Call", "name scalars args forms note mismatch ret pitched doc dev_doc")
+_B = None                # the place of the batch count (int64_t B) among the arrays
+_i8, _u8, _u16, _u64 = np.int8, np.uint8, np.uint16, np.uint64
+
+
+def _key(name, dt):
+    """Shared input of shape (N,): a key every item uses."""
+    return _Arr("key", name, dt, "N", None, name, False)
+
+
+def _in(name, dt, n="N", host=None, blocks=False):
+    """Per-item input [B][n], n an expression in the scalars; host: its name in the host method where that differs from d_<name>;
+    blocks: message bytes, which may also come as a bytes object (_blocks)."""
+    return _Arr("in", name, dt, n, None, host or name, blocks)
+
+
+def _out(name, dt, n="N", want=None):
+    """Output [B][n] ([B] with n None).  want: the keyword of the host method that gates an optional output; in the _dev method
+    the pointer may then be None, and defaults to None where no required parameter follows."""
+    return _Arr("out", name, dt, n, want, name, False)
+
+
+def _call(name, scalars, *args, forms="host dev", note="sum", mismatch=None, ret=tuple, pitched=False, doc=None, dev_doc=None):
+    """scalars: the int parameters after the engine, by name.  forms: which of host / dev / multi exist.  note: the bytes per item of
+    the _dev method's launch-log record: "sum" = the row bytes of the per-item arrays passed, None = no record, else the expression.
+    mismatch: the message (an expression) of the ValueError when per-item inputs differ in rows; unchecked without.  ret: dict returns
+    the outputs by name.  pitched: ntru_<name>_pitched_dev exists (int ld after the scalars), selected by the _dev method's ld=."""
+    return _Call(name, scalars.split(), args, forms.split(), note, mismatch, ret, pitched, doc, dev_doc)
+
+
+_MSG = _in("bytes", _u8, "nbytes", host="data", blocks=True)
+_WITNESS = (_out("quot1", _u16, want="want_witness"), _out("rem1", _u16, want="want_witness"), _out("quot2", _u8, want="want_witness"))
+_CALLS = [
+    _call("polymul_split", "N mod", _in("a", _u16), _in("b", _u16), _B, _out("quot", _u16), _out("rem", _u16), forms="host dev multi"),
+    _call("split_by_I", "N mod", _in("a", _u16, "2 * N"), _B, _out("quot", _u16), _out("rem", _u16), note=None),
+    _call("add_batch", "N mod", _in("a", _u16), _in("b", _u16), _B, _out("out", _u16), note=None),
+    _call("encrypt_batch", "N q", _key("h", _u16), _in("r", _u8), _in("m", _u8), _B, _out("e", _u16),
+          _out("quotE", _u16, want="want_quot"), forms="host dev multi", pitched=True,           # SURVEY.md 8(d): r, m in; e (+ quotientE) out
+          dev_doc="ld: row pitch of r, m, e, quotE in elements (None = dense rows of N; see ntru_encrypt_batch_pitched_dev)."),
+    _call("decrypt_batch", "N q p", _key("f", _i8), _key("fp", _u8), _in("e", _u16), _B, _out("value", _u8), *_WITNESS,
+          forms="host dev multi", pitched=True,
+          dev_doc="ld: row pitch of e, value, quot1, rem1, quot2 in elements (None = dense rows of N)."),
+    # byte messages as packed bits (include/ntru_engine.h "byte messages"): blocks of nbytes <= N // 8 bytes, bit 7 first
+    _call("bytes_to_rows", "N nbytes", _MSG, _B, _out("m", _u8),
+          doc="[B][nbytes] message bytes -> [B][N] coefficient rows (stringToBits per block, zero pad)."),
+    _call("rows_to_bytes", "N nbytes", _in("value", _u8), _B, _out("bytes", _u8, "nbytes"), _out("flags", _u8, None, want="want_flags"),
+          doc="[B][N] rows -> ([B][nbytes] bytes of the low bits, [B] flags: FLAG_NOT_BITS | FLAG_PAD_NONZERO, or None)."),
+    _call("encrypt_bytes_batch", "N q nbytes", _key("h", _u16), _in("r", _u8), _MSG, _B, _out("e", _u16),
+          _out("quotE", _u16, want="want_quot"), note=None,
+          mismatch='"encrypt_bytes_batch: %d rows of r for %d blocks" % (B, data.shape[0])',
+          doc="encrypt_batch on the rows of bytes_to_rows(data); only nbytes per block go up."),
+    _call("decrypt_bytes_batch", "N q p nbytes", _key("f", _i8), _key("fp", _u8), _in("e", _u16), _B, _out("bytes", _u8, "nbytes"),
+          _out("flags", _u8, None, want="want_flags"), note=None,
+          doc="rows_to_bytes of the value-only decrypt_batch; only nbytes (+ 1 flag byte) per block come down.  Returns (bytes, flags)."),
+    _call("encrypt_peritem_batch", "N q", _in("h", _u16), _in("r", _u8), _in("m", _u8), _B, _out("e", _u16),
+          _out("quotE", _u16, want="want_quot"), mismatch='"encrypt_peritem_batch: h, r and m need the same number of rows"',
+          doc="encrypt_batch with a separate public key per item: h, r, m are [B][N]; row b of e / quotE is encrypt_batch of row b "
+              "under h[b].", dev_doc="d_h: [B][N] public keys, one per item."),
+    _call("decrypt_peritem_batch", "N q p", _in("f", _i8), _in("fp", _u8), _in("e", _u16), _B, _out("value", _u8), *_WITNESS,
+          mismatch='"decrypt_peritem_batch: f, fp and e need the same number of rows"',
+          doc="decrypt_batch with a separate private key per item: f, fp, e are [B][N]; row b is decrypt_batch of e[b] under f[b], fp[b].",
+          dev_doc="d_f, d_fp: [B][N] private keys, one per item."),
+    _call("verify_keys_batch", "N q p", _in("f", _i8), _in("g", _i8), _in("fq", _u16), _in("fp", _u8), _in("h", _u16), _B,
+          _out("quot_fq", _u16), _out("rem_fq", _u16), _out("quot_fp", _u8), _out("rem_fp", _u8), _out("quot_h", _u16),
+          _out("rem_h", _u16), _out("flags", _u8, None), forms="host dev multi", ret=dict,
+          note="17 * N"),                      # the five operands and six witness rows; the flags byte was never counted
+    _call("public_key_batch", "N q p", _in("fq", _u16), _in("g", _i8), _B, _out("h", _u16), forms="host dev multi",
+          doc="generatePublicKeyH for B keys: rows of (p*fq mod q) * g mod (x^N - 1, q), untrimmed."),
+    _call("invert_key_batch", "N q p", _in("f", _i8), _B, _out("fq", _u16, want="want_fq"), _out("fp", _u8, want="want_fp"),
+          _out("flags", _u8, None), note=None,
+          doc="loadPrivateKeyF / polyInv for B keys: (fq [B][N] u16, fp [B][N] u8, flags [B]); a set flag = not a unit.  "
+              "want_fq / want_fp = False skips that half (its array comes back as None)."),
+    # MultiEngine's form always computes both inverses
+    _call("invert_key_batch", "N q p", _in("f", _i8), _B, _out("fq", _u16), _out("fp", _u8), _out("flags", _u8, None), forms="multi"),
+    # witness checks (VerifyEncrypt / VerifyDecrypt / VerifyInverse): uint16 rows [B][N] and [B][N + 1] -> flags uint8[B]
+    _call("check_encrypt_batch", "N q nq", _in("r", _u16), _in("m", _u16), _in("h", _u16), _in("quotE", _u16, "N + 1"),
+          _in("remE", _u16, "N + 1"), _B, _out("flags", _u8, None)),
+    _call("check_decrypt_batch", "N q nq p np_", _in("f", _u16), _in("fp", _u16), _in("e", _u16), _in("quot1", _u16, "N + 1"),
+          _in("rem1", _u16, "N + 1"), _in("quot2", _u16, "N + 1"), _in("rem2", _u16, "N + 1"), _B, _out("flags", _u8, None)),
+    _call("check_inverse_batch", "N M n", _in("f", _u16), _in("fq", _u16), _in("quotI", _u16, "N + 1"), _in("remI", _u16, "N + 1"),
+          _B, _out("flags", _u8, None)),
+    # scheme kernel + packOutput in one call.  A packed row is packOutput's output_size field elements of 32 bytes, which follows
+    # from the value range (p - 1, q - 1) and is none of the row lengths above: the records spell it out (decrypt's for p = 3)
+    _call("decrypt_pack_batch", "N q p", _key("f", _i8), _key("fp", _u8), _in("e", _u16), _B, _out("value", _u8),
+          _out("packed", _u64, "4 * output_size"), forms="dev",
+          note="2 * N + 32 * max(3, -(-N // 126)) + (N if d_value else 0)",                   # e in; packed rows (+ the plain values) out
+          dev_doc="decryptBits + packOutput(p - 1, N, value) (one kernel on the matrix path); d_value may be None there."),
+    _call("encrypt_pack_batch", "N q", _key("h", _u16), _in("r", _u8), _in("m", _u8), _B, _out("e", _u16),
+          _out("packed", _u64, "4 * output_size"), forms="dev",                                            # r, m in; packed rows (+ e) out
+          note="2 * N + 32 * max(3, -(-N // (252 // max(1, (q - 1).bit_length())))) + (2 * N if d_e else 0)",
+          dev_doc="encryptBits + packOutput(q - 1, N, e) (one kernel with d_e None where the row-image matrix kernel applies)."),
+]
+for _c in _CALLS:
+    _args = "p" + "i" * len(_c.scalars) + "".join("l" if a is _B else "p" for a in _c.args)
+    _SIGS.update({"ntru_" + _c.name + ("_dev" if f == "dev" else ""): _sig(_args) for f in _c.forms if f != "multi"})
+    if "multi" in _c.forms:
+        _SIGS["ntru_multi_" + _c.name] = _sig(_args)
+    if _c.pitched:
+        _SIGS["ntru_%s_pitched_dev" % _c.name] = _sig(_args[:1 + len(_c.scalars)] + "i" + _args[1 + len(_c.scalars):])
 
 
 def _preload_hip_runtime():
@@ -150,9 +239,109 @@ def _ptr(arr):
     return None if arr is None else arr.ctypes.data_as(C.c_void_p)
 
 
-class Engine:
+def _blocks(a, nbytes):
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(a), np.uint8)
+    return _np(a, np.uint8).reshape(-1, nbytes)
+
+
+# ---- the methods of the table's rows, as source text compiled once ---------------------------------------------------------
+def _host_source(c, prefix):
+    """Host method of a row: coerce every input (no copy where it already is contiguous and of the dtype), B from the first per-item
+    input, allocate the outputs, call, return them."""
+    arrays = [a for a in c.args if a is not _B]
+    ins, outs = [a for a in arrays if a.role != "out"], [a for a in arrays if a.role == "out"]
+    wants = list(dict.fromkeys(a.want for a in outs if a.want))
+    items = [a.host for a in ins if a.role == "in"]
+    body = []
+    for a in ins:
+        dt = "np." + np.dtype(a.dt).name
+        body.append("%s = %s" % (a.host, "_np(%s, %s, (N,))" % (a.host, dt) if a.role == "key" else
+                                 "_blocks(%s, %s)" % (a.host, a.n) if a.blocks else "_np(%s, %s).reshape(-1, %s)" % (a.host, dt, a.n)))
+    body.append("B = %s.shape[0]" % items[0])
+    if c.mismatch:
+        body.append("if %s:" % " or ".join("%s.shape[0] != B" % x for x in items[1:]))
+        body.append("    raise ValueError(%s)" % c.mismatch)
+    for a in outs:
+        body.append("%s = np.empty(%s, np.%s)%s" % (a.name, "(B, %s)" % a.n if a.n else "B", np.dtype(a.dt).name,
+                                                  " if %s else None" % a.want if a.want else ""))
+    call = ["self._h"] + c.scalars + ["B" if a is _B else "_ptr(%s)" % a.host for a in c.args]
+    body.append("self._chk(self._lib.%s%s(%s))" % (prefix, c.name, ", ".join(call)))
+    body.append("return " + ("{%s}" % ", ".join('"%s": %s' % (a.name, a.name) for a in outs) if c.ret is dict else
+                             ", ".join(a.name for a in outs)))
+    params = ["self"] + c.scalars + [a.host for a in ins] + [w + "=True" for w in wants]
+    return "def %s(%s):\n    %s\n" % (c.name, ", ".join(params), "\n    ".join(body))
+
+
+def _dev_source(c):
+    """_dev method of a row: every pointer through _dp, then the launch-log record."""
+    params, call, fixed, optional = [], [], {}, []
+    for k, a in enumerate(c.args):
+        if a is _B:
+            params.append("B"), call.append("B")
+            continue
+        trailing = all(x is not _B and x.want for x in c.args[k:])
+        params.append("d_%s%s" % (a.name, "=None" if trailing else "")), call.append("dp(d_%s)" % a.name)
+        n = "1" if a.n is None else "(%s)" % a.n if " " in a.n else a.n
+        if a.want:
+            optional.append("(%d * %s if d_%s else 0)" % (np.dtype(a.dt).itemsize, n, a.name))
+        elif a.role != "key":
+            fixed[n] = fixed.get(n, 0) + np.dtype(a.dt).itemsize          # bytes per item of the arrays that are always passed
+    note = ["%d * %s" % (size, n) for n, size in fixed.items()] + optional
+    head = ["self._h"] + c.scalars
+    sym = "self._chk(self._lib.ntru_%s%s_dev(%s))"
+    body = ["dp = self._dp"]
+    if c.pitched:
+        params.append("ld=None")
+        body += ["if ld is None:", "    " + sym % (c.name, "", ", ".join(head + call)),
+                 "else:", "    " + sym % (c.name, "_pitched", ", ".join(head + ["int(ld)"] + call))]
+    else:
+        body.append(sym % (c.name, "", ", ".join(head + call)))
+    if c.note:
+        body.append("self._note(N, B, %s)" % (" + ".join(note) if c.note == "sum" else c.note))
+    return "def %s_dev(%s):\n    %s\n" % (c.name, ", ".join(["self"] + c.scalars + params), "\n    ".join(body))
+
+
+def _derive(cls, form):
+    """Give cls the methods of every row that has the form: host, dev or multi."""
+    for c in _CALLS:
+        if form in c.forms:
+            src = _dev_source(c) if form == "dev" else _host_source(c, "ntru_multi_" if form == "multi" else "ntru_")
+            name = c.name + ("_dev" if form == "dev" else "")
+            filename = "<%s.%s of %s>" % (cls.__name__, name, os.path.basename(__file__))
+            linecache.cache[filename] = (len(src), None, src.splitlines(True), filename)    # tracebacks and inspect show the text
+            ns = {}
+            exec(compile(src, filename, "exec"), globals(), ns)
+            fn = ns[name]
+            fn.__qualname__, fn.__doc__ = "%s.%s" % (cls.__name__, name), c.dev_doc if form == "dev" else c.doc
+            setattr(cls, name, fn)
+
+
+class _Handle:
+    """What Engine and MultiEngine share: the library, a handle from it, the error check, and the handle's release."""
+    _destroy = None          # name of the C call that frees the handle
+
+    def _chk(self, rc):
+        if rc:
+            raise EngineError(rc, self._lib.ntru_last_error().decode())
+
+    def close(self):
+        if self._h is not None:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(_Handle):
     """One engine per HIP device.  Host-buffer methods take/return numpy arrays; *_dev methods take raw
-    device pointers (ints, e.g. torch.Tensor.data_ptr()) and only enqueue work on the engine's stream."""
+    device pointers (ints, e.g. torch.Tensor.data_ptr()) and only enqueue work on the engine's stream.
+    The regular batch calls (encrypt_batch, decrypt_batch_dev, ...) are not written out here: they come from _CALLS."""
+    _destroy = "ntru_engine_destroy"
 
     def __init__(self, device=0):
         self._lib = load_library()
@@ -161,21 +350,6 @@ class Engine:
         self._chk(self._lib.ntru_engine_create(int(device), C.byref(h)))
         self._h = h
         self.device = int(device)
-
-    def _chk(self, rc):
-        if rc:
-            raise EngineError(rc, self._lib.ntru_last_error().decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.ntru_engine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- launch log (profiling aid) ----------------------------------------------------------------------------
     # NTRU_LAUNCH_LOG=<path>: every single-kernel *_dev call appends {"kernel", "N", "items", "bytes_per_item"} in launch order;
@@ -193,7 +367,7 @@ class Engine:
 
     def set_kernel_path(self, path):
         """0 auto, 1 packed-u16 MAC kernels, 2 ternary add path, 3 add path without dot8, 4 int8 matrix-core path
-        (each where applicable; same results)."""
+        (matrix cores, two workgroups per CU), 5 (matrix cores, lock-step decrypt); each where applicable, same results."""
         self._chk(self._lib.ntru_engine_set_kernel_path(self._h, int(path)))
 
     def last_kernel(self):
@@ -206,27 +380,6 @@ class Engine:
         return bool(self._lib.ntru_engine_supports(int(N), int(mod)))
 
     # ---- host buffers ------------------------------------------------------------------------------------
-    def polymul_split(self, N, mod, a, b):
-        a, b = _np(a, np.uint16).reshape(-1, N), _np(b, np.uint16).reshape(-1, N)
-        B = a.shape[0]
-        quot, rem = np.empty((B, N), np.uint16), np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_polymul_split(self._h, N, mod, _ptr(a), _ptr(b), B, _ptr(quot), _ptr(rem)))
-        return quot, rem
-
-    def split_by_I(self, N, mod, a):
-        a = _np(a, np.uint16).reshape(-1, 2 * N)
-        B = a.shape[0]
-        quot, rem = np.empty((B, N), np.uint16), np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_split_by_I(self._h, N, mod, _ptr(a), B, _ptr(quot), _ptr(rem)))
-        return quot, rem
-
-    def add_batch(self, N, mod, a, b):
-        a, b = _np(a, np.uint16).reshape(-1, N), _np(b, np.uint16).reshape(-1, N)
-        B = a.shape[0]
-        out = np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_add_batch(self._h, N, mod, _ptr(a), _ptr(b), B, _ptr(out)))
-        return out
-
     @staticmethod
     def _groups(rows, offsets, K, weights):
         """(offsets as int64 or None, K, G, weights as uint16 or None) of a sum over the rows [B][N]."""
@@ -356,79 +509,13 @@ class Engine:
     def pack_bytes_batch_dev(self, max_val, data_len, d_data, B, d_out):
         self._chk(self._lib.ntru_pack_bytes_batch_dev(self._h, int(max_val), int(data_len), self._dp(d_data), B, self._dp(d_out)))
 
-    def encrypt_batch(self, N, q, h, r, m, want_quot=True):
-        h = _np(h, np.uint16, (N,))
-        r, m = _np(r, np.uint8).reshape(-1, N), _np(m, np.uint8).reshape(-1, N)
-        B = r.shape[0]
-        e = np.empty((B, N), np.uint16)
-        quot = np.empty((B, N), np.uint16) if want_quot else None
-        self._chk(self._lib.ntru_encrypt_batch(self._h, N, q, _ptr(h), _ptr(r), _ptr(m), B, _ptr(e), _ptr(quot)))
-        return e, quot
-
-    def decrypt_batch(self, N, q, p, f, fp, e, want_witness=True):
-        f, fp = _np(f, np.int8, (N,)), _np(fp, np.uint8, (N,))
-        e = _np(e, np.uint16).reshape(-1, N)
-        B = e.shape[0]
-        value = np.empty((B, N), np.uint8)
-        q1 = np.empty((B, N), np.uint16) if want_witness else None
-        r1 = np.empty((B, N), np.uint16) if want_witness else None
-        q2 = np.empty((B, N), np.uint8) if want_witness else None
-        self._chk(self._lib.ntru_decrypt_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(value),
-                                               _ptr(q1), _ptr(r1), _ptr(q2)))
-        return value, q1, r1, q2
-
     # ---- byte messages as packed bits (include/ntru_engine.h "byte messages"): blocks of nbytes <= N // 8 bytes, bit 7 first
-    @staticmethod
-    def _blocks(a, nbytes):
-        if isinstance(a, (bytes, bytearray, memoryview)):
-            a = np.frombuffer(bytes(a), np.uint8)
-        return _np(a, np.uint8).reshape(-1, nbytes)
-
-    def bytes_to_rows(self, N, nbytes, data):
-        """[B][nbytes] message bytes -> [B][N] coefficient rows (stringToBits per block, zero pad)."""
-        data = self._blocks(data, nbytes)
-        B = data.shape[0]
-        m = np.empty((B, N), np.uint8)
-        self._chk(self._lib.ntru_bytes_to_rows(self._h, N, nbytes, _ptr(data), B, _ptr(m)))
-        return m
-
-    def rows_to_bytes(self, N, nbytes, value, want_flags=True):
-        """[B][N] rows -> ([B][nbytes] bytes of the low bits, [B] flags: FLAG_NOT_BITS | FLAG_PAD_NONZERO, or None)."""
-        value = _np(value, np.uint8).reshape(-1, N)
-        B = value.shape[0]
-        out = np.empty((B, nbytes), np.uint8)
-        flags = np.empty(B, np.uint8) if want_flags else None
-        self._chk(self._lib.ntru_rows_to_bytes(self._h, N, nbytes, _ptr(value), B, _ptr(out), _ptr(flags)))
-        return out, flags
-
-    def encrypt_bytes_batch(self, N, q, nbytes, h, r, data, want_quot=True):
-        """encrypt_batch on the rows of bytes_to_rows(data); only nbytes per block go up."""
-        h = _np(h, np.uint16, (N,))
-        r, data = _np(r, np.uint8).reshape(-1, N), self._blocks(data, nbytes)
-        B = r.shape[0]
-        if data.shape[0] != B:
-            raise ValueError("encrypt_bytes_batch: %d rows of r for %d blocks" % (B, data.shape[0]))
-        e = np.empty((B, N), np.uint16)
-        quot = np.empty((B, N), np.uint16) if want_quot else None
-        self._chk(self._lib.ntru_encrypt_bytes_batch(self._h, N, q, nbytes, _ptr(h), _ptr(r), _ptr(data), B, _ptr(e), _ptr(quot)))
-        return e, quot
-
-    def decrypt_bytes_batch(self, N, q, p, nbytes, f, fp, e, want_flags=True):
-        """rows_to_bytes of the value-only decrypt_batch; only nbytes (+ 1 flag byte) per block come down.  Returns (bytes, flags)."""
-        f, fp = _np(f, np.int8, (N,)), _np(fp, np.uint8, (N,))
-        e = _np(e, np.uint16).reshape(-1, N)
-        B = e.shape[0]
-        out = np.empty((B, nbytes), np.uint8)
-        flags = np.empty(B, np.uint8) if want_flags else None
-        self._chk(self._lib.ntru_decrypt_bytes_batch(self._h, N, q, p, nbytes, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(out), _ptr(flags)))
-        return out, flags
-
     def pipeline_bytes_batch(self, N, q, p, nbytes, h, msg, f=None, fp=None, key=None, first_item=0, n1=0, n2=0, r=None,
                              want_r=False, want_e=False, want_msg=False, want_flags=False, out=None):
         """ntru_pipeline_bytes_batch: pipeline_batch with msg [B][nbytes] in place of m and msg_out / flags in place of value.
         `out` may hold preallocated arrays (e.g. pinned_empty) under "r", "e", "msg", "flags".  Returns a dict of the outputs."""
         h = _np(h, np.uint16, (N,))
-        msg = self._blocks(msg, nbytes)
+        msg = _blocks(msg, nbytes)
         B = msg.shape[0]
         f = None if f is None else _np(f, np.int8, (N,))
         fp = None if fp is None else _np(fp, np.uint8, (N,))
@@ -445,116 +532,6 @@ class Engine:
                                                       int(n2), _ptr(r), nbytes, _ptr(msg), B, _ptr(out.get("r")), _ptr(out.get("e")),
                                                       _ptr(out.get("msg")), _ptr(out.get("flags"))))
         return out
-
-    def encrypt_peritem_batch(self, N, q, h, r, m, want_quot=True):
-        """encrypt_batch with a separate public key per item: h, r, m are [B][N]; row b of e / quotE is encrypt_batch of row b
-        under h[b]."""
-        h = _np(h, np.uint16).reshape(-1, N)
-        r, m = _np(r, np.uint8).reshape(-1, N), _np(m, np.uint8).reshape(-1, N)
-        B = r.shape[0]
-        if h.shape[0] != B or m.shape[0] != B:
-            raise ValueError("encrypt_peritem_batch: h, r and m need the same number of rows")
-        e = np.empty((B, N), np.uint16)
-        quot = np.empty((B, N), np.uint16) if want_quot else None
-        self._chk(self._lib.ntru_encrypt_peritem_batch(self._h, N, q, _ptr(h), _ptr(r), _ptr(m), B, _ptr(e), _ptr(quot)))
-        return e, quot
-
-    def decrypt_peritem_batch(self, N, q, p, f, fp, e, want_witness=True):
-        """decrypt_batch with a separate private key per item: f, fp, e are [B][N]; row b is decrypt_batch of e[b] under f[b], fp[b]."""
-        f, fp = _np(f, np.int8).reshape(-1, N), _np(fp, np.uint8).reshape(-1, N)
-        e = _np(e, np.uint16).reshape(-1, N)
-        B = e.shape[0]
-        if f.shape[0] != B or fp.shape[0] != B:
-            raise ValueError("decrypt_peritem_batch: f, fp and e need the same number of rows")
-        value = np.empty((B, N), np.uint8)
-        q1 = np.empty((B, N), np.uint16) if want_witness else None
-        r1 = np.empty((B, N), np.uint16) if want_witness else None
-        q2 = np.empty((B, N), np.uint8) if want_witness else None
-        self._chk(self._lib.ntru_decrypt_peritem_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(value),
-                                                       _ptr(q1), _ptr(r1), _ptr(q2)))
-        return value, q1, r1, q2
-
-    def verify_keys_batch(self, N, q, p, f, g, fq, fp, h):
-        f, g = _np(f, np.int8).reshape(-1, N), _np(g, np.int8).reshape(-1, N)
-        fq, h = _np(fq, np.uint16).reshape(-1, N), _np(h, np.uint16).reshape(-1, N)
-        fp = _np(fp, np.uint8).reshape(-1, N)
-        B = f.shape[0]
-        out = {"quot_fq": np.empty((B, N), np.uint16), "rem_fq": np.empty((B, N), np.uint16),
-               "quot_fp": np.empty((B, N), np.uint8), "rem_fp": np.empty((B, N), np.uint8),
-               "quot_h": np.empty((B, N), np.uint16), "rem_h": np.empty((B, N), np.uint16),
-               "flags": np.empty(B, np.uint8)}
-        self._chk(self._lib.ntru_verify_keys_batch(self._h, N, q, p, _ptr(f), _ptr(g), _ptr(fq), _ptr(fp), _ptr(h), B,
-                                                   _ptr(out["quot_fq"]), _ptr(out["rem_fq"]), _ptr(out["quot_fp"]),
-                                                   _ptr(out["rem_fp"]), _ptr(out["quot_h"]), _ptr(out["rem_h"]),
-                                                   _ptr(out["flags"])))
-        return out
-
-    def public_key_batch(self, N, q, p, fq, g):
-        """generatePublicKeyH for B keys: rows of (p*fq mod q) * g mod (x^N - 1, q), untrimmed."""
-        fq, g = _np(fq, np.uint16).reshape(-1, N), _np(g, np.int8).reshape(-1, N)
-        B = fq.shape[0]
-        h = np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_public_key_batch(self._h, N, q, p, _ptr(fq), _ptr(g), B, _ptr(h)))
-        return h
-
-    def invert_key_batch(self, N, q, p, f, want_fq=True, want_fp=True):
-        """loadPrivateKeyF / polyInv for B keys: (fq [B][N] u16, fp [B][N] u8, flags [B]); a set flag = not a unit.
-        want_fq / want_fp = False skips that half (its array comes back as None)."""
-        f = _np(f, np.int8).reshape(-1, N)
-        B = f.shape[0]
-        fq = np.empty((B, N), np.uint16) if want_fq else None
-        fp = np.empty((B, N), np.uint8) if want_fp else None
-        flags = np.empty(B, np.uint8)
-        self._chk(self._lib.ntru_invert_key_batch(self._h, N, q, p, _ptr(f), B, _ptr(fq), _ptr(fp), _ptr(flags)))
-        return fq, fp, flags
-
-    # ---- witness checks (VerifyEncrypt / VerifyDecrypt / VerifyInverse): uint16 rows [B][N] and [B][N + 1] -> flags uint8[B] ----
-    @staticmethod
-    def _rows(a, n):
-        return _np(a, np.uint16).reshape(-1, n)
-
-    def check_encrypt_batch(self, N, q, nq, r, m, h, quotE, remE):
-        r, m, h = (self._rows(x, N) for x in (r, m, h))
-        quotE, remE = self._rows(quotE, N + 1), self._rows(remE, N + 1)
-        B = r.shape[0]
-        flags = np.empty(B, np.uint8)
-        self._chk(self._lib.ntru_check_encrypt_batch(self._h, N, q, nq, _ptr(r), _ptr(m), _ptr(h), _ptr(quotE), _ptr(remE), B,
-                                                     _ptr(flags)))
-        return flags
-
-    def check_decrypt_batch(self, N, q, nq, p, np_, f, fp, e, quot1, rem1, quot2, rem2):
-        f, fp, e = (self._rows(x, N) for x in (f, fp, e))
-        quot1, rem1, quot2, rem2 = (self._rows(x, N + 1) for x in (quot1, rem1, quot2, rem2))
-        B = f.shape[0]
-        flags = np.empty(B, np.uint8)
-        self._chk(self._lib.ntru_check_decrypt_batch(self._h, N, q, nq, p, np_, _ptr(f), _ptr(fp), _ptr(e), _ptr(quot1), _ptr(rem1),
-                                                     _ptr(quot2), _ptr(rem2), B, _ptr(flags)))
-        return flags
-
-    def check_inverse_batch(self, N, M, n, f, fq, quotI, remI):
-        f, fq = self._rows(f, N), self._rows(fq, N)
-        quotI, remI = self._rows(quotI, N + 1), self._rows(remI, N + 1)
-        B = f.shape[0]
-        flags = np.empty(B, np.uint8)
-        self._chk(self._lib.ntru_check_inverse_batch(self._h, N, M, n, _ptr(f), _ptr(fq), _ptr(quotI), _ptr(remI), B, _ptr(flags)))
-        return flags
-
-    def check_encrypt_batch_dev(self, N, q, nq, d_r, d_m, d_h, d_quotE, d_remE, B, d_flags):
-        dp = self._dp
-        self._chk(self._lib.ntru_check_encrypt_batch_dev(self._h, N, q, nq, dp(d_r), dp(d_m), dp(d_h), dp(d_quotE), dp(d_remE), B,
-                                                         dp(d_flags)))
-        self._note(N, B, 6 * N + 4 * (N + 1) + 1)
-
-    def check_decrypt_batch_dev(self, N, q, nq, p, np_, d_f, d_fp, d_e, d_quot1, d_rem1, d_quot2, d_rem2, B, d_flags):
-        dp = self._dp
-        self._chk(self._lib.ntru_check_decrypt_batch_dev(self._h, N, q, nq, p, np_, dp(d_f), dp(d_fp), dp(d_e), dp(d_quot1), dp(d_rem1),
-                                                         dp(d_quot2), dp(d_rem2), B, dp(d_flags)))
-        self._note(N, B, 6 * N + 8 * (N + 1) + 1)
-
-    def check_inverse_batch_dev(self, N, M, n, d_f, d_fq, d_quotI, d_remI, B, d_flags):
-        dp = self._dp
-        self._chk(self._lib.ntru_check_inverse_batch_dev(self._h, N, M, n, dp(d_f), dp(d_fq), dp(d_quotI), dp(d_remI), B, dp(d_flags)))
-        self._note(N, B, 4 * N + 4 * (N + 1) + 1)
 
     # ---- pinned host memory ---------------------------------------------------------------------------------
     def pinned_empty(self, shape, dtype):
@@ -652,45 +629,10 @@ class Engine:
         self._chk(self._lib.ntru_keygen_batch_dev(self._h, N, q, p, df, dg, _ptr(key), int(first_item), int(max_tries), int(B), dp(d_work),
                                                   dp(d_f), dp(d_g), dp(d_fq), dp(d_fp), dp(d_h), dp(d_tries), dp(d_flags)))
 
-    def invert_key_batch_dev(self, N, q, p, d_f, B, d_fq, d_fp, d_flags):
-        dp = self._dp
-        self._chk(self._lib.ntru_invert_key_batch_dev(self._h, N, q, p, dp(d_f), B, dp(d_fq), dp(d_fp), dp(d_flags)))
-
-    def decrypt_pack_batch_dev(self, N, q, p, d_f, d_fp, d_e, B, d_value, d_packed):
-        """decryptBits + packOutput(p - 1, N, value) (one kernel on the matrix path); d_value may be None there."""
-        dp = self._dp
-        self._chk(self._lib.ntru_decrypt_pack_batch_dev(self._h, N, q, p, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_value), dp(d_packed)))
-        self._note(N, B, 2 * N + 32 * max(3, -(-N // 126)) + (N if d_value else 0))      # e in; packed rows (+ the plain values) out
-
-    def encrypt_pack_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_packed):
-        """encryptBits + packOutput(q - 1, N, e) (one kernel with d_e None where the row-image matrix kernel applies)."""
-        dp = self._dp
-        self._chk(self._lib.ntru_encrypt_pack_batch_dev(self._h, N, q, dp(d_h), dp(d_r), dp(d_m), B, dp(d_e), dp(d_packed)))
-        bits = max(1, (q - 1).bit_length())
-        self._note(N, B, 2 * N + 32 * max(3, -(-N // (252 // bits))) + (2 * N if d_e else 0))   # r, m in; packed rows (+ e) out
-
-    def public_key_batch_dev(self, N, q, p, d_fq, d_g, B, d_h):
-        dp = self._dp
-        self._chk(self._lib.ntru_public_key_batch_dev(self._h, N, q, p, dp(d_fq), dp(d_g), B, dp(d_h)))
-        self._note(N, B, 5 * N)
-
     # ---- device pointers (asynchronous) -------------------------------------------------------------------
     @staticmethod
     def _dp(x):
         return C.c_void_p(int(x)) if x else None
-
-    def polymul_split_dev(self, N, mod, d_a, d_b, B, d_quot, d_rem):
-        dp = self._dp
-        self._chk(self._lib.ntru_polymul_split_dev(self._h, N, mod, dp(d_a), dp(d_b), B, dp(d_quot), dp(d_rem)))
-        self._note(N, B, 8 * N)
-
-    def split_by_I_dev(self, N, mod, d_a, B, d_quot, d_rem):
-        dp = self._dp
-        self._chk(self._lib.ntru_split_by_I_dev(self._h, N, mod, dp(d_a), B, dp(d_quot), dp(d_rem)))
-
-    def add_batch_dev(self, N, mod, d_a, d_b, B, d_out):
-        dp = self._dp
-        self._chk(self._lib.ntru_add_batch_dev(self._h, N, mod, dp(d_a), dp(d_b), B, dp(d_out)))
 
     def sum_groups_dev(self, N, mod, d_rows, d_out, G, d_offsets=None, K=None, d_weights=None):
         """d_offsets: DEVICE int64 [G + 1], or None for uniform groups of K rows."""
@@ -704,152 +646,24 @@ class Engine:
                                                          int(K or 0), int(G), dp(d_sum), dp(d_value), dp(d_quot1), dp(d_rem1),
                                                          dp(d_quot2)))
 
-    def encrypt_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_quotE=None, ld=None):
-        """ld: row pitch of r, m, e, quotE in elements (None = dense rows of N; see ntru_encrypt_batch_pitched_dev)."""
-        dp = self._dp
-        if ld is None:
-            self._chk(self._lib.ntru_encrypt_batch_dev(self._h, N, q, dp(d_h), dp(d_r), dp(d_m), B, dp(d_e), dp(d_quotE)))
-        else:
-            self._chk(self._lib.ntru_encrypt_batch_pitched_dev(self._h, N, q, int(ld), dp(d_h), dp(d_r), dp(d_m), B,
-                                                               dp(d_e), dp(d_quotE)))
-        self._note(N, B, (6 if d_quotE else 4) * N)             # SURVEY.md 8(d): r, m in; e (+ quotientE) out
 
-    def decrypt_batch_dev(self, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1=None, d_rem1=None, d_quot2=None, ld=None):
-        """ld: row pitch of e, value, quot1, rem1, quot2 in elements (None = dense rows of N)."""
-        dp = self._dp
-        if ld is None:
-            self._chk(self._lib.ntru_decrypt_batch_dev(self._h, N, q, p, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_value),
-                                                       dp(d_quot1), dp(d_rem1), dp(d_quot2)))
-        else:
-            self._chk(self._lib.ntru_decrypt_batch_pitched_dev(self._h, N, q, p, int(ld), dp(d_f), dp(d_fp), dp(d_e), B,
-                                                               dp(d_value), dp(d_quot1), dp(d_rem1), dp(d_quot2)))
-        self._note(N, B, (3 + (2 if d_quot1 else 0) + (2 if d_rem1 else 0) + (1 if d_quot2 else 0)) * N)
-
-    def bytes_to_rows_dev(self, N, nbytes, d_bytes, B, d_m):
-        dp = self._dp
-        self._chk(self._lib.ntru_bytes_to_rows_dev(self._h, N, nbytes, dp(d_bytes), B, dp(d_m)))
-        self._note(N, B, N + nbytes)
-
-    def rows_to_bytes_dev(self, N, nbytes, d_value, B, d_bytes, d_flags=None):
-        dp = self._dp
-        self._chk(self._lib.ntru_rows_to_bytes_dev(self._h, N, nbytes, dp(d_value), B, dp(d_bytes), dp(d_flags)))
-        self._note(N, B, N + nbytes + (1 if d_flags else 0))
-
-    def encrypt_bytes_batch_dev(self, N, q, nbytes, d_h, d_r, d_bytes, B, d_e, d_quotE=None):
-        dp = self._dp
-        self._chk(self._lib.ntru_encrypt_bytes_batch_dev(self._h, N, q, nbytes, dp(d_h), dp(d_r), dp(d_bytes), B, dp(d_e), dp(d_quotE)))
-
-    def decrypt_bytes_batch_dev(self, N, q, p, nbytes, d_f, d_fp, d_e, B, d_bytes, d_flags=None):
-        dp = self._dp
-        self._chk(self._lib.ntru_decrypt_bytes_batch_dev(self._h, N, q, p, nbytes, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_bytes), dp(d_flags)))
-
-    def encrypt_peritem_batch_dev(self, N, q, d_h, d_r, d_m, B, d_e, d_quotE=None):
-        """d_h: [B][N] public keys, one per item."""
-        dp = self._dp
-        self._chk(self._lib.ntru_encrypt_peritem_batch_dev(self._h, N, q, dp(d_h), dp(d_r), dp(d_m), B, dp(d_e), dp(d_quotE)))
-        self._note(N, B, (6 if d_quotE else 4) * N + 2 * N)      # h, r, m in; e (+ quotientE) out
-
-    def decrypt_peritem_batch_dev(self, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1=None, d_rem1=None, d_quot2=None):
-        """d_f, d_fp: [B][N] private keys, one per item."""
-        dp = self._dp
-        self._chk(self._lib.ntru_decrypt_peritem_batch_dev(self._h, N, q, p, dp(d_f), dp(d_fp), dp(d_e), B, dp(d_value),
-                                                           dp(d_quot1), dp(d_rem1), dp(d_quot2)))
-        self._note(N, B, (5 + (2 if d_quot1 else 0) + (2 if d_rem1 else 0) + (1 if d_quot2 else 0)) * N)
-
-    def verify_keys_batch_dev(self, N, q, p, d_f, d_g, d_fq, d_fp, d_h, B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp,
-                              d_quot_h, d_rem_h, d_flags):
-        dp = self._dp
-        self._chk(self._lib.ntru_verify_keys_batch_dev(self._h, N, q, p, dp(d_f), dp(d_g), dp(d_fq), dp(d_fp), dp(d_h),
-                                                       B, dp(d_quot_fq), dp(d_rem_fq), dp(d_quot_fp), dp(d_rem_fp),
-                                                       dp(d_quot_h), dp(d_rem_h), dp(d_flags)))
-        self._note(N, B, 17 * N)
-
-
-class MultiEngine:
+class MultiEngine(_Handle):
     """Several devices in one process (ntru_multi_*): a host batch is cut into contiguous shards, one engine + host thread per
-    listed device id (an id may repeat).  Host numpy arrays in and out, same results as Engine."""
+    listed device id (an id may repeat).  Host numpy arrays in and out, same results as Engine; its batch methods come from _CALLS."""
+    _destroy = "ntru_multi_destroy"
 
     def __init__(self, device_ids):
         self._lib = load_library()
         ids = (C.c_int * len(device_ids))(*[int(d) for d in device_ids])
         h = C.c_void_p()
         self._h = None
-        rc = self._lib.ntru_multi_create(ids, len(device_ids), C.byref(h))
-        if rc:
-            raise EngineError(rc, self._lib.ntru_last_error().decode())
+        self._chk(self._lib.ntru_multi_create(ids, len(device_ids), C.byref(h)))
         self._h = h
-
-    def _chk(self, rc):
-        if rc:
-            raise EngineError(rc, self._lib.ntru_last_error().decode())
-
-    def close(self):
-        if self._h is not None:
-            self._lib.ntru_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def engines(self):
         return int(self._lib.ntru_multi_engines(self._h))
 
-    def encrypt_batch(self, N, q, h, r, m, want_quot=True):
-        h = _np(h, np.uint16, (N,))
-        r, m = _np(r, np.uint8).reshape(-1, N), _np(m, np.uint8).reshape(-1, N)
-        B = r.shape[0]
-        e = np.empty((B, N), np.uint16)
-        quot = np.empty((B, N), np.uint16) if want_quot else None
-        self._chk(self._lib.ntru_multi_encrypt_batch(self._h, N, q, _ptr(h), _ptr(r), _ptr(m), B, _ptr(e), _ptr(quot)))
-        return e, quot
 
-    def decrypt_batch(self, N, q, p, f, fp, e, want_witness=True):
-        f, fp = _np(f, np.int8, (N,)), _np(fp, np.uint8, (N,))
-        e = _np(e, np.uint16).reshape(-1, N)
-        B = e.shape[0]
-        value = np.empty((B, N), np.uint8)
-        q1 = np.empty((B, N), np.uint16) if want_witness else None
-        r1 = np.empty((B, N), np.uint16) if want_witness else None
-        q2 = np.empty((B, N), np.uint8) if want_witness else None
-        self._chk(self._lib.ntru_multi_decrypt_batch(self._h, N, q, p, _ptr(f), _ptr(fp), _ptr(e), B, _ptr(value),
-                                                     _ptr(q1), _ptr(r1), _ptr(q2)))
-        return value, q1, r1, q2
-
-    def verify_keys_batch(self, N, q, p, f, g, fq, fp, h):
-        f, g = _np(f, np.int8).reshape(-1, N), _np(g, np.int8).reshape(-1, N)
-        fq, h = _np(fq, np.uint16).reshape(-1, N), _np(h, np.uint16).reshape(-1, N)
-        fp = _np(fp, np.uint8).reshape(-1, N)
-        B = f.shape[0]
-        out = {"quot_fq": np.empty((B, N), np.uint16), "rem_fq": np.empty((B, N), np.uint16),
-               "quot_fp": np.empty((B, N), np.uint8), "rem_fp": np.empty((B, N), np.uint8),
-               "quot_h": np.empty((B, N), np.uint16), "rem_h": np.empty((B, N), np.uint16),
-               "flags": np.empty(B, np.uint8)}
-        self._chk(self._lib.ntru_multi_verify_keys_batch(self._h, N, q, p, _ptr(f), _ptr(g), _ptr(fq), _ptr(fp), _ptr(h), B,
-                                                         _ptr(out["quot_fq"]), _ptr(out["rem_fq"]), _ptr(out["quot_fp"]),
-                                                         _ptr(out["rem_fp"]), _ptr(out["quot_h"]), _ptr(out["rem_h"]),
-                                                         _ptr(out["flags"])))
-        return out
-
-    def polymul_split(self, N, mod, a, b):
-        a, b = _np(a, np.uint16).reshape(-1, N), _np(b, np.uint16).reshape(-1, N)
-        B = a.shape[0]
-        quot, rem = np.empty((B, N), np.uint16), np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_multi_polymul_split(self._h, N, mod, _ptr(a), _ptr(b), B, _ptr(quot), _ptr(rem)))
-        return quot, rem
-
-    def invert_key_batch(self, N, q, p, f):
-        f = _np(f, np.int8).reshape(-1, N)
-        B = f.shape[0]
-        fq, fp, flags = np.empty((B, N), np.uint16), np.empty((B, N), np.uint8), np.empty(B, np.uint8)
-        self._chk(self._lib.ntru_multi_invert_key_batch(self._h, N, q, p, _ptr(f), B, _ptr(fq), _ptr(fp), _ptr(flags)))
-        return fq, fp, flags
-
-    def public_key_batch(self, N, q, p, fq, g):
-        fq, g = _np(fq, np.uint16).reshape(-1, N), _np(g, np.int8).reshape(-1, N)
-        B = fq.shape[0]
-        h = np.empty((B, N), np.uint16)
-        self._chk(self._lib.ntru_multi_public_key_batch(self._h, N, q, p, _ptr(fq), _ptr(g), B, _ptr(h)))
-        return h
+_derive(Engine, "host")
+_derive(Engine, "dev")
+_derive(MultiEngine, "multi")
