@@ -154,8 +154,10 @@ static __device__ __forceinline__ void pi_product_cyc(const v4i (&F)[NPL], const
 // ten matrix instructions per trip for 24 lane-shift instructions (two loops took 40), one set of planes, one loop prologue, fq
 // read once.  Five accumulator pairs = 160 registers: two waves per SIMD.  Same device: 2.12-2.13 ms per 2^18 against 2.18-2.20 ms for
 // the two-loop form at three waves per SIMD (products 1 + 2, then product 3 with its own planes), 2.09 against 2.18 J per launch.
-static __host__ __device__ inline size_t pi_verify_wave_bytes(const PGeom &g) { return pi_nat_bytes(g) + (size_t)32 * g.tpitch; }
-
+struct PiPlanVerify {                 // streams: f, g; accumulators 0, 1 = fq * f; 2, 3 = fq * g; 4 = fp * f
+  static constexpr int streams = 2, terms = 5;
+  static constexpr PiTerm term(int t) { return t < 4 ? PiTerm{t >> 1, t & 1, (t >> 1) + 2 * (t & 1), t >> 1} : PiTerm{2, 0, 4, 2}; }
+};
 __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_verify_keys_m(
     PGeom g, u32 q, const int8_t *__restrict__ f, const int8_t *__restrict__ gg, const u16 *__restrict__ fq,
     const uint8_t *__restrict__ fp, const u16 *__restrict__ h, long B, u16 *__restrict__ quot_fq,
@@ -163,24 +165,16 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(2
     u16 *__restrict__ rem_h, uint8_t *__restrict__ flags) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * pi_verify_wave_bytes(g);
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, 2);
   u32 *Tf = (u32 *)(nat + pi_nat_bytes(g)), *Tg = Tf + 4 * g.tpitch;
   const int N = g.N, NT = g.NT;
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };      // this lane's chunk of every operand row
-  auto index_of = [](int ln) { return 128 * (ln >> 5) + (ln & 31); };    // accumulator register i holds index 32 ((i&3) + 8 (i>>2)) + this
   const long item_step = (long)gridDim.x * PI_WAVES;
-  // An item's operand rows are requested at the end of the PREVIOUS item's last epilogue (a wave that fetched them where it needs
-  // them sat idle for a round trip to HBM per item) and stay in these registers across the loop back-edge.
-  RawChunks<2> r_fq;
-  RawChunks<1> r_f, r_fp, r_g;
+  // An item's operand rows are requested at the end of the PREVIOUS item's last epilogue (PiRow).
+  PiRow<2> r_fq;
+  PiRow<1> r_f, r_fp, r_g;
   auto request_rows = [&](long it) {
-    // (descriptors of ONE row: the lanes whose chunk lies beyond it -- chunks NT .. 63 -- read zeros instead of fetching the next items' rows)
-    const long row = it * N;
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc s_fq = aligned_src(fq + row, 2L * N), s_f = aligned_src(f + row, (long)N), s_fp = aligned_src(fp + row, (long)N),
-                     s_g = aligned_src(gg + row, (long)N);
-    r_fq = load_raw<2>(s_fq, s_fq.a0 + 32 * ch, 0); r_f = load_raw<1>(s_f, s_f.a0 + 16 * ch, 0);
-    r_g = load_raw<1>(s_g, s_g.a0 + 16 * ch, 0); r_fp = load_raw<1>(s_fp, s_fp.a0 + 16 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    r_fq.request(fq, it, N, ch); r_f.request(f, it, N, ch); r_g.request(gg, it, N, ch); r_fp.request(fp, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request_rows((long)blockIdx.x * PI_WAVES + wave);
   [[maybe_unused]] int stamp_iter = -1;                    // -DNTRU_STAMPS: phase stamps of the first items (tools/phase_stamps_peritem.py)
@@ -189,186 +183,77 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(2
     u32 fl = 0;
     stamp_iter++;
     STAMP(0);
-    auto bytes_of = [&](const RawChunks<1> &rw, const void *p) {
-      v4i v[1];
-      shift_raw<1>(rw, __builtin_amdgcn_readfirstlane((int)((unsigned long long)p & 15)), v);
-      return v[0];
-    };
-    // ternary operands: any negative byte is -1 (ValTernary), bytes at and beyond N are zero -- four bytes at a time
-    auto ternary = [&](v4i v, const v4i &cmask) {
-      v4i o;
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const u32 w = (u32)(v[c] & cmask[c]);
-        const u32 neg = (w >> 7) & 0x01010101u;            // 1 in every negative byte ...
-        o[c] = (int)(w | neg * 0xFFu);                     // ... spread to 0xFF (no carries: the factors are below 2^8 and 2^25)
-      }
-      return o;
-    };
     // ---- operands: the reversed arrays of f and g, the planes fq lo / fq hi / fp mod 3 (index.js:155-166)
     v4i F[3];
     {
-      const int ch = chunk_of(opaque(lane));
+      const int ch = pi_chunk_of(opaque(lane));
       const v4i cmask = col_mask16(16 * ch, N);            // bytes of this lane's chunk that are below N
-      pi_build_array_ch(nat, Tf, g, lane, ch, ternary(bytes_of(r_f, f + row), cmask));
-      pi_build_array_ch(nat, Tg, g, lane, ch, ternary(bytes_of(r_g, gg + row), cmask));
+      pi_build_array_ch(nat, Tf, g, lane, ch, pi_ternary(r_f.bytes(f + row), cmask));
+      pi_build_array_ch(nat, Tg, g, lane, ch, pi_ternary(r_g.bytes(gg + row), cmask));
       STAMP(1);                                            // the two reversed arrays
       u32 xq[8];
-      {
-        v4i v[2];
-        shift_raw<2>(r_fq, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(fq + row) & 15)), v);
-#pragma unroll
-        for (int c = 0; c < 4; c++) { xq[c] = (u32)v[0][c]; xq[4 + c] = (u32)v[1][c]; }
-      }
+      r_fq.pairs(fq + row, xq);
       pi_digits(xq, q, 1u, 16 * ch, N, F[0], F[1]);
-      // fp mod 3 as the third plane.  A key's fp is already reduced: one wave-wide test (is any byte >= 3?) skips the byte-wise division
-      union { v4i v; unsigned char c[16]; } u; u.v = bytes_of(r_fp, fp + row) & cmask;
-      u32 big = 0;
-#pragma unroll
-      for (int c = 0; c < 4; c++) big |= ((((u32)u.v[c] & 0x7F7F7F7Fu) + 0x7D7D7D7Du) | (u32)u.v[c]) & 0x80808080u;
-      if (__ballot(big != 0) != 0) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) u.c[j] = (unsigned char)((u32)u.c[j] % 3u);
-      }
-      F[2] = u.v;
+      F[2] = pi_mod3_bytes(r_fp.bytes(fp + row) & cmask);  // fp mod 3 as the third plane
     }
     // h is requested before the loop whose remainder it is compared with, as a natural-order row chunk (16 coefficients per lane);
     // the remainder gets into the same layout through the wave's LDS (the natural-order area is free again by then)
-    const AlignedSrc s_h = aligned_src(h + row, 2L * N);
-    const RawChunks<2> r_h = load_raw<2>(s_h, s_h.a0 + 32 * opaque(lane), 0);
+    PiRow<2> r_h;
+    r_h.request(h, item, N, opaque(lane));
     STAMP(2);                                              // the three planes in registers
-    // ---- the loop: L1 / H1 (two planes) = fq * f, L2 / H2 = fp * f, L3 / H3 (two planes) = fq * g
-    v16i L1[2], H1[2], L2, H2, L3[2], H3[2];
-    {
-      const int ln = opaque(lane);
-      const int y0 = 32 * NT - 1 - (ln & 31) + 16 * (ln >> 5);
-      const u32 *tb = Tf + (y0 & 3) * g.tpitch + (y0 >> 2);     // this lane's fragment of f at distance 0; g's lies 4 tpitch dwords above
-      const int tstep = 4 * g.tpitch;
-      int seam_up = ln == 32 ? 0 : -1, seam_dn = ln == 31 ? 0 : -1;
-      asm volatile("" : "+v"(seam_up), "+v"(seam_dn));
-      struct Fr { v4i f, g; };
-      auto frag = [&](int d) {                             // |d| <= NT - 1; requests past the last step read the last fragment again
-        d = d > NT - 1 ? NT - 1 : (d < 1 - NT ? 1 - NT : d);
-        const u32 *p = tb - 8 * d, *p1 = p + tstep;
-        Fr fr;
-        fr.f = (v4i){(int)p[0], (int)p[1], (int)p[2], (int)p[3]};
-        fr.g = (v4i){(int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
-        return fr;
-      };
-      const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      const Fr f0 = frag(0);
-      Fr la = frag(1), ha = frag(-1), lb, hb;
-      {                                                    // d = 0: split by the diagonal mask; the first term of every accumulator
-        u32 mlow[4], mhigh[4];
-        pi_diag_low_mask(ln, mlow);
-#pragma unroll
-        for (int c = 0; c < 4; c++) mhigh[c] = ~mlow[c];
-        const v4i fl_ = and4(f0.f, mlow), fh_ = and4(f0.f, mhigh), gl_ = and4(f0.g, mlow), gh_ = and4(f0.g, mhigh);
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-          L1[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], fl_, zero, 0, 0, 0);
-          H1[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], fh_, zero, 0, 0, 0);
-          L3[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], gl_, zero, 0, 0, 0);
-          H3[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], gh_, zero, 0, 0, 0);
-        }
-        L2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[2], fl_, zero, 0, 0, 0);
-        H2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[2], fh_, zero, 0, 0, 0);
-      }
-      v4i AL[3] = {F[0], F[1], F[2]}, AH[3] = {F[0], F[1], F[2]};
-      auto trip = [&](const Fr &wl, const Fr &wh) {        // every shifted plane feeds two matrix instructions (the fp plane one)
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-          AL[p] = rows_up(AL[p], seam_up);
-          L1[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AL[p], wl.f, L1[p], 0, 0, 0);
-          L3[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AL[p], wl.g, L3[p], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);               // the next plane's shifts issue under these matrix instructions
-        }
-        AL[2] = rows_up(AL[2], seam_up);
-        L2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(AL[2], wl.f, L2, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int p = 0; p < 2; p++) {
-          AH[p] = rows_down(AH[p], seam_dn);
-          H1[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AH[p], wh.f, H1[p], 0, 0, 0);
-          H3[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AH[p], wh.g, H3[p], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        AH[2] = rows_down(AH[2], seam_dn);
-        H2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(AH[2], wh.f, H2, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      int j = 1;
-      for (; j + 1 < NT; j += 2) {
-        lb = frag(j + 1); hb = frag(-(j + 1));
-        trip(la, ha);
-        la = frag(j + 2); ha = frag(-(j + 2));
-        trip(lb, hb);
-      }
-      if (j < NT) trip(la, ha);
-    }
+    // ---- the loop: L1 / H1 (two planes) = fq * f, L3 / H3 (two planes) = fq * g, L2 / H2 = fp * f: every shifted plane of fq feeds two
+    // matrix instructions, the fp plane one
+    v16i L[5], H[5];
+    pi_product_plan<PiPlanVerify>(F, Tf, g, lane, L, H);
+    const v16i *const L1 = L, *const H1 = H, *const L3 = L + 2, *const H3 = H + 2, &L2 = L[4], &H2 = H[4];
     STAMP(3);                                              // the matrix loop
-    const int kl = index_of(opaque(lane));
+    const int kl = pi_index_of(opaque(lane));
     {
       // stores through one-row descriptors: index k = 32 kb + r is a per-lane offset (128 hh + r) plus a compile-time
       // one per register, indices >= N fall outside the descriptor and are dropped -- no address arithmetic per store
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(rem_fq + row, 2L * N), rs_q = rows_rsrc(quot_fq + row, 2L * N);
-      // index.js:159: invalid iff the remainder has a non-zero coefficient above the constant one AND its constant one is not 1.
-      // Register i of this lane holds index ko_i + kl: it exists iff ko_i < N - kl (one compare against a per-lane limit, ko_i a
-      // constant); coefficient 0 is register 0 of lane 0.
-      u32 any_hi = 0, c0 = 0;
-      const int lim = N - kl;
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
-        const int lo = L1[0][i] + 128 * L1[1][i], hi = H1[0][i] + 128 * H1[1][i];
-        const u32 rv = (u32)(lo + hi) & (q - 1);
+      PiNotOne rem;                                        // index.js:159
+      pi_for_split<2>(L1, H1, [&](int i, int ko, u32 lo, u32 hi) {
+        const u32 rv = (lo + hi) & (q - 1);
         __builtin_amdgcn_raw_buffer_store_b16((u16)rv, rs_r, 2 * kl, 2 * ko, 0);
-        __builtin_amdgcn_raw_buffer_store_b16((u16)((u32)(0 - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
-        if (i == 0) { c0 = rv; any_hi |= kl == 0 ? 0u : rv; }
-        else any_hi |= ko < lim ? rv : 0u;
-      }
-      const bool nz_hi = any_hi != 0, first_not_one = kl == 0 && c0 != 1;
-      if (__ballot(nz_hi) != 0 && __ballot(first_not_one) != 0) fl |= NTRU_FLAG_INVALID_FQ;   // length !== 1 && [0] !== 1
+        __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
+        rem.see(i, ko, kl, N, rv);
+      });
+      if (rem.invalid(kl)) fl |= NTRU_FLAG_INVALID_FQ;
     }
     STAMP(4);                                              // product 1's epilogue
     {
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(rem_fp + row, (long)N), rs_q = rows_rsrc(quot_fp + row, (long)N);
-      u32 any_hi = 0, c0 = 0;                              // as for product 1
-      const int lim = N - kl;
+      PiNotOne rem;                                        // as for product 1
 #pragma unroll
       for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
+        const int ko = pi_ko(i);
         // |L + H|, |H| <= 127 N (f is an int8, fp < 3): a multiple of 3 above that keeps the dividend non-negative
         const u32 x = (u32)(L2[i] + H2[i] + 3 * 131072), y = (u32)(3 * 131072 - H2[i]);
         const u32 rv = x % 3u, qv = y % 3u;
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)rv, rs_r, kl, ko, 0);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)qv, rs_q, kl, ko, 0);
-        if (i == 0) { c0 = rv; any_hi |= kl == 0 ? 0u : rv; }
-        else any_hi |= ko < lim ? rv : 0u;
+        rem.see(i, ko, kl, N, rv);
       }
-      const bool nz_hi = any_hi != 0, first_not_one = kl == 0 && c0 != 1;
-      if (__ballot(nz_hi) != 0 && __ballot(first_not_one) != 0) fl |= NTRU_FLAG_INVALID_FP;
+      if (rem.invalid(kl)) fl |= NTRU_FLAG_INVALID_FP;
     }
     STAMP(5);                                              // product 2's epilogue
     {
       // product 3 = p (fq * g) mod q (index.js:155,164): the factor p = 3 is applied here, to the low and the high half alike
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(rem_h + row, 2L * N), rs_q = rows_rsrc(quot_h + row, 2L * N);
       u16 *remx = (u16 *)nat;
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
-        const int lo = L3[0][i] + 128 * L3[1][i], hi = H3[0][i] + 128 * H3[1][i];
-        const u32 rv = (u32)(3 * (lo + hi)) & (q - 1);
+      pi_for_split<2>(L3, H3, [&](int, int ko, u32 lo, u32 hi) {
+        const u32 rv = (3u * (lo + hi)) & (q - 1);
         __builtin_amdgcn_raw_buffer_store_b16((u16)rv, rs_r, 2 * kl, 2 * ko, 0);
-        __builtin_amdgcn_raw_buffer_store_b16((u16)((u32)(0 - 3 * hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
+        __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - 3u * hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
         remx[ko + kl] = (u16)rv;                           // ko + kl <= 1151: inside the area for every N (pi_nat_bytes)
-      }
+      });
       if (item + item_step < B) request_rows(item + item_step);   // the next item's rows: in flight from here on (the accumulators are dead)
       wave_lds_fence();
       STAMP(6);                                            // product 3's result stores issued
       // index.js:165: h[k] must equal the remainder for every k below h's trimmed length
       v4i hc[2];
-      shift_raw<2>(r_h, __builtin_amdgcn_readfirstlane(s_h.a0), hc);
+      r_h.take(h + row, hc);
       const int i0 = 16 * opaque(lane);
       // Per lane two 16-bit sets in a SPLIT layout (coefficient i0 + 2 c in bit c, i0 + 2 c + 1 in bit 16 + c: what one packed
       // 16-bit minimum and one shift-or per dword give): nz = h is non-zero there, df = h differs from the remainder there;
@@ -426,36 +311,29 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int NPL = ONE ? 1 : 2;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * pi_reg_wave_bytes(g);
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, 1);
   u32 *T = (u32 *)(nat + pi_nat_bytes(g));
   const int N = g.N;
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };
   // The operands of the NEXT item are requested as soon as this item's are in registers (the round trip to HBM runs under the matrix
   // loops and the result stores instead of in front of every item).
   const long item_step = (long)gridDim.x * PI_WAVES;
-  RawChunks<2> ra;
-  RawChunks<1> rs;
+  PiRow<2> ra;
+  PiRow<1> rs;
   auto request = [&](long it) {
-    const long rw = it * N;                                // (one-row descriptors: see k_verify_keys_m)
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc sa = aligned_src(a + rw, 2L * N), ss = aligned_src(s + rw, (long)N);
-    ra = load_raw<2>(sa, sa.a0 + 32 * ch, 0);
-    rs = load_raw<1>(ss, ss.a0 + 16 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    ra.request(a, it, N, ch); rs.request(s, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request((long)blockIdx.x * PI_WAVES + wave);
   for (long item = (long)blockIdx.x * PI_WAVES + wave; item < B; item += item_step) {
     const long row = item * N;
     v4i F[NPL];
     {
-      const int ch = chunk_of(opaque(lane));
-      v4i va[2], vs[1];
-      shift_raw<2>(ra, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(a + row) & 15)), va);
-      shift_raw<1>(rs, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(s + row) & 15)), vs);
-      if (item + item_step < B) request(item + item_step);
+      const int ch = pi_chunk_of(opaque(lane));
       u32 xa[8];
-#pragma unroll
-      for (int c = 0; c < 4; c++) { xa[c] = (u32)va[0][c]; xa[4 + c] = (u32)va[1][c]; }
-      pi_build_array_half(nat, T, g, lane, ch, pi_ternary(vs[0], col_mask16(16 * ch, N)));     // (its last fence: nat is free for the planes' images)
+      ra.pairs(a + row, xa);
+      const v4i vs = rs.bytes(s + row);
+      if (item + item_step < B) request(item + item_step);
+      pi_build_array_half(nat, T, g, lane, ch, pi_ternary(vs, col_mask16(16 * ch, N)));     // (its last fence: nat is free for the planes' images)
       v4i o0, o1;
       pi_digits(xa, q, mul, 16 * ch, N, o0, o1);
       F[0] = o0;
@@ -468,11 +346,11 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
     pi_cyc_keep(g, lane, keep);
     pi_product_cyc<NPL>(F, nat, T, g, lane, keep, C);
     {
-      const int ln = opaque(lane), kl = 128 * (ln >> 5) + (ln & 31);     // see k_verify_keys_m: indices >= N are dropped
+      const int kl = pi_index_of(opaque(lane));     // see k_verify_keys_m: indices >= N are dropped
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(rem + row, 2L * N);
 #pragma unroll
       for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
+        const int ko = pi_ko(i);
         const int c = C[0][i] + (ONE ? 0 : 128 * C[NPL - 1][i]);
         __builtin_amdgcn_raw_buffer_store_b16((u16)((u32)c & (q - 1)), rs_r, 2 * kl, 2 * ko, 0);
       }
@@ -491,20 +369,16 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
     PGeom g, u32 kb, u32 m, const int8_t *__restrict__ f, u16 *v, long B) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * pi_reg_wave_bytes(g);
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, 1);
   u32 *T = (u32 *)(nat + pi_nat_bytes(g));
   const int N = g.N;
   const u32 mr = 1u << m, me = 1u << (m - kb);
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };
   const long item_step = (long)gridDim.x * PI_WAVES;
-  RawChunks<2> rv;
-  RawChunks<1> rf;
+  PiRow<2> rv;
+  PiRow<1> rf;
   auto request = [&](long it) {
-    const long rw = it * N;
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc sv = aligned_src(v + rw, 2L * N), sf = aligned_src(f + rw, (long)N);
-    rv = load_raw<2>(sv, sv.a0 + 32 * ch, 0);
-    rf = load_raw<1>(sf, sf.a0 + 16 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    rv.request(v, it, N, ch); rf.request(f, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request((long)blockIdx.x * PI_WAVES + wave);
   [[maybe_unused]] int stamp_iter = -1;                    // -DNTRU_STAMPS: phase stamps of the first items (tools/phase_stamps_peritem.py)
@@ -515,18 +389,15 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
     v4i b0;                                                // v modulo 2^(m - kb), centred: the second product's Toeplitz operand
     v4i F[1];
     {
-      const int ch = chunk_of(opaque(lane));
-      v4i va[2], vf[1];
-      shift_raw<2>(rv, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(v + row) & 15)), va);
-      shift_raw<1>(rf, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(f + row) & 15)), vf);
+      const int ch = pi_chunk_of(opaque(lane));
       u32 xv[8];
-#pragma unroll
-      for (int c = 0; c < 4; c++) { xv[c] = (u32)va[0][c]; xv[4 + c] = (u32)va[1][c]; }
+      rv.pairs(v + row, xv);
+      const v4i vf = rf.bytes(f + row);
       v4i o1;
       pi_digits(xv, me, 1u, 16 * ch, N, b0, o1);
       pi_digits(xv, 256u, 1u, 16 * ch, N, F[0], o1);      // v < 2^kb <= 128: its own centred representative modulo 256
       STAMP(1);                                            // operands arrived, digits
-      pi_build_array_half(nat, T, g, lane, ch, pi_ternary(vf[0], col_mask16(16 * ch, N)));       // (its last fence: nat is free for v's image)
+      pi_build_array_half(nat, T, g, lane, ch, pi_ternary(vf, col_mask16(16 * ch, N)));          // (its last fence: nat is free for v's image)
       pi_store_image(nat, g, ch, F[0]);
       wave_lds_fence();
     }
@@ -538,7 +409,7 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
     STAMP(3);
     if (item + item_step < B) request(item + item_step);   // the next item's rows (nobody lifts them before this wave does): a product ahead
     {
-      const int ln = opaque(lane), kl = 128 * (ln >> 5) + (ln & 31), ch = chunk_of(ln);
+      const int ln = opaque(lane), kl = pi_index_of(ln), ch = pi_chunk_of(ln);
       u32 e[16];                                           // e = (f v - 1) / 2^kb modulo 2^(m - kb): bits kb .. m - 1 of f v - 1
 #pragma unroll
       for (int i = 0; i < 16; i++)
@@ -546,22 +417,22 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
       pi_build_array_half(nat, T, g, lane, ch, b0);          // (over f's array; its last fence orders the reads of nat before the writes below)
       unsigned char *img = nat + (32 * g.NT - N);          // e's image for the entering rows IS its natural-order byte image, P bytes up
 #pragma unroll
-      for (int i = 0; i < 16; i++) img[32 * ((i & 3) + 8 * (i >> 2)) + kl] = (unsigned char)e[i];     // index <= 1023 + 31
+      for (int i = 0; i < 16; i++) img[pi_ko(i) + kl] = (unsigned char)e[i];     // index <= 1023 + 31
       wave_lds_fence();
       F[0] = *(const v4i *)(img + 16 * ch) & col_mask16(16 * ch, N);       // (any alignment; bytes at and beyond N: whatever the product left there)
     }
     // v in the accumulator layout, for the lift (the row this item staged a moment ago: an L2 hit), in flight during the second product
     const __amdgpu_buffer_rsrc_t rs_v = rows_rsrc(v + row, 2L * N);
-    const int kl2 = 128 * (opaque(lane) >> 5) + (opaque(lane) & 31);
+    const int kl2 = pi_index_of(opaque(lane));
     u16 vold[16];
 #pragma unroll
-    for (int i = 0; i < 16; i++) vold[i] = (u16)__builtin_amdgcn_raw_buffer_load_b16(rs_v, 2 * kl2, 2 * 32 * ((i & 3) + 8 * (i >> 2)), 0);
+    for (int i = 0; i < 16; i++) vold[i] = (u16)__builtin_amdgcn_raw_buffer_load_b16(rs_v, 2 * kl2, 2 * pi_ko(i), 0);
     STAMP(4);                                              // e, v's reversed array, e's image and rows
     pi_product_cyc<1>(F, nat, T, g, lane, keep, C);        // e v
     STAMP(5);
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-      const int ko = 32 * ((i & 3) + 8 * (i >> 2));
+      const int ko = pi_ko(i);
       u32 nv;                                              // vold - 2^kb (e v): of e v only its residue modulo 2^(m - kb) reaches the low m bits
       asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(nv) : "v"(C[0][i]), "s"(0 - (int)(1u << kb)), "v"(vold[i]));   // |e v| < 2^23; vold's upper half: masked below
       __builtin_amdgcn_raw_buffer_store_b16((u16)(nv & (mr - 1)), rs_v, 2 * kl2, 2 * ko, 0);
@@ -576,26 +447,20 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
 // a0 b0 + 128 (a0 b1 + a1 b0) + 16384 a1 b1, and 16384 = 0 mod q: three plane products, two accumulator groups, two reversed arrays
 // (the digit planes of b) per item, the rows of a0 and a1 in registers.
 // ONE (q <= 256): one digit plane per operand.
-static __host__ __device__ inline size_t pi_reg_wave_bytes2(const PGeom &g) { return pi_reg_wave_bytes(g) + (size_t)16 * g.tpitch; }
-
 template <bool ONE>
 __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(ONE ? 4 : 3, 4))) void k_polymul_m(
     PGeom g, u32 q, const u16 *__restrict__ a, const u16 *__restrict__ b, long B, u16 *__restrict__ quot, u16 *__restrict__ rem) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * (ONE ? pi_reg_wave_bytes(g) : pi_reg_wave_bytes2(g));
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, ONE ? 1 : 2);
   u32 *T0 = (u32 *)(nat + pi_nat_bytes(g)), *T1 = T0 + 4 * g.tpitch;
   const int N = g.N, NT = g.NT;
   const bool want_q = quot != nullptr;
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };
   const long item_step = (long)gridDim.x * PI_WAVES;         // the NEXT item's operands are requested early: see k_product_tern_m
-  RawChunks<2> rwa, rwb;
+  PiRow<2> rwa, rwb;
   auto request = [&](long it) {
-    const long rw = it * N;
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc sa = aligned_src(a + rw, 2L * N), sb = aligned_src(b + rw, 2L * N);
-    rwa = load_raw<2>(sa, sa.a0 + 32 * ch, 0);
-    rwb = load_raw<2>(sb, sb.a0 + 32 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    rwa.request(a, it, N, ch); rwb.request(b, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request((long)blockIdx.x * PI_WAVES + wave);
   [[maybe_unused]] int stamp_iter = -1;                    // -DNTRU_STAMPS: phase stamps of the first items (tools/phase_stamps_peritem.py)
@@ -605,15 +470,10 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
     STAMP(0);
     v4i a0, a1;
     {
-      const int ch = chunk_of(opaque(lane));
+      const int ch = pi_chunk_of(opaque(lane));
       u32 xa[8], xb[8];
-      {
-        v4i va[2], vb[2];
-        shift_raw<2>(rwa, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(a + row) & 15)), va);
-        shift_raw<2>(rwb, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(b + row) & 15)), vb);
-#pragma unroll
-        for (int c = 0; c < 4; c++) { xa[c] = (u32)va[0][c]; xa[4 + c] = (u32)va[1][c]; xb[c] = (u32)vb[0][c]; xb[4 + c] = (u32)vb[1][c]; }
-      }
+      rwa.pairs(a + row, xa);
+      rwb.pairs(b + row, xb);
       STAMP(1);                                            // operands arrived
       if (item + item_step < B) request(item + item_step);
       v4i b0, b1;
@@ -633,7 +493,8 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
 #pragma unroll
       for (int i = 0; i < 16; i++) { XL[1][i] = 0; XH[1][i] = 0; }
     } else {
-      // as pi_product_reg, with two fragment streams (the planes of b) and three matrix instructions per half trip
+      // as pi_product_plan, with the terms (a0, b0, X0) behind plane 0 and (a0, b1, X1), (a1, b0, X1) behind plane 1: written out, because
+      // the plan form takes 142 registers here where this takes 140
       const int ln = opaque(lane);
       const int y0 = 32 * NT - 1 - (ln & 31) + 16 * (ln >> 5);
       const u32 *tb = T0 + (y0 & 3) * g.tpitch + (y0 >> 2);
@@ -692,16 +553,13 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
     }
     STAMP(4);                                              // matrix loops
     {
-      const int ln = opaque(lane), kl = 128 * (ln >> 5) + (ln & 31);     // see k_verify_keys_m: indices >= N are dropped
+      const int kl = pi_index_of(opaque(lane));     // see k_verify_keys_m: indices >= N are dropped
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(rem + row, 2L * N);
       const __amdgpu_buffer_rsrc_t rs_q = rows_rsrc(want_q ? quot + row : nullptr, want_q ? 2L * N : 0L);
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
-        const u32 lo = (u32)XL[0][i] + 128u * (u32)XL[1][i], hi = (u32)XH[0][i] + 128u * (u32)XH[1][i];
+      pi_for_split<2>(XL, XH, [&](int, int ko, u32 lo, u32 hi) {
         __builtin_amdgcn_raw_buffer_store_b16((u16)((lo + hi) & (q - 1)), rs_r, 2 * kl, 2 * ko, 0);
         if (want_q) __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
-      }
+      });
     }
     wave_lds_fence();
     STAMP(5);                                              // result stores issued
@@ -716,8 +574,8 @@ int ntru_launch_polymul_matrix(ntru_engine *eng, int N, int mod, const uint16_t 
   const PGeom pg = make_pgeom(N);
   const bool one = mod <= 256;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_polymul_m");
-  return launch_resident(eng, one ? k_polymul_m<true> : k_polymul_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
-                         PI_WAVES * (one ? pi_reg_wave_bytes(pg) : pi_reg_wave_bytes2(pg)), pg, (u32)mod, d_a, d_b, (long)B, d_quot, d_rem);
+  return launch_peritem(eng, one ? k_polymul_m<true> : k_polymul_m<false>, B, pi_wave_bytes(pg, one ? 1 : 2), pg, (u32)mod, d_a, d_b, (long)B,
+                        d_quot, d_rem);
 }
 
 bool ntru_product_tern_matrix_applies(const ntru_engine *eng, int N, int q) { return peritem_applies(eng, N, q); }
@@ -725,8 +583,8 @@ bool ntru_product_tern_matrix_applies(const ntru_engine *eng, int N, int q) { re
 int ntru_launch_product_tern_matrix(ntru_engine *eng, int N, int q, uint32_t mul, const uint16_t *d_a, const int8_t *d_s, long B,
                                     uint16_t *d_rem) {
   const PGeom pg = make_pgeom(N);
-  return launch_resident(eng, q <= 256 ? k_product_tern_m<true> : k_product_tern_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
-                         PI_WAVES * pi_reg_wave_bytes(pg), pg, (u32)q, (u32)mul, d_a, d_s, B, d_rem);
+  return launch_peritem(eng, q <= 256 ? k_product_tern_m<true> : k_product_tern_m<false>, B, pi_wave_bytes(pg, 1), pg, (u32)q, (u32)mul, d_a,
+                        d_s, B, d_rem);
 }
 
 int ntru_launch_verify_keys_matrix(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, const int8_t *d_g, const uint16_t *d_fq,
@@ -735,8 +593,8 @@ int ntru_launch_verify_keys_matrix(ntru_engine *eng, int N, int q, int p, const 
   if (p != 3 || !peritem_applies(eng, N, q)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_verify_keys_m");
-  return launch_resident(eng, k_verify_keys_m, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES, PI_WAVES * pi_verify_wave_bytes(pg), pg,
-                         (u32)q, d_f, d_g, d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq, d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
+  return launch_peritem(eng, k_verify_keys_m, B, pi_wave_bytes(pg, 2), pg, (u32)q, d_f, d_g, d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq,
+                        d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
 }
 
 
@@ -747,8 +605,7 @@ bool ntru_newton_round_matrix_applies(const ntru_engine *eng, int N, int kb, int
 int ntru_launch_newton_round_matrix(ntru_engine *eng, int N, int kb, int m, const int8_t *d_f, uint16_t *d_v, long B) {
   if (!ntru_newton_round_matrix_applies(eng, N, kb, m)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
-  return launch_resident(eng, k_newton_round_m, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES, PI_WAVES * pi_reg_wave_bytes(pg), pg, (u32)kb,
-                         (u32)m, d_f, d_v, B);
+  return launch_peritem(eng, k_newton_round_m, B, pi_wave_bytes(pg, 1), pg, (u32)kb, (u32)m, d_f, d_v, B);
 }
 
 #ifdef NTRU_STAMPS

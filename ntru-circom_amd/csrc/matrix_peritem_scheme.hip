@@ -27,59 +27,49 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int NPL = ONE ? 1 : 2;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * pi_reg_wave_bytes(g);
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, 1);
   u32 *T = (u32 *)(nat + pi_nat_bytes(g));
   const int N = g.N;
   const bool want_q = quotE != nullptr;
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };
   const long item_step = (long)gridDim.x * PI_WAVES;         // the NEXT item's rows are requested early: see k_product_tern_m
-  RawChunks<2> rh;
-  RawChunks<1> rr;
+  PiRow<2> rh;
+  PiRow<1> rr;
   auto request = [&](long it) {
-    const long rw = it * N;                                // (one-row descriptors: see k_verify_keys_m)
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc sh = aligned_src(h + rw, 2L * N), sr = aligned_src(r + rw, (long)N);
-    rh = load_raw<2>(sh, sh.a0 + 32 * ch, 0);
-    rr = load_raw<1>(sr, sr.a0 + 16 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    rh.request(h, it, N, ch); rr.request(r, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request((long)blockIdx.x * PI_WAVES + wave);
   for (long item = (long)blockIdx.x * PI_WAVES + wave; item < B; item += item_step) {
     const long row = item * N;
     v4i F[NPL];
     {
-      const int ch = chunk_of(opaque(lane));
-      v4i vh[2], vr[1];
-      shift_raw<2>(rh, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(h + row) & 15)), vh);
-      shift_raw<1>(rr, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(r + row) & 15)), vr);
-      if (item + item_step < B) request(item + item_step);
-      pi_build_array_ch(nat, T, g, lane, ch, vr[0] & col_mask16(16 * ch, N));
+      const int ch = pi_chunk_of(opaque(lane));
       u32 xh[8];
-#pragma unroll
-      for (int c = 0; c < 4; c++) { xh[c] = (u32)vh[0][c]; xh[4 + c] = (u32)vh[1][c]; }
+      rh.pairs(h + row, xh);
+      const v4i vr = rr.bytes(r + row);
+      if (item + item_step < B) request(item + item_step);
+      pi_build_array_ch(nat, T, g, lane, ch, vr & col_mask16(16 * ch, N));
       v4i o0, o1;
       pi_digits(xh, q, 1u, 16 * ch, N, o0, o1);
       F[0] = o0;
       if (!ONE) F[NPL - 1] = o1;
     }
-    // m in the accumulator layout (register i of this lane: index 32 ((i&3) + 8 (i>>2)) + kl), in flight during the product;
+    // m in the accumulator layout (register i of this lane: index pi_ko(i) + kl), in flight during the product;
     // bytes at and beyond N read as zero
-    const int kl = 128 * (opaque(lane) >> 5) + (opaque(lane) & 31);
+    const int kl = pi_index_of(opaque(lane));
     const __amdgpu_buffer_rsrc_t rs_m = rows_rsrc(m + row, (long)N);
     u32 mv[16];
 #pragma unroll
-    for (int i = 0; i < 16; i++) mv[i] = __builtin_amdgcn_raw_buffer_load_b8(rs_m, kl, 32 * ((i & 3) + 8 * (i >> 2)), 0);
+    for (int i = 0; i < 16; i++) mv[i] = __builtin_amdgcn_raw_buffer_load_b8(rs_m, kl, pi_ko(i), 0);
     v16i L[NPL], H[NPL];
     pi_product_reg<NPL>(F, T, g, lane, L, H);
     {
       const __amdgpu_buffer_rsrc_t rs_e = rows_rsrc(e + row, 2L * N);
       const __amdgpu_buffer_rsrc_t rs_q = rows_rsrc(want_q ? quotE + row : nullptr, want_q ? 2L * N : 0L);
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
-        const u32 lo = (u32)L[0][i] + (ONE ? 0u : 128u * (u32)L[NPL - 1][i]), hi = (u32)H[0][i] + (ONE ? 0u : 128u * (u32)H[NPL - 1][i]);
+      pi_for_split<NPL>(L, H, [&](int i, int ko, u32 lo, u32 hi) {
         __builtin_amdgcn_raw_buffer_store_b16((u16)((lo + hi + mv[i]) & (q - 1)), rs_e, 2 * kl, 2 * ko, 0);
         if (want_q) __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
-      }
+      });
     }
     wave_lds_fence();
   }
@@ -87,8 +77,6 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
 
 // ---- decryptBits, one key per item ------------------------------------------------------------------------------------------
 // p == 3.  ONE: q <= 256, a single (centred) digit plane of e.  quot1 / rem1 / quot2 may be NULL (empty descriptors).
-static __host__ __device__ inline size_t pi_decrypt_wave_bytes(const PGeom &g) { return pi_nat_bytes(g) + (size_t)32 * g.tpitch; }
-
 template <bool ONE>
 __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_decrypt_pi_m(
     PGeom g, u32 q, const int8_t *__restrict__ f, const uint8_t *__restrict__ fp, const u16 *__restrict__ e, long B,
@@ -96,72 +84,51 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(3
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int NPL = ONE ? 1 : 2;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  unsigned char *nat = lds + (size_t)wave * pi_decrypt_wave_bytes(g);
+  unsigned char *nat = lds + (size_t)wave * pi_wave_bytes(g, 2);
   u32 *Tf = (u32 *)(nat + pi_nat_bytes(g)), *Tp = Tf + 4 * g.tpitch;
   const int N = g.N;
   const bool want_q1 = quot1 != nullptr, want_r1 = rem1 != nullptr, want_q2 = quot2 != nullptr;
-  auto chunk_of = [](int ln) { return 2 * (ln & 31) + (ln >> 5); };
   const long item_step = (long)gridDim.x * PI_WAVES;
-  RawChunks<2> re;
-  RawChunks<1> rf, rp;
+  PiRow<2> re;
+  PiRow<1> rf, rp;
   auto request = [&](long it) {
-    const long rw = it * N;
-    const int ch = chunk_of(opaque(lane));
-    const AlignedSrc se = aligned_src(e + rw, 2L * N), sf = aligned_src(f + rw, (long)N), sp = aligned_src(fp + rw, (long)N);
-    re = load_raw<2>(se, se.a0 + 32 * ch, 0);
-    rf = load_raw<1>(sf, sf.a0 + 16 * ch, 0);
-    rp = load_raw<1>(sp, sp.a0 + 16 * ch, 0);
+    const int ch = pi_chunk_of(opaque(lane));
+    re.request(e, it, N, ch); rf.request(f, it, N, ch); rp.request(fp, it, N, ch);
   };
   if ((long)blockIdx.x * PI_WAVES + wave < B) request((long)blockIdx.x * PI_WAVES + wave);
   for (long item = (long)blockIdx.x * PI_WAVES + wave; item < B; item += item_step) {
     const long row = item * N;
     v4i F[NPL];
     {
-      const int ch = chunk_of(opaque(lane));
+      const int ch = pi_chunk_of(opaque(lane));
       const v4i cmask = col_mask16(16 * ch, N);
-      v4i ve[2], vf[1], vp[1];
-      shift_raw<2>(re, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(e + row) & 15)), ve);
-      shift_raw<1>(rf, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(f + row) & 15)), vf);
-      shift_raw<1>(rp, __builtin_amdgcn_readfirstlane((int)((unsigned long long)(fp + row) & 15)), vp);
-      if (item + item_step < B) request(item + item_step);
-      pi_build_array_ch(nat, Tf, g, lane, ch, pi_ternary(vf[0], cmask));
-      // fp mod 3: a key's fp is already reduced, so one wave-wide test (is any byte >= 3?) skips the byte-wise division
-      union { v4i v; unsigned char c[16]; } u; u.v = vp[0] & cmask;
-      u32 big = 0;
-#pragma unroll
-      for (int c = 0; c < 4; c++) big |= ((((u32)u.v[c] & 0x7F7F7F7Fu) + 0x7D7D7D7Du) | (u32)u.v[c]) & 0x80808080u;
-      if (__ballot(big != 0) != 0) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) u.c[j] = (unsigned char)((u32)u.c[j] % 3u);
-      }
-      pi_build_array_ch(nat, Tp, g, lane, ch, u.v);        // (its last fence: nat is free for the image of a)
       u32 xe[8];
-#pragma unroll
-      for (int c = 0; c < 4; c++) { xe[c] = (u32)ve[0][c]; xe[4 + c] = (u32)ve[1][c]; }
+      re.pairs(e + row, xe);
+      const v4i vf = rf.bytes(f + row), vp = rp.bytes(fp + row);
+      if (item + item_step < B) request(item + item_step);
+      pi_build_array_ch(nat, Tf, g, lane, ch, pi_ternary(vf, cmask));
+      pi_build_array_ch(nat, Tp, g, lane, ch, pi_mod3_bytes(vp & cmask));   // (its last fence: nat is free for the image of a)
       v4i o0, o1;
       pi_digits(xe, q, 1u, 16 * ch, N, o0, o1);
       F[0] = o0;
       if (!ONE) F[NPL - 1] = o1;
     }
     // ---- product 1: f (x) e modulo q, then the lift into a natural-order byte image (index <= 1151 whatever N is: pi_nat_bytes)
-    const int kl = 128 * (opaque(lane) >> 5) + (opaque(lane) & 31);
+    const int kl = pi_index_of(opaque(lane));
     v4i A[1];
     {
       v16i L[NPL], H[NPL];
       pi_product_reg<NPL>(F, Tf, g, lane, L, H);
       const __amdgpu_buffer_rsrc_t rs_q = rows_rsrc(want_q1 ? quot1 + row : nullptr, want_q1 ? 2L * N : 0L);
       const __amdgpu_buffer_rsrc_t rs_r = rows_rsrc(want_r1 ? rem1 + row : nullptr, want_r1 ? 2L * N : 0L);
-#pragma unroll
-      for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
-        const u32 lo = (u32)L[0][i] + (ONE ? 0u : 128u * (u32)L[NPL - 1][i]), hi = (u32)H[0][i] + (ONE ? 0u : 128u * (u32)H[NPL - 1][i]);
+      pi_for_split<NPL>(L, H, [&](int, int ko, u32 lo, u32 hi) {
         const u32 rv = (lo + hi) & (q - 1);
         if (want_r1) __builtin_amdgcn_raw_buffer_store_b16((u16)rv, rs_r, 2 * kl, 2 * ko, 0);
         if (want_q1) __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
         nat[ko + kl] = (unsigned char)(2 * rv > q ? (rv + 1) % 3u : rv % 3u);     // index.js:117, strict >
-      }
+      });
       wave_lds_fence();
-      const int ch = chunk_of(opaque(lane));
+      const int ch = pi_chunk_of(opaque(lane));
       A[0] = *(const v4i *)(nat + 16 * ch) & col_mask16(16 * ch, N);        // (bytes at and beyond N: junk tiles, cut)
     }
     // ---- product 2: a (x) fp modulo 3
@@ -172,7 +139,7 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(3
       const __amdgpu_buffer_rsrc_t rs_q = rows_rsrc(want_q2 ? quot2 + row : nullptr, want_q2 ? (long)N : 0L);
 #pragma unroll
       for (int i = 0; i < 16; i++) {
-        const int ko = 32 * ((i & 3) + 8 * (i >> 2));
+        const int ko = pi_ko(i);
         // 0 <= L, H <= 4 N (a, fp < 3): no sign to take care of
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((u32)(L2[0][i] + H2[0][i]) % 3u), rs_v, kl, ko, 0);
         if (want_q2) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((3u - (u32)H2[0][i] % 3u) % 3u), rs_q, kl, ko, 0);
@@ -290,8 +257,8 @@ extern "C" int ntru_encrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   if (!peritem_applies(eng, N, q)) return encrypt_composed(eng, N, q, d_h, d_r, d_m, B, d_e, d_quotE);
   const PGeom pg = make_pgeom(N);
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_encrypt_pi_m");
-  return launch_resident(eng, q <= 256 ? k_encrypt_pi_m<true> : k_encrypt_pi_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
-                         PI_WAVES * pi_reg_wave_bytes(pg), pg, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
+  return launch_peritem(eng, q <= 256 ? k_encrypt_pi_m<true> : k_encrypt_pi_m<false>, B, pi_wave_bytes(pg, 1), pg, (u32)q, d_h, d_r, d_m,
+                        (long)B, d_e, d_quotE);
 }
 
 extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
@@ -305,8 +272,8 @@ extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   if (p != 3 || !peritem_applies(eng, N, q)) return decrypt_composed(eng, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1, d_rem1, d_quot2);
   const PGeom pg = make_pgeom(N);
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_pi_m");
-  return launch_resident(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES,
-                         PI_WAVES * pi_decrypt_wave_bytes(pg), pg, (u32)q, d_f, d_fp, d_e, (long)B, d_value, d_quot1, d_rem1, d_quot2);
+  return launch_peritem(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, B, pi_wave_bytes(pg, 2), pg, (u32)q, d_f, d_fp, d_e,
+                        (long)B, d_value, d_quot1, d_rem1, d_quot2);
 }
 
 // ---- host-pointer forms: the chunked pipeline of ntru_host.hip ------------------------------------------------------------------------

@@ -25,6 +25,47 @@ static __host__ __device__ inline size_t pi_nat_bytes(const PGeom &g) {
   return periods > 2304 ? periods : 2304;
 }
 
+// Per wave: the natural-order area (pi_nat_bytes: three periods of the ternary / Toeplitz operand, later a product's natural-order image,
+// e.g. product 3's remainder for the comparison with h), then `arrays` (1 or 2) reversed arrays of four byte-shifted copies each.  No
+// chunk matrix: the rows live in registers.  Used by every kernel body and by its launcher.
+static __host__ __device__ inline size_t pi_wave_bytes(const PGeom &g, int arrays) { return pi_nat_bytes(g) + (size_t)arrays * 16 * g.tpitch; }
+
+// Lane (r, hh) = 32 hh + r holds chunk 2 r + hh (16 coefficients) of every operand row -- the layout the matrix instruction wants its
+// A operand in -- and accumulator register i of that lane holds index pi_ko(i) + pi_index_of(lane).
+static __device__ __forceinline__ int pi_chunk_of(int lane) { return 2 * (lane & 31) + (lane >> 5); }
+static __device__ __forceinline__ int pi_index_of(int lane) { return 128 * (lane >> 5) + (lane & 31); }
+constexpr int pi_ko(int i) { return 32 * ((i & 3) + 8 * (i >> 2)); }
+
+// One operand row of an item on its way from HBM into this lane's registers: 16 coefficients of NCH bytes each per lane.  An item's rows
+// are requested one item AHEAD (a wave that fetched them where it needs them sat idle for a round trip to HBM per item) and stay in
+// `raw` across the loop back-edge; take them with the row's own pointer, whose low four bits are the shift.
+template <int NCH>
+struct PiRow {
+  RawChunks<NCH> raw;
+  // Row `item` of rows[B][N], chunk ch of it.  The descriptor covers ONE row: the lanes whose chunk lies beyond it -- chunks NT .. 63 --
+  // read zeros instead of fetching the next items' rows.
+  template <class E>
+  __device__ __forceinline__ void request(const E *rows, long item, int N, int ch) {
+    static_assert(sizeof(E) == NCH, "16 coefficients per lane");
+    const AlignedSrc s = aligned_src(rows + item * N, (long)NCH * N);
+    raw = load_raw<NCH>(s, s.a0 + 16 * NCH * ch, 0);
+  }
+  __device__ __forceinline__ void take(const void *row, v4i (&v)[NCH]) const {
+    shift_raw<NCH>(raw, __builtin_amdgcn_readfirstlane((int)((unsigned long long)row & 15)), v);
+  }
+  __device__ __forceinline__ v4i bytes(const void *row) const {              // NCH == 1
+    v4i v[NCH];
+    take(row, v);
+    return v[0];
+  }
+  __device__ __forceinline__ void pairs(const void *row, u32 (&x)[8]) const {   // NCH == 2: what pi_digits wants
+    v4i v[NCH];
+    take(row, v);
+#pragma unroll
+    for (int c = 0; c < 4; c++) { x[c] = (u32)v[0][c]; x[4 + c] = (u32)v[NCH - 1][c]; }
+  }
+};
+
 // Digit planes of 16 values (u16 pairs in x[8], element i0 + j; zero at and beyond N) -> natural-order int8 bytes, on
 // packed 16-bit pairs.  mul: the operand is (mul v) mod q (p fq of index.js:155; 1 otherwise).  q > 256: v = d0 + 128 d1 with
 // d0 = v & 127, d1 = v >> 7 <= 63 (the two planes have SEPARATE accumulators, so nothing needs a signed representative).
@@ -69,6 +110,19 @@ static __device__ __forceinline__ v4i pi_ternary(v4i v, const v4i &cmask) {
   return o;
 }
 
+// Sixteen bytes modulo 3.  A key's fp is already reduced: one wave-wide test (is any byte >= 3?) skips the byte-wise division.
+static __device__ __forceinline__ v4i pi_mod3_bytes(v4i v) {
+  union { v4i v; unsigned char c[16]; } u; u.v = v;
+  u32 big = 0;
+#pragma unroll
+  for (int c = 0; c < 4; c++) big |= ((((u32)u.v[c] & 0x7F7F7F7Fu) + 0x7D7D7D7Du) | (u32)u.v[c]) & 0x80808080u;
+  if (__ballot(big != 0) != 0) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) u.c[j] = (unsigned char)((u32)u.c[j] % 3u);
+  }
+  return u.v;
+}
+
 // ---- chunk rows in REGISTERS (k_verify_keys_m) -----------------------------------------------------------------------------------
 // The A operand of tile distance d is the chunk matrix moved down by d rows: lane (r, hh) holds bytes 16 hh .. 16 hh + 15 of chunk
 // r - d.  Going from d to d + 1 (d >= 0) every lane takes its lower neighbour's 16 bytes and nothing enters at row 0; going from d to
@@ -110,64 +164,119 @@ static __device__ __forceinline__ v4i rows_down(v4i a, int seam) {        // lan
   return o;
 }
 
-// NPL planes F[p] (unshifted chunk rows of this lane, zero at and beyond N) against the Toeplitz fragments of T: L[p] / H[p] = low /
-// high half of plane p's product.  Low and high parts advance together (two independent fragment reads and 2 NPL matrix
-// instructions per trip, fragments requested one trip ahead, unrolled by two so that the two fragment sets rotate without moves).
-template <int NPL>
-static __device__ __forceinline__ void pi_product_reg(const v4i (&F)[NPL], const u32 *T, const PGeom &g, int lane_, v16i (&L)[NPL], v16i (&H)[NPL]) {
+// The split (quotient-keeping) product loop, driven by a compile-time PLAN: planes F[p] (unshifted chunk rows of this lane, zero at and
+// beyond N) against the Toeplitz fragments of one or two reversed arrays ("streams": stream s lies 4 s tpitch dwords above T), summed
+// into accumulators L[a] / H[a] = low / high half.  A plan lists the terms acc += plane (x) stream and, for each, the plane behind
+// whose shift it issues; the sched_barrier(0) closes the group of every plane, so that the next plane's shifts issue under the group's
+// matrix instructions.  Low and high parts advance together (independent fragment reads, fragments requested one trip ahead, unrolled
+// by two so that the two fragment sets rotate without moves).
+struct PiTerm { int plane, stream, acc, after; };
+template <class Plan, int NP, int NA>
+static __device__ __forceinline__ void pi_product_plan(const v4i (&F)[NP], const u32 *T, const PGeom &g, int lane_, v16i (&L)[NA], v16i (&H)[NA]) {
+  constexpr int NS = Plan::streams, NTERM = Plan::terms;
   const int lane = opaque(lane_), NT = g.NT;
   const int y0 = 32 * NT - 1 - (lane & 31) + 16 * (lane >> 5);
   const u32 *tb = T + (y0 & 3) * g.tpitch + (y0 >> 2);     // this lane's fragment of distance 0; distance d lies 8 d dwords below
+  const int tstep = 4 * g.tpitch;
   int seam_up = lane == 32 ? 0 : -1, seam_dn = lane == 31 ? 0 : -1;
   asm volatile("" : "+v"(seam_up), "+v"(seam_dn));         // (opaque: as a known 0 / -1 the AND becomes a select that cannot carry the DPP shift)
+  struct Fr { v4i w[NS]; };
   auto frag = [&](int d) {                                 // |d| <= NT - 1; requests past the last step read the last fragment again
     d = d > NT - 1 ? NT - 1 : (d < 1 - NT ? 1 - NT : d);
-    const u32 *p = tb - 8 * d;
-    return (v4i){(int)p[0], (int)p[1], (int)p[2], (int)p[3]};
+    Fr fr;
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      const u32 *p = tb - 8 * d + s * tstep;
+      fr.w[s] = (v4i){(int)p[0], (int)p[1], (int)p[2], (int)p[3]};
+    }
+    return fr;
   };
   const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  v4i AL[NPL], AH[NPL];
-  const v4i w0 = frag(0);
-  v4i wl_a = frag(1), wh_a = frag(-1), wl_b, wh_b;
+  const Fr f0 = frag(0);
+  Fr la = frag(1), ha = frag(-1), lb, hb;
   {                                                        // d = 0: split by the diagonal mask; the first term of every accumulator
-    u32 mlow[4];
+    u32 mlow[4], mhigh[4];
     pi_diag_low_mask(lane, mlow);
-    const v4i wl = and4(w0, mlow);
-    const v4i wh = {(int)((u32)w0[0] & ~mlow[0]), (int)((u32)w0[1] & ~mlow[1]), (int)((u32)w0[2] & ~mlow[2]), (int)((u32)w0[3] & ~mlow[3])};
 #pragma unroll
-    for (int p = 0; p < NPL; p++) {
-      L[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], wl, zero, 0, 0, 0);
-      H[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[p], wh, zero, 0, 0, 0);
-      AL[p] = F[p]; AH[p] = F[p];
+    for (int c = 0; c < 4; c++) mhigh[c] = ~mlow[c];
+    Fr wl, wh;
+#pragma unroll
+    for (int s = 0; s < NS; s++) { wl.w[s] = and4(f0.w[s], mlow); wh.w[s] = and4(f0.w[s], mhigh); }
+#pragma unroll
+    for (int t = 0; t < NTERM; t++) {
+      constexpr auto first = [](int t_) { for (int u = 0; u < t_; u++) if (Plan::term(u).acc == Plan::term(t_).acc) return false; return true; };
+      const PiTerm k = Plan::term(t);
+      L[k.acc] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[k.plane], wl.w[k.stream], first(t) ? zero : L[k.acc], 0, 0, 0);
+      H[k.acc] = __builtin_amdgcn_mfma_i32_32x32x32_i8(F[k.plane], wh.w[k.stream], first(t) ? zero : H[k.acc], 0, 0, 0);
     }
   }
-  auto trip = [&](const v4i &wl, const v4i &wh) {
+  v4i AL[NP], AH[NP];
 #pragma unroll
-    for (int p = 0; p < NPL; p++) {
+  for (int p = 0; p < NP; p++) { AL[p] = F[p]; AH[p] = F[p]; }
+  auto trip = [&](const Fr &wl, const Fr &wh) {
+#pragma unroll
+    for (int p = 0; p < NP; p++) {
       AL[p] = rows_up(AL[p], seam_up);
-      L[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AL[p], wl, L[p], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);                   // the next plane's shifts issue under this matrix instruction
+#pragma unroll
+      for (int t = 0; t < NTERM; t++)
+        if (Plan::term(t).after == p) L[Plan::term(t).acc] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AL[Plan::term(t).plane], wl.w[Plan::term(t).stream], L[Plan::term(t).acc], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);                   // the next plane's shifts issue under these matrix instructions
     }
 #pragma unroll
-    for (int p = 0; p < NPL; p++) {
+    for (int p = 0; p < NP; p++) {
       AH[p] = rows_down(AH[p], seam_dn);
-      H[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AH[p], wh, H[p], 0, 0, 0);
+#pragma unroll
+      for (int t = 0; t < NTERM; t++)
+        if (Plan::term(t).after == p) H[Plan::term(t).acc] = __builtin_amdgcn_mfma_i32_32x32x32_i8(AH[Plan::term(t).plane], wh.w[Plan::term(t).stream], H[Plan::term(t).acc], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
   int j = 1;
   for (; j + 1 < NT; j += 2) {
-    wl_b = frag(j + 1); wh_b = frag(-(j + 1));
-    trip(wl_a, wh_a);
-    wl_a = frag(j + 2); wh_a = frag(-(j + 2));
-    trip(wl_b, wh_b);
+    lb = frag(j + 1); hb = frag(-(j + 1));
+    trip(la, ha);
+    la = frag(j + 2); ha = frag(-(j + 2));
+    trip(lb, hb);
   }
-  if (j < NT) trip(wl_a, wh_a);
+  if (j < NT) trip(la, ha);
 }
 
-// Per wave: three natural-order periods of the ternary operand (the source of its reversed array; later the remainder of product 3
-// for the comparison with h), then the reversed array.  No chunk matrix: the rows live in registers.
-static __host__ __device__ inline size_t pi_reg_wave_bytes(const PGeom &g) { return pi_nat_bytes(g) + (size_t)16 * g.tpitch; }
+// NPL planes against ONE reversed array: L[p] / H[p] = low / high half of plane p's product.
+template <int NPL>
+struct PiPlanPlanes {
+  static constexpr int streams = 1, terms = NPL;
+  static constexpr PiTerm term(int t) { return {t, 0, t, t}; }
+};
+template <int NPL>
+static __device__ __forceinline__ void pi_product_reg(const v4i (&F)[NPL], const u32 *T, const PGeom &g, int lane, v16i (&L)[NPL], v16i (&H)[NPL]) {
+  pi_product_plan<PiPlanPlanes<NPL>>(F, T, g, lane, L, H);
+}
+
+// The epilogue of a split product: f(i, ko, lo, hi) for the sixteen accumulator registers with the digit planes combined (value = acc0 +
+// 128 acc1), lo / hi = low / high half of coefficient ko + pi_index_of(lane): remainder = lo + hi, quotient = -hi (modulo q).
+template <int NPL, class Fn>
+static __device__ __forceinline__ void pi_for_split(const v16i *L, const v16i *H, Fn f) {     // L[0 .. NPL - 1], H likewise
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const u32 lo = (u32)L[0][i] + (NPL == 1 ? 0u : 128u * (u32)L[NPL - 1][i]), hi = (u32)H[0][i] + (NPL == 1 ? 0u : 128u * (u32)H[NPL - 1][i]);
+    f(i, pi_ko(i), lo, hi);
+  }
+}
+
+// index.js:159: a remainder is invalid iff it has a non-zero coefficient above the constant one AND its constant one is not 1
+// (length !== 1 && [0] !== 1).  Register i of lane kl = pi_index_of(lane) holds index ko_i + kl: it exists iff ko_i < N - kl (one compare
+// against a per-lane limit, ko_i a constant); coefficient 0 is register 0 of lane 0.
+struct PiNotOne {
+  u32 any_hi = 0, c0 = 0;
+  __device__ __forceinline__ void see(int i, int ko, int kl, int N, u32 rv) {
+    if (i == 0) { c0 = rv; any_hi |= kl == 0 ? 0u : rv; }
+    else any_hi |= ko < N - kl ? rv : 0u;
+  }
+  __device__ __forceinline__ bool invalid(int kl) const {                   // wave-wide
+    const bool nz_hi = any_hi != 0, first_not_one = kl == 0 && c0 != 1;
+    return __ballot(nz_hi) != 0 && __ballot(first_not_one) != 0;
+  }
+};
 
 // Reversed cyclic array (4 byte-shifted copies) of a ternary / int8 operand of which this lane holds chunk ch (the 16 bytes sv:
 // coefficients 16 ch .. 16 ch + 15, zero at and beyond N; any assignment of chunks to lanes): three periods in natural order (period
@@ -224,6 +333,12 @@ static inline PGeom make_pgeom(int N) {
 // The per-item matrix kernels: modulus a power of two <= 8192 (two int8 digit planes), 64 <= N <= 1024; automatic from N = 128.
 static inline bool peritem_applies(const ntru_engine *eng, int N, int q) {
   return matrix_path_allowed(eng) && is_pow2(q) && q <= 8192 && N <= 1024 && N >= (eng->path >= 4 ? 64 : 128);
+}
+
+// A launch of the family: one item per wave, PI_WAVES waves per workgroup, each with wave_bytes of LDS.
+template <class Kern, class... Args>
+static int launch_peritem(ntru_engine *eng, Kern kern, long B, size_t wave_bytes, Args... args) {
+  return launch_resident(eng, kern, (B + PI_WAVES - 1) / PI_WAVES, 64 * PI_WAVES, PI_WAVES * wave_bytes, args...);
 }
 
 #endif

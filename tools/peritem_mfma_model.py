@@ -77,7 +77,7 @@ def product_split(a, s_planes, scales, N):
 
 
 def product_split_registers(a_planes, s, N):
-    """The form the kernels use since round 5 (csrc/matrix_peritem.hip, "chunk rows in REGISTERS"): lane (r, hh) of the wave holds
+    """The form the kernels use since round 5 (`pi_product_plan`, csrc/peritem_common.h, "chunk rows in REGISTERS"): lane (r, hh) of the wave holds
     bytes 16 hh .. 16 hh + 15 of chunk r of every plane; the low part walks d = 1, 2, ... by moving every lane's 16 bytes one lane UP
     (wave_shr:1, lane 0 takes zero, lane 32 -- the seam between the half-waves -- is cut to zero), the high part walks d = -1, -2, ...
     one lane DOWN (wave_shl:1, lanes 63 and 31 take zero).  No row of the chunk matrix is ever read from the LDS again; the fragment of
