@@ -187,6 +187,12 @@ int ntru_check_common(const ntru_engine *eng, int N, int q, long B) {
   return NTRU_OK;
 }
 
+int ntru_check_decrypt_p(int N, int p) {
+  if (is_pow2(p) || !ntru_engine_supports(N, p))
+    return fail(NTRU_ERR_UNSUPPORTED, "unsupported p: need a small non-power-of-two modulus with N*(p-1)^2 < 65536");
+  return NTRU_OK;
+}
+
 static int check_pitch(int N, int ld) {
   if (ld < N || ld > 1024) return fail(NTRU_ERR_ARG, "row pitch must satisfy N <= ld <= 1024 elements");
   return NTRU_OK;
@@ -223,8 +229,7 @@ extern "C" int ntru_decrypt_batch_pitched_dev(ntru_engine_t *eng, int N, int q, 
                                               uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2) {
   if (int rc = ntru_check_common(eng, N, q, B)) return rc;
   if (ld != N) if (int rc = check_pitch(N, ld)) return rc;
-  if (is_pow2(p) || !ntru_engine_supports(N, p))
-    return fail(NTRU_ERR_UNSUPPORTED, "unsupported p: need a small non-power-of-two modulus with N*(p-1)^2 < 65536");
+  if (int rc = ntru_check_decrypt_p(N, p)) return rc;
   if (B == 0) return NTRU_OK;
   if (!d_f || !d_fp || !d_e || !d_value) return fail(NTRU_ERR_ARG, "ntru_decrypt_batch: NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
@@ -240,8 +245,7 @@ extern "C" int ntru_decrypt_batch_pitched_dev(ntru_engine_t *eng, int N, int q, 
 extern "C" int ntru_decrypt_pack_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
                                            const uint16_t *d_e, int64_t B, uint8_t *d_value, uint64_t *d_packed) {
   if (int rc = ntru_check_common(eng, N, q, B)) return rc;
-  if (is_pow2(p) || !ntru_engine_supports(N, p))
-    return fail(NTRU_ERR_UNSUPPORTED, "unsupported p: need a small non-power-of-two modulus with N*(p-1)^2 < 65536");
+  if (int rc = ntru_check_decrypt_p(N, p)) return rc;
   int bits, per, al, os;
   if (int rc = ntru_pack_params(p - 1, N, &bits, &per, &al, &os)) return rc;
   if (B == 0) return NTRU_OK;
@@ -308,8 +312,7 @@ extern "C" int ntru_verify_keys_batch_dev(ntru_engine_t *eng, int N, int q, int 
                                           uint8_t *d_quot_fp, uint8_t *d_rem_fp, uint16_t *d_quot_h,
                                           uint16_t *d_rem_h, uint8_t *d_flags) {
   if (int rc = ntru_check_common(eng, N, q, B)) return rc;
-  if (is_pow2(p) || !ntru_engine_supports(N, p))
-    return fail(NTRU_ERR_UNSUPPORTED, "unsupported p: need a small non-power-of-two modulus with N*(p-1)^2 < 65536");
+  if (int rc = ntru_check_decrypt_p(N, p)) return rc;
   if ((long)(q - 1) * p > 65535) return fail(NTRU_ERR_UNSUPPORTED, "p*(q-1) must fit 16 bits");
   if (B == 0) return NTRU_OK;
   if (!d_f || !d_g || !d_fq || !d_fp || !d_h || !d_quot_fq || !d_rem_fq || !d_quot_fp || !d_rem_fp || !d_quot_h ||

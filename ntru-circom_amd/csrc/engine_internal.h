@@ -6,13 +6,14 @@
 //   matrix_decrypt.hip       family 4, decryptBits with a shared key (k_decrypt_m, k_decrypt_m8)
 //   matrix_peritem.hip       family 4 with per-item operands (k_verify_keys_m, k_polymul_m, k_product_tern_m)
 //   keygen_sampler_pack.hip  key inversion, ternary sampler, field packing, elementwise kernels + their *_dev entry points
-//   ntru_host.hip            host-pointer entry points: pinned staging, three stage streams, chunked H2D / kernel / D2H pipeline
+//   ntru_host.hip            host-pointer entry points: every regular one (its _dev form through the chunked H2D / kernel / D2H pipeline below,
+//                            from one description per call) with its ntru_multi_ form, ntru_pipeline_batch, device buffers; no kernels
 //   ntru_generic.hip         reference-faithful generic family (arbitrary divisors, moduli up to 2^26, signed coefficients)
-//   witness_check.hip        witness checks against the Verify* circuits (kernels, *_dev and host-pointer entry points)
+//   witness_check.hip        witness checks against the Verify* circuits (kernels and *_dev entry points)
 //   keygen_batch.hip         batched key generation with on-device redraws (kernels, *_dev and host-pointer entry points)
 //   ciphertext_sum.hip       segmented, weighted sums of ciphertext rows + tally decrypt (kernels, *_dev and host-pointer entry points)
 //   message_bytes.hip        byte messages as packed bits: bytes <-> coefficient rows, encrypt / decrypt / pipeline on bytes (kernels, *_dev
-//                            and host-pointer entry points)
+//                            entry points and ntru_pipeline_bytes_batch)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -128,6 +129,8 @@ static inline dim3 elementwise_grid(const ntru_engine *eng, long total, bool str
 }
 // (N, q, B) of the packed kernels: q a power of two <= 65536, 2 <= N <= NTRU_MAX_N
 NTRU_HIDDEN int ntru_check_common(const ntru_engine *eng, int N, int q, long B);
+// p of decryptBits and of the key checks: a small modulus that is no power of two, N*(p-1)^2 < 65536
+NTRU_HIDDEN int ntru_check_decrypt_p(int N, int p);
 
 // ---- launchers (defined next to their kernels) --------------------------------------------------------------------------------
 // encryptBits / decryptBits with a shared key on the matrix cores; rows at a pitch of ld elements
@@ -172,7 +175,7 @@ NTRU_HIDDEN int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int
                                              uint16_t *d_quot_fq, uint16_t *d_rem_fq, uint8_t *d_quot_fp, uint8_t *d_rem_fp,
                                              uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags);
 
-// ---- host-pointer entry points (ntru_host.hip, witness_check.hip) --------------------------------------------------------------
+// ---- host-pointer entry points (ntru_host.hip; keygen_batch, ciphertext_sum, message_bytes) --------------------------------------------------------------
 // True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).
 NTRU_HIDDEN bool ntru_is_pinned(const void *p);
 // memcpy on several threads once the block is large enough for the extra threads to pay for themselves.

@@ -1,5 +1,5 @@
 // matrix_peritem_scheme.hip -- encryptBits / decryptBits (index.js:87-140) with a SEPARATE key pair for every item: the kernels, the
-// composed fallback outside their range, the *_dev entry points and the host-pointer forms.
+// composed fallback outside their range, and the *_dev entry points (host-pointer forms: ntru_host.hip).
 //
 // The reference's unit is one NTRU instance per key, so "one ciphertext per recipient" and "one decryption per key holder" are the
 // batches its users have.  Both kernels follow k_verify_keys_m (matrix_peritem.hip): one item per wavefront, the chunk rows of the
@@ -239,12 +239,6 @@ int decrypt_composed(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, c
   return NTRU_OK;
 }
 
-int check_decrypt_p(int N, int p) {
-  if (is_pow2(p) || !ntru_engine_supports(N, p))
-    return fail(NTRU_ERR_UNSUPPORTED, "unsupported p: need a small non-power-of-two modulus with N*(p-1)^2 < 65536");
-  return NTRU_OK;
-}
-
 }  // namespace
 
 // ---- device-pointer entry points ----------------------------------------------------------------------------------------------------
@@ -265,7 +259,7 @@ extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
                                               const uint16_t *d_e, int64_t B, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
                                               uint8_t *d_quot2) {
   if (int rc = ntru_check_common(eng, N, q, B)) return rc;
-  if (int rc = check_decrypt_p(N, p)) return rc;
+  if (int rc = ntru_check_decrypt_p(N, p)) return rc;
   if (B == 0) return NTRU_OK;
   if (!d_f || !d_fp || !d_e || !d_value) return fail(NTRU_ERR_ARG, "ntru_decrypt_peritem_batch: NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
@@ -274,35 +268,4 @@ extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_pi_m");
   return launch_peritem(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, B, pi_wave_bytes(pg, 2), pg, (u32)q, d_f, d_fp, d_e,
                         (long)B, d_value, d_quot1, d_rem1, d_quot2);
-}
-
-// ---- host-pointer forms: the chunked pipeline of ntru_host.hip ------------------------------------------------------------------------
-extern "C" int ntru_encrypt_peritem_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *m,
-                                          int64_t B, uint16_t *e, uint16_t *quotE) {
-  if (int rc = ntru_check_common(eng, N, q, B)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!h || !r || !m || !e) return fail(NTRU_ERR_ARG, "ntru_encrypt_peritem_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t n8 = (size_t)N, n16 = 2 * (size_t)N;
-  const int ih = P.in(h, n16), ir = P.in(r, n8), im = P.in(m, n8), ie = P.out(e, n16), iq = P.out(quotE, n16);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_encrypt_peritem_batch_dev(eng, N, q, (const uint16_t *)d[ih], (const uint8_t *)d[ir], (const uint8_t *)d[im], n,
-                                          (uint16_t *)d[ie], (uint16_t *)d[iq]);
-  });
-}
-
-extern "C" int ntru_decrypt_peritem_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e,
-                                          int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
-  if (int rc = ntru_check_common(eng, N, q, B)) return rc;
-  if (int rc = check_decrypt_p(N, p)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !fp || !e || !value) return fail(NTRU_ERR_ARG, "ntru_decrypt_peritem_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t n8 = (size_t)N, n16 = 2 * (size_t)N;
-  const int jf = P.in(f, n8), jp = P.in(fp, n8), je = P.in(e, n16), jv = P.out(value, n8), jq1 = P.out(quot1, n16), jr1 = P.out(rem1, n16),
-            jq2 = P.out(quot2, n8);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_decrypt_peritem_batch_dev(eng, N, q, p, (const int8_t *)d[jf], (const uint8_t *)d[jp], (const uint16_t *)d[je], n,
-                                          (uint8_t *)d[jv], (uint16_t *)d[jq1], (uint16_t *)d[jr1], (uint8_t *)d[jq2]);
-  });
 }

@@ -1,5 +1,6 @@
 // message_bytes.hip -- byte messages as packed bits: the device side of the reference's stringToBits / bitsToString (index.js:538-556)
-// and of encryptStr / decryptStr (index.js:80-86) built on them: kernels, *_dev entry points and the host-pointer forms.
+// and of encryptStr / decryptStr (index.js:80-86) built on them: kernels, *_dev entry points and
+// ntru_pipeline_bytes_batch (the regular host-pointer forms: ntru_host.hip).
 //
 //   row b, coefficient 8 i + j  =  (bytes[b][i] >> (7 - j)) & 1        i < nbytes, most significant bit first (index.js:542)
 //   row b, coefficient k        =  0                                   8 nbytes <= k < N: the pad
@@ -294,56 +295,7 @@ extern "C" int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, in
   return NTRU_OK;
 }
 
-// ---- host-pointer forms: the chunked pipeline of engine_internal.h -------------------------------------------------------------------
-
-extern "C" int ntru_bytes_to_rows(ntru_engine_t *eng, int N, int nbytes, const uint8_t *bytes, int64_t B, uint8_t *m) {
-  if (int rc = check_bytes_args(eng, N, nbytes, B, "ntru_bytes_to_rows")) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!bytes || !m) return fail(NTRU_ERR_ARG, "ntru_bytes_to_rows: NULL buffer");
-  Pipeline P(eng);
-  const int ib = P.in(bytes, nbytes), im = P.out(m, N);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_bytes_to_rows_dev(eng, N, nbytes, (const uint8_t *)d[ib], n, (uint8_t *)d[im]);
-  });
-}
-
-extern "C" int ntru_rows_to_bytes(ntru_engine_t *eng, int N, int nbytes, const uint8_t *value, int64_t B, uint8_t *bytes, uint8_t *flags) {
-  if (int rc = check_bytes_args(eng, N, nbytes, B, "ntru_rows_to_bytes")) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!value || !bytes) return fail(NTRU_ERR_ARG, "ntru_rows_to_bytes: NULL buffer");
-  Pipeline P(eng);
-  const int iv = P.in(value, N), ib = P.out(bytes, nbytes), ifl = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_rows_to_bytes_dev(eng, N, nbytes, (const uint8_t *)d[iv], n, (uint8_t *)d[ib], (uint8_t *)d[ifl]);
-  });
-}
-
-extern "C" int ntru_encrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int nbytes, const uint16_t *h, const uint8_t *r,
-                                        const uint8_t *bytes, int64_t B, uint16_t *e, uint16_t *quotE) {
-  if (int rc = ntru_encrypt_bytes_batch_dev(eng, N, q, nbytes, nullptr, nullptr, nullptr, B < 0 ? B : 0, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!h || !r || !bytes || !e) return fail(NTRU_ERR_ARG, "ntru_encrypt_bytes_batch: NULL buffer");
-  Pipeline P(eng);
-  const int ih = P.in(h, (size_t)N * 2, true), ir = P.in(r, N), ib = P.in(bytes, nbytes), ie = P.out(e, (size_t)N * 2),
-            iq = P.out(quotE, (size_t)N * 2);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_encrypt_bytes_batch_dev(eng, N, q, nbytes, (const uint16_t *)d[ih], (const uint8_t *)d[ir], (const uint8_t *)d[ib], n,
-                                        (uint16_t *)d[ie], (uint16_t *)d[iq]);
-  });
-}
-
-extern "C" int ntru_decrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp,
-                                        const uint16_t *e, int64_t B, uint8_t *bytes, uint8_t *flags) {
-  if (int rc = ntru_decrypt_bytes_batch_dev(eng, N, q, p, nbytes, nullptr, nullptr, nullptr, B < 0 ? B : 0, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !fp || !e || !bytes) return fail(NTRU_ERR_ARG, "ntru_decrypt_bytes_batch: NULL buffer");
-  Pipeline P(eng);
-  const int jf = P.in(f, N, true), jfp = P.in(fp, N, true), je = P.in(e, (size_t)N * 2), jb = P.out(bytes, nbytes), jfl = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_decrypt_bytes_batch_dev(eng, N, q, p, nbytes, (const int8_t *)d[jf], (const uint8_t *)d[jfp], (const uint16_t *)d[je], n,
-                                        (uint8_t *)d[jb], (uint8_t *)d[jfl]);
-  });
-}
+// ---- host-pointer form (the regular ones -- bytes_to_rows, rows_to_bytes, encrypt_bytes, decrypt_bytes -- are in ntru_host.hip) -------
 
 // ntru_pipeline_batch with the plaintext as bytes at both ends: sampler -> bytes_to_rows -> encryptBits -> decryptBits -> rows_to_bytes
 // per chunk.  m and value are device-only rows of the chunk; msg, msg_out and flags are what crosses the bus.

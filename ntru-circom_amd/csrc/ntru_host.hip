@@ -1,4 +1,6 @@
-// ntru_host.hip -- the host-pointer entry points of include/ntru_engine.h (the ones Node.js reaches through the addon).
+// ntru_host.hip -- the host-pointer entry points of include/ntru_engine.h (the ones Node.js reaches through the addon): every regular
+// one (a _dev form run chunk by chunk, with its ntru_multi_ form where it has one), ntru_pipeline_batch, plain device buffers and the
+// multi-device engine.  No kernels here: tests/hostcheck builds this file and abi.hip for the CPU under the sanitizers.
 //
 // The reference keeps everything in JS arrays (index.js:87-197); a host binding therefore hands the engine HOST buffers.
 // This file moves them through the GPU as a pipeline instead of "allocate, copy, run, copy, free" per call:
@@ -18,6 +20,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "engine_internal.h"
@@ -66,175 +69,330 @@ extern "C" void ntru_host_free(void *p) {
   if (p) (void)hipHostFree(p);
 }
 
-#define CHECK_ENGINE()                                                      \
-  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");               \
-  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "negative batch size")
+// ---- one description per call ---------------------------------------------------------------------------------------------------
+// A regular host form is its own _dev form, run chunk by chunk through a Pipeline.  It states the _dev form's arguments once, in
+// order, and describes each array where it passes it:
+//   rows(p, len)       one row of len elements per item
+//   shared(p, len)     one row that travels with every chunk (key material; inputs only)
+//   optional(p, len)   rows per item that may be NULL
+// The element type gives the bytes; a pointer to const is an input (uploaded), a pointer to non-const an output (downloaded).
+// `items` stands where the _dev form takes the item count and first(v) where it takes the index of its first item: the two
+// scalars that change per chunk (and per shard).  Every other argument is passed on as it is.
+namespace {
+enum Role { ROWS, SHARED, OPTIONAL };
+template <class T>
+struct Arr {
+  T *p;
+  size_t len;
+  Role role;
+  int slot;                  // its index in the Pipeline, once declared
+};
+template <class T> Arr<T> rows(T *p, size_t len) { return {p, len, ROWS, -1}; }
+template <class T> Arr<const T> shared(const T *p, size_t len) { return {p, len, SHARED, -1}; }
+template <class T> Arr<T> optional(T *p, size_t len) { return {p, len, OPTIONAL, -1}; }
+struct Items {};
+constexpr Items items;
+struct First { uint64_t v; };
+inline First first(uint64_t v) { return {v}; }
 
-extern "C" int ntru_encrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r,
-                                  const uint8_t *m, int64_t B, uint16_t *e, uint16_t *quotE) {
-  CHECK_ENGINE();
-  if (int rc = ntru_encrypt_batch_dev(eng, N, q, nullptr, nullptr, nullptr, 0, nullptr, nullptr)) return rc;   // parameter checks
+// An argument as the _dev form gets it for n items from item o on: arrays at their device addresses d (without d: NULL).
+template <class T> T *dev_arg(const Arr<T> &a, int64_t, int64_t, void **d) { return d ? static_cast<T *>(d[a.slot]) : nullptr; }
+inline int64_t dev_arg(Items, int64_t, int64_t n, void **) { return n; }
+inline uint64_t dev_arg(First f, int64_t o, int64_t, void **) { return f.v + (uint64_t)o; }
+template <class S> S dev_arg(S s, int64_t, int64_t, void **) { return s; }
+
+template <class T> bool missing(const Arr<T> &a) { return a.role != OPTIONAL && !a.p; }
+template <class S> bool missing(const S &) { return false; }
+
+template <class T> void declare(Pipeline &P, Arr<T> &a) {
+  if constexpr (std::is_const_v<T>) a.slot = P.in(a.p, a.len * sizeof(T), a.role == SHARED);
+  else a.slot = P.out(a.p, a.len * sizeof(T));
+}
+template <class S> void declare(Pipeline &, S &) {}
+
+// The host form of dev_form: its parameter checks (no arrays, no items; a negative B goes through as it is), nothing to do at B = 0,
+// "<name>: NULL buffer" for a missing array, then the arrays through the Pipeline in argument order, one dev_form call per chunk.
+template <class Fn, class... A>
+int host_call(const char *name, ntru_engine_t *eng, int64_t B, Fn dev_form, A... a) {
+  if (int rc = dev_form(eng, dev_arg(a, 0, B < 0 ? B : 0, nullptr)...)) return rc;
   if (B == 0) return NTRU_OK;
-  if (!h || !r || !m || !e) return ntru_fail(NTRU_ERR_ARG, "ntru_encrypt_batch: NULL buffer");
+  if ((missing(a) || ...)) return ntru_fail(NTRU_ERR_ARG, std::string(name) + ": NULL buffer");
   Pipeline P(eng);
-  const int ih = P.in(h, (size_t)N * 2, true), ir = P.in(r, N), im = P.in(m, N), ie = P.out(e, (size_t)N * 2),
-            iq = P.out(quotE, (size_t)N * 2);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_encrypt_batch_dev(eng, N, q, (const uint16_t *)d[ih], (const uint8_t *)d[ir], (const uint8_t *)d[im], n,
-                                  (uint16_t *)d[ie], (uint16_t *)d[iq]);
-  });
+  (declare(P, a), ...);
+  return P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) { return dev_form(eng, dev_arg(a, o, n, d)...); });
+}
+}  // namespace
+
+// ---- several devices in ONE process: contiguous shards, one host thread + engine (with its three stage streams) per device ------
+// SURVEY.md 8(e): item b depends only on (key, m[b], r[b]) / (key, e[b]) / key[b], so a host batch is cut into contiguous
+// slices [g B / G, (g + 1) B / G) and every slice runs the single-device host form on its own thread; nothing is exchanged
+// between devices.  (The benchmark's multi-GPU mode is one PROCESS per GPU instead -- bench.py under torchrun; this is for a
+// host program, e.g. the Node.js addon, that owns all the GPUs of a node itself.)
+struct ntru_multi {
+  std::vector<ntru_engine_t *> eng;
+};
+
+extern "C" int ntru_multi_create(const int *device_ids, int n_dev, ntru_multi_t **out) {
+  if (!out) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_create: out is NULL");
+  *out = nullptr;
+  if (!device_ids || n_dev < 1 || n_dev > 64) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_create: need 1 .. 64 device ids");
+  ntru_multi *m = new ntru_multi;
+  for (int i = 0; i < n_dev; i++) {
+    ntru_engine_t *e = nullptr;
+    if (int rc = ntru_engine_create(device_ids[i], &e)) {
+      for (ntru_engine_t *x : m->eng) ntru_engine_destroy(x);
+      delete m;
+      return rc;
+    }
+    m->eng.push_back(e);
+  }
+  *out = m;
+  return NTRU_OK;
 }
 
+extern "C" void ntru_multi_destroy(ntru_multi_t *m) {
+  if (!m) return;
+  for (ntru_engine_t *e : m->eng) ntru_engine_destroy(e);
+  delete m;
+}
+
+extern "C" int ntru_multi_engines(const ntru_multi_t *m) { return m ? (int)m->eng.size() : 0; }
+
+namespace {
+// fn(engine, first item, items) on one thread per engine; the first failure (lowest shard) is what the caller sees
+template <class F>
+int for_each_shard(ntru_multi_t *m, int64_t B, F fn) {
+  if (!m) return ntru_fail(NTRU_ERR_ARG, "multi-device engine is NULL");
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "negative batch size");
+  const int G = (int)m->eng.size();
+  std::vector<int> rc(G, NTRU_OK);
+  std::vector<std::string> msg(G);
+  std::vector<std::thread> th;
+  auto shard = [&](int g) {
+    const int64_t base = B / G, extra = B % G, lo = g * base + (g < extra ? g : extra), n = base + (g < extra ? 1 : 0);
+    rc[g] = fn(m->eng[g], lo, n);
+    if (rc[g]) msg[g] = ntru_last_error();               // the message is per thread: carry it over
+  };
+  for (int g = 1; g < G; g++) th.emplace_back(shard, g);
+  shard(0);
+  for (auto &t : th) t.join();
+  for (int g = 0; g < G; g++)
+    if (rc[g]) return ntru_fail(rc[g], "device shard " + std::to_string(g) + ": " + msg[g]);
+  return NTRU_OK;
+}
+
+// The same argument list for the shard of n items from item lo on: rows per item move by lo rows, shared rows stay.
+template <class T> Arr<T> shard_arg(Arr<T> a, int64_t lo) {
+  if (a.p && a.role != SHARED) a.p += (size_t)lo * a.len;
+  return a;
+}
+inline First shard_arg(First f, int64_t lo) { return {f.v + (uint64_t)lo}; }
+template <class S> S shard_arg(S s, int64_t) { return s; }
+
+// Where a form runs: on one engine, or in shards on the engines of a multi-device engine.  Either takes (name, _dev form, arguments),
+// so a call that has both forms states its arguments once.
+auto on_engine(ntru_engine_t *eng, int64_t B) {
+  return [=](const char *name, auto dev_form, auto... a) { return host_call(name, eng, B, dev_form, a...); };
+}
+auto on_shards(ntru_multi_t *m, int64_t B) {
+  return [=](const char *name, auto dev_form, auto... a) {
+    return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) { return host_call(name, eng, n, dev_form, shard_arg(a, lo)...); });
+  };
+}
+template <class... P> bool any_null(const P *...p) { return (!p || ...); }
+}  // namespace
+
+// ---- the calls that have a multi-device form: arguments stated once, run on an engine or in shards ----------------------------------
+template <class Run>
+static int encrypt_form(Run run, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *m, uint16_t *e, uint16_t *quotE) {
+  return run("ntru_encrypt_batch", ntru_encrypt_batch_dev, N, q, shared(h, N), rows(r, N), rows(m, N), items, rows(e, N), optional(quotE, N));
+}
+extern "C" int ntru_encrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r,
+                                  const uint8_t *m, int64_t B, uint16_t *e, uint16_t *quotE) {
+  return encrypt_form(on_engine(eng, B), N, q, h, r, m, e, quotE);
+}
+extern "C" int ntru_multi_encrypt_batch(ntru_multi_t *m, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *mm,
+                                        int64_t B, uint16_t *e, uint16_t *quotE) {
+  return encrypt_form(on_shards(m, B), N, q, h, r, mm, e, quotE);
+}
+
+template <class Run>
+static int decrypt_form(Run run, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e, uint8_t *value, uint16_t *quot1,
+                        uint16_t *rem1, uint8_t *quot2) {
+  return run("ntru_decrypt_batch", ntru_decrypt_batch_dev, N, q, p, shared(f, N), shared(fp, N), rows(e, N), items, rows(value, N),
+             optional(quot1, N), optional(rem1, N), optional(quot2, N));
+}
 extern "C" int ntru_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
                                   const uint16_t *e, int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1,
                                   uint8_t *quot2) {
-  CHECK_ENGINE();
-  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !fp || !e || !value) return ntru_fail(NTRU_ERR_ARG, "ntru_decrypt_batch: NULL buffer");
-  Pipeline P(eng);
-  const int jf = P.in(f, N, true), jfp = P.in(fp, N, true), je = P.in(e, (size_t)N * 2), jv = P.out(value, N),
-            jq1 = P.out(quot1, (size_t)N * 2), jr1 = P.out(rem1, (size_t)N * 2), jq2 = P.out(quot2, N);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_decrypt_batch_dev(eng, N, q, p, (const int8_t *)d[jf], (const uint8_t *)d[jfp], (const uint16_t *)d[je], n,
-                                  (uint8_t *)d[jv], (uint16_t *)d[jq1], (uint16_t *)d[jr1], (uint8_t *)d[jq2]);
-  });
+  return decrypt_form(on_engine(eng, B), N, q, p, f, fp, e, value, quot1, rem1, quot2);
+}
+extern "C" int ntru_multi_decrypt_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, const uint8_t *fp,
+                                        const uint16_t *e, int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1,
+                                        uint8_t *quot2) {
+  return decrypt_form(on_shards(m, B), N, q, p, f, fp, e, value, quot1, rem1, quot2);
 }
 
+template <class Run>
+static int polymul_split_form(Run run, int N, int mod, const uint16_t *a, const uint16_t *b, uint16_t *quot, uint16_t *rem) {
+  return run("ntru_polymul_split", ntru_polymul_split_dev, N, mod, rows(a, N), rows(b, N), items, rows(quot, N), rows(rem, N));
+}
 extern "C" int ntru_polymul_split(ntru_engine_t *eng, int N, int mod, const uint16_t *a, const uint16_t *b,
                                   int64_t B, uint16_t *quot, uint16_t *rem) {
-  CHECK_ENGINE();
-  if (int rc = ntru_polymul_split_dev(eng, N, mod, nullptr, nullptr, 0, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!a || !b || !quot || !rem) return ntru_fail(NTRU_ERR_ARG, "ntru_polymul_split: NULL buffer");
-  Pipeline P(eng);
-  const size_t row = (size_t)N * 2;
-  const int ia = P.in(a, row), ib = P.in(b, row), iq = P.out(quot, row), ir = P.out(rem, row);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_polymul_split_dev(eng, N, mod, (const uint16_t *)d[ia], (const uint16_t *)d[ib], n, (uint16_t *)d[iq],
-                                  (uint16_t *)d[ir]);
-  });
+  return polymul_split_form(on_engine(eng, B), N, mod, a, b, quot, rem);
+}
+extern "C" int ntru_multi_polymul_split(ntru_multi_t *m, int N, int mod, const uint16_t *a, const uint16_t *b, int64_t B,
+                                        uint16_t *quot, uint16_t *rem) {
+  if (B > 0 && any_null(a, b, quot, rem)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_polymul_split: NULL buffer");
+  return polymul_split_form(on_shards(m, B), N, mod, a, b, quot, rem);
 }
 
+template <class Run>
+static int invert_key_form(Run run, int N, int q, int p, const int8_t *f, uint16_t *fq, uint8_t *fp, uint8_t *flags) {
+  if (!fq && !fp) flags = nullptr;       // "fq or fp, at least one": with neither, the call lacks a buffer as if flags were missing
+  return run("ntru_invert_key_batch", ntru_invert_key_batch_dev, N, q, p, rows(f, N), items, optional(fq, N), optional(fp, N), rows(flags, 1));
+}
 extern "C" int ntru_invert_key_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, int64_t B, uint16_t *fq,
                                      uint8_t *fp, uint8_t *flags) {
-  CHECK_ENGINE();
-  if (int rc = ntru_invert_key_batch_dev(eng, N, q, p, nullptr, 0, nullptr, nullptr, nullptr)) return rc;   // incl. p == 3
-  if (B == 0) return NTRU_OK;
-  if (!f || (!fq && !fp) || !flags) return ntru_fail(NTRU_ERR_ARG, "ntru_invert_key_batch: NULL buffer");
-  Pipeline P(eng);
-  const int jf = P.in(f, N), jfq = P.out(fq, (size_t)N * 2), jfp = P.out(fp, N), jfl = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_invert_key_batch_dev(eng, N, q, p, (const int8_t *)d[jf], n, (uint16_t *)d[jfq], (uint8_t *)d[jfp],
-                                     (uint8_t *)d[jfl]);
-  });
+  return invert_key_form(on_engine(eng, B), N, q, p, f, fq, fp, flags);
+}
+extern "C" int ntru_multi_invert_key_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, int64_t B, uint16_t *fq,
+                                           uint8_t *fp, uint8_t *flags) {
+  if (B > 0 && any_null(f, flags)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_invert_key_batch: NULL buffer");
+  return invert_key_form(on_shards(m, B), N, q, p, f, fq, fp, flags);
 }
 
+template <class Run>
+static int public_key_form(Run run, int N, int q, int p, const uint16_t *fq, const int8_t *g, uint16_t *h) {
+  return run("ntru_public_key_batch", ntru_public_key_batch_dev, N, q, p, rows(fq, N), rows(g, N), items, rows(h, N));
+}
 extern "C" int ntru_public_key_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *fq, const int8_t *g,
                                      int64_t B, uint16_t *h) {
-  CHECK_ENGINE();
-  if (int rc = ntru_public_key_batch_dev(eng, N, q, p, nullptr, nullptr, 0, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!fq || !g || !h) return ntru_fail(NTRU_ERR_ARG, "ntru_public_key_batch: NULL buffer");
-  Pipeline P(eng);
-  const int jfq = P.in(fq, (size_t)N * 2), jg = P.in(g, N), jh = P.out(h, (size_t)N * 2);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_public_key_batch_dev(eng, N, q, p, (const uint16_t *)d[jfq], (const int8_t *)d[jg], n, (uint16_t *)d[jh]);
-  });
+  return public_key_form(on_engine(eng, B), N, q, p, fq, g, h);
+}
+extern "C" int ntru_multi_public_key_batch(ntru_multi_t *m, int N, int q, int p, const uint16_t *fq, const int8_t *g, int64_t B,
+                                           uint16_t *h) {
+  if (B > 0 && any_null(fq, g, h)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_public_key_batch: NULL buffer");
+  return public_key_form(on_shards(m, B), N, q, p, fq, g, h);
 }
 
+template <class Run>
+static int verify_keys_form(Run run, int N, int q, int p, const int8_t *f, const int8_t *g, const uint16_t *fq, const uint8_t *fp,
+                            const uint16_t *h, uint16_t *quot_fq, uint16_t *rem_fq, uint8_t *quot_fp, uint8_t *rem_fp, uint16_t *quot_h,
+                            uint16_t *rem_h, uint8_t *flags) {
+  return run("ntru_verify_keys_batch", ntru_verify_keys_batch_dev, N, q, p, rows(f, N), rows(g, N), rows(fq, N), rows(fp, N), rows(h, N), items,
+             rows(quot_fq, N), rows(rem_fq, N), rows(quot_fp, N), rows(rem_fp, N), rows(quot_h, N), rows(rem_h, N), rows(flags, 1));
+}
 extern "C" int ntru_verify_keys_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const int8_t *g,
                                       const uint16_t *fq, const uint8_t *fp, const uint16_t *h, int64_t B,
                                       uint16_t *quot_fq, uint16_t *rem_fq, uint8_t *quot_fp, uint8_t *rem_fp,
                                       uint16_t *quot_h, uint16_t *rem_h, uint8_t *flags) {
-  CHECK_ENGINE();
-  if (int rc = ntru_verify_keys_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !g || !fq || !fp || !h || !quot_fq || !rem_fq || !quot_fp || !rem_fp || !quot_h || !rem_h || !flags)
-    return ntru_fail(NTRU_ERR_ARG, "ntru_verify_keys_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t r8 = (size_t)N, r16 = (size_t)N * 2;
-  const int jf = P.in(f, r8), jg = P.in(g, r8), jfq = P.in(fq, r16), jfp = P.in(fp, r8), jh = P.in(h, r16);
-  const int o1 = P.out(quot_fq, r16), o2 = P.out(rem_fq, r16), o3 = P.out(quot_fp, r8), o4 = P.out(rem_fp, r8),
-            o5 = P.out(quot_h, r16), o6 = P.out(rem_h, r16), ofl = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_verify_keys_batch_dev(eng, N, q, p, (const int8_t *)d[jf], (const int8_t *)d[jg], (const uint16_t *)d[jfq],
-                                      (const uint8_t *)d[jfp], (const uint16_t *)d[jh], n, (uint16_t *)d[o1], (uint16_t *)d[o2],
-                                      (uint8_t *)d[o3], (uint8_t *)d[o4], (uint16_t *)d[o5], (uint16_t *)d[o6], (uint8_t *)d[ofl]);
-  });
+  return verify_keys_form(on_engine(eng, B), N, q, p, f, g, fq, fp, h, quot_fq, rem_fq, quot_fp, rem_fp, quot_h, rem_h, flags);
+}
+extern "C" int ntru_multi_verify_keys_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, const int8_t *g,
+                                            const uint16_t *fq, const uint8_t *fp, const uint16_t *h, int64_t B,
+                                            uint16_t *quot_fq, uint16_t *rem_fq, uint8_t *quot_fp, uint8_t *rem_fp,
+                                            uint16_t *quot_h, uint16_t *rem_h, uint8_t *flags) {
+  if (B > 0 && any_null(f, g, fq, fp, h, quot_fq, rem_fq, quot_fp, rem_fp, quot_h, rem_h, flags))
+    return ntru_fail(NTRU_ERR_ARG, "ntru_multi_verify_keys_batch: NULL buffer");
+  return verify_keys_form(on_shards(m, B), N, q, p, f, g, fq, fp, h, quot_fq, rem_fq, quot_fp, rem_fp, quot_h, rem_h, flags);
 }
 
+// ---- the other regular calls -------------------------------------------------------------------------------------------------------
 extern "C" int ntru_split_by_I(ntru_engine_t *eng, int N, int mod, const uint16_t *a, int64_t B, uint16_t *quot,
                                uint16_t *rem) {
-  CHECK_ENGINE();
-  if (int rc = ntru_split_by_I_dev(eng, N, mod, nullptr, 0, nullptr, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!a || !quot || !rem) return ntru_fail(NTRU_ERR_ARG, "ntru_split_by_I: NULL buffer");
-  Pipeline P(eng);
-  const size_t row = (size_t)N * 2;
-  const int ia = P.in(a, 2 * row), iq = P.out(quot, row), ir = P.out(rem, row);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_split_by_I_dev(eng, N, mod, (const uint16_t *)d[ia], n, (uint16_t *)d[iq], (uint16_t *)d[ir]);
-  });
+  return host_call("ntru_split_by_I", eng, B, ntru_split_by_I_dev, N, mod, rows(a, 2 * (size_t)N), items, rows(quot, N), rows(rem, N));
 }
 
 extern "C" int ntru_add_batch(ntru_engine_t *eng, int N, int mod, const uint16_t *a, const uint16_t *b, int64_t B,
                               uint16_t *out) {
-  CHECK_ENGINE();
-  if (int rc = ntru_add_batch_dev(eng, N, mod, nullptr, nullptr, 0, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!a || !b || !out) return ntru_fail(NTRU_ERR_ARG, "ntru_add_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t row = (size_t)N * 2;
-  const int ia = P.in(a, row), ib = P.in(b, row), io = P.out(out, row);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_add_batch_dev(eng, N, mod, (const uint16_t *)d[ia], (const uint16_t *)d[ib], n, (uint16_t *)d[io]);
-  });
+  return host_call("ntru_add_batch", eng, B, ntru_add_batch_dev, N, mod, rows(a, N), rows(b, N), items, rows(out, N));
 }
 
 extern "C" int ntru_sample_ternary(ntru_engine_t *eng, int N, int n1, int n2, int other, const uint32_t *key,
                                    uint64_t first_item, int64_t B, uint8_t *out) {
-  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B > 0 && !out) return ntru_fail(NTRU_ERR_ARG, "ntru_sample_ternary: NULL buffer");
-  if (B <= 0) return ntru_sample_ternary_dev(eng, N, n1, n2, other, key, first_item, B, nullptr);
-  if (int rc = ntru_sample_ternary_dev(eng, N, n1, n2, other, key, first_item, 0, nullptr)) return rc;
-  Pipeline P(eng);
-  const int io = P.out(out, N);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) {
-    return ntru_sample_ternary_dev(eng, N, n1, n2, other, key, first_item + (uint64_t)o, n, (uint8_t *)d[io]);
-  });
+  if (eng && B > 0 && !out) return ntru_fail(NTRU_ERR_ARG, "ntru_sample_ternary: NULL buffer");   // ahead of the parameter checks here
+  return host_call("ntru_sample_ternary", eng, B, ntru_sample_ternary_dev, N, n1, n2, other, key, first(first_item), items, rows(out, N));
 }
 
 extern "C" int ntru_pack_batch(ntru_engine_t *eng, int max_val, int data_len, const uint16_t *data, int64_t B,
                                uint64_t *out) {
   if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
   int bits, per, al, os;
-  if (int rc = ntru_pack_params(max_val, data_len, &bits, &per, &al, &os)) return rc;
-  if (B <= 0) return B == 0 ? NTRU_OK : ntru_fail(NTRU_ERR_ARG, "negative batch size");
-  if ((!data && data_len) || !out) return ntru_fail(NTRU_ERR_ARG, "ntru_pack_batch: NULL buffer");
-  Pipeline P(eng);
-  const int ii = P.in(data_len ? data : nullptr, (size_t)data_len * 2), io = P.out(out, (size_t)os * 32);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_pack_batch_dev(eng, max_val, data_len, (const uint16_t *)d[ii], n, (uint64_t *)d[io]);
-  });
+  if (int rc = ntru_pack_params(max_val, data_len, &bits, &per, &al, &os)) return rc;                // ahead of the batch size here
+  if (B > 0 && !data && data_len) return ntru_fail(NTRU_ERR_ARG, "ntru_pack_batch: NULL buffer");   // rows of no elements need no array
+  return host_call("ntru_pack_batch", eng, B, ntru_pack_batch_dev, max_val, data_len, optional(data_len ? data : nullptr, data_len), items,
+                   rows(out, (size_t)os * 4));
 }
 
 extern "C" int ntru_unpack_batch(ntru_engine_t *eng, int max_val, int packed_bits, const uint64_t *in, int packed_size,
                                  int64_t B, uint16_t *out) {
-  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
-  if (int rc = ntru_unpack_batch_dev(eng, max_val, packed_bits, nullptr, packed_size, 0, nullptr)) return rc;
+  if (int rc = ntru_unpack_batch_dev(eng, max_val, packed_bits, nullptr, packed_size, 0, nullptr)) return rc;   // ahead of the batch size here
   if (B < 0) return ntru_fail(NTRU_ERR_ARG, "negative batch size");
-  if (B == 0 || packed_size == 0) return NTRU_OK;
-  if (!in || !out) return ntru_fail(NTRU_ERR_ARG, "ntru_unpack_batch: NULL buffer");
+  if (packed_size == 0) return NTRU_OK;
   int bits = 0;
   while ((max_val >> bits) != 0) bits++;
-  const int per = packed_bits / bits;
-  Pipeline P(eng);
-  const int ii = P.in(in, (size_t)packed_size * 32), io = P.out(out, (size_t)packed_size * per * 2);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_unpack_batch_dev(eng, max_val, packed_bits, (const uint64_t *)d[ii], packed_size, n, (uint16_t *)d[io]);
-  });
+  const size_t per = packed_bits / bits;
+  return host_call("ntru_unpack_batch", eng, B, ntru_unpack_batch_dev, max_val, packed_bits, rows(in, (size_t)packed_size * 4), packed_size, items,
+                   rows(out, (size_t)packed_size * per));
+}
+
+// per-item keys (matrix_peritem_scheme.hip)
+extern "C" int ntru_encrypt_peritem_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *m,
+                                          int64_t B, uint16_t *e, uint16_t *quotE) {
+  return host_call("ntru_encrypt_peritem_batch", eng, B, ntru_encrypt_peritem_batch_dev, N, q, rows(h, N), rows(r, N), rows(m, N), items,
+                   rows(e, N), optional(quotE, N));
+}
+
+extern "C" int ntru_decrypt_peritem_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e,
+                                          int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
+  return host_call("ntru_decrypt_peritem_batch", eng, B, ntru_decrypt_peritem_batch_dev, N, q, p, rows(f, N), rows(fp, N), rows(e, N), items,
+                   rows(value, N), optional(quot1, N), optional(rem1, N), optional(quot2, N));
+}
+
+// byte messages (message_bytes.hip)
+extern "C" int ntru_bytes_to_rows(ntru_engine_t *eng, int N, int nbytes, const uint8_t *bytes, int64_t B, uint8_t *m) {
+  return host_call("ntru_bytes_to_rows", eng, B, ntru_bytes_to_rows_dev, N, nbytes, rows(bytes, nbytes), items, rows(m, N));
+}
+
+extern "C" int ntru_rows_to_bytes(ntru_engine_t *eng, int N, int nbytes, const uint8_t *value, int64_t B, uint8_t *bytes, uint8_t *flags) {
+  return host_call("ntru_rows_to_bytes", eng, B, ntru_rows_to_bytes_dev, N, nbytes, rows(value, N), items, rows(bytes, nbytes), optional(flags, 1));
+}
+
+extern "C" int ntru_encrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int nbytes, const uint16_t *h, const uint8_t *r,
+                                        const uint8_t *bytes, int64_t B, uint16_t *e, uint16_t *quotE) {
+  return host_call("ntru_encrypt_bytes_batch", eng, B, ntru_encrypt_bytes_batch_dev, N, q, nbytes, shared(h, N), rows(r, N), rows(bytes, nbytes),
+                   items, rows(e, N), optional(quotE, N));
+}
+
+extern "C" int ntru_decrypt_bytes_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp,
+                                        const uint16_t *e, int64_t B, uint8_t *bytes, uint8_t *flags) {
+  return host_call("ntru_decrypt_bytes_batch", eng, B, ntru_decrypt_bytes_batch_dev, N, q, p, nbytes, shared(f, N), shared(fp, N), rows(e, N),
+                   items, rows(bytes, nbytes), optional(flags, 1));
+}
+
+// witness checks (witness_check.hip): their batch-size message comes ahead of the parameter checks
+extern "C" int ntru_check_encrypt_batch(ntru_engine_t *eng, int N, int q, int nq, const uint16_t *r, const uint16_t *m,
+                                        const uint16_t *h, const uint16_t *quotE, const uint16_t *remE, int64_t B, uint8_t *flags) {
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "witness check: negative batch size");
+  return host_call("ntru_check_encrypt_batch", eng, B, ntru_check_encrypt_batch_dev, N, q, nq, rows(r, N), rows(m, N), rows(h, N),
+                   rows(quotE, (size_t)N + 1), rows(remE, (size_t)N + 1), items, rows(flags, 1));
+}
+
+extern "C" int ntru_check_decrypt_batch(ntru_engine_t *eng, int N, int q, int nq, int p, int np, const uint16_t *f, const uint16_t *fp,
+                                        const uint16_t *e, const uint16_t *quot1, const uint16_t *rem1, const uint16_t *quot2,
+                                        const uint16_t *rem2, int64_t B, uint8_t *flags) {
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "witness check: negative batch size");
+  return host_call("ntru_check_decrypt_batch", eng, B, ntru_check_decrypt_batch_dev, N, q, nq, p, np, rows(f, N), rows(fp, N), rows(e, N),
+                   rows(quot1, (size_t)N + 1), rows(rem1, (size_t)N + 1), rows(quot2, (size_t)N + 1), rows(rem2, (size_t)N + 1), items,
+                   rows(flags, 1));
+}
+
+extern "C" int ntru_check_inverse_batch(ntru_engine_t *eng, int N, int M, int n, const uint16_t *f, const uint16_t *fq,
+                                        const uint16_t *quotI, const uint16_t *remI, int64_t B, uint8_t *flags) {
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "witness check: negative batch size");
+  return host_call("ntru_check_inverse_batch", eng, B, ntru_check_inverse_batch_dev, N, M, n, rows(f, N), rows(fq, N), rows(quotI, (size_t)N + 1),
+                   rows(remI, (size_t)N + 1), items, rows(flags, 1));
 }
 
 // ---- device-resident stages for a caller without HIP of its own (Node.js) -------------------------------------------------------
@@ -246,7 +404,8 @@ extern "C" int ntru_unpack_batch(ntru_engine_t *eng, int max_val, int packed_bit
 extern "C" int ntru_pipeline_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const int8_t *f, const uint8_t *fp,
                                    const uint32_t *key, uint64_t first_item, int n1, int n2, const uint8_t *r, const uint8_t *m,
                                    int64_t B, uint8_t *r_out, uint16_t *e, uint8_t *value, uint64_t *packed) {
-  CHECK_ENGINE();
+  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "negative batch size");
   const bool decrypt = f != nullptr || fp != nullptr;
   if (decrypt && (!f || !fp)) return ntru_fail(NTRU_ERR_ARG, "ntru_pipeline_batch: the decrypt stage needs both f and fp");
   if (!decrypt && value) return ntru_fail(NTRU_ERR_ARG, "ntru_pipeline_batch: `value` needs the decrypt stage (f, fp)");
@@ -327,121 +486,4 @@ extern "C" int ntru_dev_download(ntru_engine_t *eng, void *dst, const void *d_sr
   if (bytes) HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, eng->stream));
   HIP_TRY(hipStreamSynchronize(eng->stream));
   return NTRU_OK;
-}
-
-// ---- several devices in ONE process: contiguous shards, one host thread + engine (with its three stage streams) per device ------
-// SURVEY.md 8(e): item b depends only on (key, m[b], r[b]) / (key, e[b]) / key[b], so a host batch is cut into contiguous
-// slices [g B / G, (g + 1) B / G) and every slice runs the single-device pipeline above on its own thread; nothing is exchanged
-// between devices.  (The benchmark's multi-GPU mode is one PROCESS per GPU instead -- bench.py under torchrun; this is for a
-// host program, e.g. the Node.js addon, that owns all the GPUs of a node itself.)
-struct ntru_multi {
-  std::vector<ntru_engine_t *> eng;
-};
-
-extern "C" int ntru_multi_create(const int *device_ids, int n_dev, ntru_multi_t **out) {
-  if (!out) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_create: out is NULL");
-  *out = nullptr;
-  if (!device_ids || n_dev < 1 || n_dev > 64) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_create: need 1 .. 64 device ids");
-  ntru_multi *m = new ntru_multi;
-  for (int i = 0; i < n_dev; i++) {
-    ntru_engine_t *e = nullptr;
-    if (int rc = ntru_engine_create(device_ids[i], &e)) {
-      for (ntru_engine_t *x : m->eng) ntru_engine_destroy(x);
-      delete m;
-      return rc;
-    }
-    m->eng.push_back(e);
-  }
-  *out = m;
-  return NTRU_OK;
-}
-
-extern "C" void ntru_multi_destroy(ntru_multi_t *m) {
-  if (!m) return;
-  for (ntru_engine_t *e : m->eng) ntru_engine_destroy(e);
-  delete m;
-}
-
-extern "C" int ntru_multi_engines(const ntru_multi_t *m) { return m ? (int)m->eng.size() : 0; }
-
-namespace {
-// fn(engine, first item, items) on one thread per engine; the first failure (lowest shard) is what the caller sees
-template <class F>
-int for_each_shard(ntru_multi_t *m, int64_t B, F fn) {
-  if (!m) return ntru_fail(NTRU_ERR_ARG, "multi-device engine is NULL");
-  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "negative batch size");
-  const int G = (int)m->eng.size();
-  std::vector<int> rc(G, NTRU_OK);
-  std::vector<std::string> msg(G);
-  std::vector<std::thread> th;
-  auto shard = [&](int g) {
-    const int64_t base = B / G, extra = B % G, lo = g * base + (g < extra ? g : extra), n = base + (g < extra ? 1 : 0);
-    rc[g] = fn(m->eng[g], lo, n);
-    if (rc[g]) msg[g] = ntru_last_error();               // the message is per thread: carry it over
-  };
-  for (int g = 1; g < G; g++) th.emplace_back(shard, g);
-  shard(0);
-  for (auto &t : th) t.join();
-  for (int g = 0; g < G; g++)
-    if (rc[g]) return ntru_fail(rc[g], "device shard " + std::to_string(g) + ": " + msg[g]);
-  return NTRU_OK;
-}
-}  // namespace
-
-extern "C" int ntru_multi_encrypt_batch(ntru_multi_t *m, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *mm,
-                                        int64_t B, uint16_t *e, uint16_t *quotE) {
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_encrypt_batch(eng, N, q, h, r ? r + o : r, mm ? mm + o : mm, n, e ? e + o : e, quotE ? quotE + o : nullptr);
-  });
-}
-
-extern "C" int ntru_multi_decrypt_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, const uint8_t *fp,
-                                        const uint16_t *e, int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1,
-                                        uint8_t *quot2) {
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_decrypt_batch(eng, N, q, p, f, fp, e ? e + o : e, n, value ? value + o : value, quot1 ? quot1 + o : nullptr,
-                              rem1 ? rem1 + o : nullptr, quot2 ? quot2 + o : nullptr);
-  });
-}
-
-extern "C" int ntru_multi_verify_keys_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, const int8_t *g,
-                                            const uint16_t *fq, const uint8_t *fp, const uint16_t *h, int64_t B,
-                                            uint16_t *quot_fq, uint16_t *rem_fq, uint8_t *quot_fp, uint8_t *rem_fp,
-                                            uint16_t *quot_h, uint16_t *rem_h, uint8_t *flags) {
-  if (B > 0 && (!f || !g || !fq || !fp || !h || !quot_fq || !rem_fq || !quot_fp || !rem_fp || !quot_h || !rem_h || !flags))
-    return ntru_fail(NTRU_ERR_ARG, "ntru_multi_verify_keys_batch: NULL buffer");
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_verify_keys_batch(eng, N, q, p, f + o, g + o, fq + o, fp + o, h + o, n, quot_fq + o, rem_fq + o, quot_fp + o,
-                                  rem_fp + o, quot_h + o, rem_h + o, flags + lo);
-  });
-}
-
-extern "C" int ntru_multi_polymul_split(ntru_multi_t *m, int N, int mod, const uint16_t *a, const uint16_t *b, int64_t B,
-                                        uint16_t *quot, uint16_t *rem) {
-  if (B > 0 && (!a || !b || !quot || !rem)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_polymul_split: NULL buffer");
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_polymul_split(eng, N, mod, a + o, b + o, n, quot + o, rem + o);
-  });
-}
-
-extern "C" int ntru_multi_invert_key_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, int64_t B, uint16_t *fq,
-                                           uint8_t *fp, uint8_t *flags) {
-  if (B > 0 && (!f || !flags)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_invert_key_batch: NULL buffer");
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_invert_key_batch(eng, N, q, p, f + o, n, fq ? fq + o : nullptr, fp ? fp + o : nullptr, flags + lo);
-  });
-}
-
-extern "C" int ntru_multi_public_key_batch(ntru_multi_t *m, int N, int q, int p, const uint16_t *fq, const int8_t *g, int64_t B,
-                                           uint16_t *h) {
-  if (B > 0 && (!fq || !g || !h)) return ntru_fail(NTRU_ERR_ARG, "ntru_multi_public_key_batch: NULL buffer");
-  return for_each_shard(m, B, [&](ntru_engine_t *eng, int64_t lo, int64_t n) {
-    const size_t o = (size_t)lo * N;
-    return ntru_public_key_batch(eng, N, q, p, fq + o, g + o, n, h + o);
-  });
 }

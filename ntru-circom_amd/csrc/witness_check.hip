@@ -1,6 +1,6 @@
 // witness_check.hip -- batched witness checking against the reference's Verify* circuits (circuits/ntru.circom with circomlib
 // 2.0.5 LessThan / LessEqThan / IsEqual / IsZero / Num2Bits): VerifyEncrypt, VerifyDecrypt and VerifyInverse, their kernels, the
-// *_dev entry points and the host-pointer forms.
+// *_dev entry points (host-pointer forms: ntru_host.hip).
 //
 // Every witness entry is an integer in [0, 65536), so no signal leaves [0, 2^43) and the field arithmetic of the templates is
 // integer arithmetic.  Each template then reduces to ("Witness checks"):
@@ -355,55 +355,4 @@ extern "C" int ntru_check_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, in
   gt.hi = (int)std::min<long>(1l << 20, (long)(q / 2) + span);
   return launch_check(eng, k_check_decrypt, "k_check_decrypt", geom_of(N), B, stage_of(q, nq), stage_of(p, np), gt, d_f, d_fp, d_e,
                       d_quot1, d_rem1, d_quot2, d_rem2, (long)B, d_flags);
-}
-
-// ---- host-pointer forms: the chunked pipeline of ntru_host.hip -------------------------------------------------------------------
-
-extern "C" int ntru_check_encrypt_batch(ntru_engine_t *eng, int N, int q, int nq, const uint16_t *r, const uint16_t *m,
-                                        const uint16_t *h, const uint16_t *quotE, const uint16_t *remE, int64_t B, uint8_t *flags) {
-  if (B < 0) return fail(NTRU_ERR_ARG, "witness check: negative batch size");
-  if (int rc = ntru_check_encrypt_batch_dev(eng, N, q, nq, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!r || !m || !h || !quotE || !remE || !flags) return fail(NTRU_ERR_ARG, "ntru_check_encrypt_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t rn = (size_t)N * 2, rq = (size_t)(N + 1) * 2;
-  const int ir = P.in(r, rn), im = P.in(m, rn), ih = P.in(h, rn), iq = P.in(quotE, rq), ie = P.in(remE, rq), io = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_check_encrypt_batch_dev(eng, N, q, nq, (const uint16_t *)d[ir], (const uint16_t *)d[im], (const uint16_t *)d[ih],
-                                        (const uint16_t *)d[iq], (const uint16_t *)d[ie], n, (uint8_t *)d[io]);
-  });
-}
-
-extern "C" int ntru_check_decrypt_batch(ntru_engine_t *eng, int N, int q, int nq, int p, int np, const uint16_t *f, const uint16_t *fp,
-                                        const uint16_t *e, const uint16_t *quot1, const uint16_t *rem1, const uint16_t *quot2,
-                                        const uint16_t *rem2, int64_t B, uint8_t *flags) {
-  if (B < 0) return fail(NTRU_ERR_ARG, "witness check: negative batch size");
-  if (int rc = ntru_check_decrypt_batch_dev(eng, N, q, nq, p, np, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                                            nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !fp || !e || !quot1 || !rem1 || !quot2 || !rem2 || !flags) return fail(NTRU_ERR_ARG, "ntru_check_decrypt_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t rn = (size_t)N * 2, rq = (size_t)(N + 1) * 2;
-  const int jf = P.in(f, rn), jfp = P.in(fp, rn), je = P.in(e, rn), j1 = P.in(quot1, rq), j2 = P.in(rem1, rq), j3 = P.in(quot2, rq),
-            j4 = P.in(rem2, rq), jo = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t n, void **d) {
-    return ntru_check_decrypt_batch_dev(eng, N, q, nq, p, np, (const uint16_t *)d[jf], (const uint16_t *)d[jfp], (const uint16_t *)d[je],
-                                        (const uint16_t *)d[j1], (const uint16_t *)d[j2], (const uint16_t *)d[j3], (const uint16_t *)d[j4],
-                                        n, (uint8_t *)d[jo]);
-  });
-}
-
-extern "C" int ntru_check_inverse_batch(ntru_engine_t *eng, int N, int M, int n, const uint16_t *f, const uint16_t *fq,
-                                        const uint16_t *quotI, const uint16_t *remI, int64_t B, uint8_t *flags) {
-  if (B < 0) return fail(NTRU_ERR_ARG, "witness check: negative batch size");
-  if (int rc = ntru_check_inverse_batch_dev(eng, N, M, n, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!f || !fq || !quotI || !remI || !flags) return fail(NTRU_ERR_ARG, "ntru_check_inverse_batch: NULL buffer");
-  Pipeline P(eng);
-  const size_t rn = (size_t)N * 2, rq = (size_t)(N + 1) * 2;
-  const int jf = P.in(f, rn), jq = P.in(fq, rn), j1 = P.in(quotI, rq), j2 = P.in(remI, rq), jo = P.out(flags, 1);
-  return P.run(B, ntru_chunk_items(B), [&](int64_t, int64_t nn, void **d) {
-    return ntru_check_inverse_batch_dev(eng, N, M, n, (const uint16_t *)d[jf], (const uint16_t *)d[jq], (const uint16_t *)d[j1],
-                                        (const uint16_t *)d[j2], nn, (uint8_t *)d[jo]);
-  });
 }

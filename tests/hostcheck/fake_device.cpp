@@ -124,3 +124,83 @@ extern "C" int ntru_unpack_batch_dev(ntru_engine_t *eng, int max_val, int packed
   fake_enqueue(eng->stream, [=] { for (int64_t b = 0; b < B; b++) for (int j = 0; j < packed_size * per; j++) d_out[b * packed_size * per + j] = (uint16_t)(d_in[(b * packed_size + j / per) * 4] + j); });
   return NTRU_OK;
 }
+
+// ---- the entry points of matrix_peritem_scheme.hip, message_bytes.hip and witness_check.hip behind the regular host forms ------
+extern "C" int ntru_encrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint8_t *d_m,
+                                              int64_t B, uint16_t *d_e, uint16_t *d_quotE) {
+  if (int rc = ntru_check_common(eng, N, q, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_encrypt_peritem(N, q, d_h, d_r, d_m, B, d_e, d_quotE); });
+  return NTRU_OK;
+}
+extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp, const uint16_t *d_e,
+                                              int64_t B, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2) {
+  if (int rc = ntru_check_common(eng, N, q, B)) return rc;
+  if (int rc = ntru_check_decrypt_p(N, p)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_decrypt_peritem(N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1, d_rem1, d_quot2); });
+  return NTRU_OK;
+}
+static int fake_check_bytes(const ntru_engine *eng, int N, int nbytes, int64_t B) {
+  if (nbytes < 1 || nbytes > N / 8) return ntru_fail(NTRU_ERR_ARG, "fake device: need 1 <= nbytes <= N / 8");
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "fake device: negative batch size");
+  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
+  return NTRU_OK;
+}
+extern "C" int ntru_bytes_to_rows_dev(ntru_engine_t *eng, int N, int nbytes, const uint8_t *d_bytes, int64_t B, uint8_t *d_m) {
+  if (int rc = fake_check_bytes(eng, N, nbytes, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_bytes_to_rows(N, nbytes, d_bytes, B, d_m); });
+  return NTRU_OK;
+}
+extern "C" int ntru_rows_to_bytes_dev(ntru_engine_t *eng, int N, int nbytes, const uint8_t *d_value, int64_t B, uint8_t *d_bytes, uint8_t *d_flags) {
+  if (int rc = fake_check_bytes(eng, N, nbytes, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_rows_to_bytes(N, nbytes, d_value, B, d_bytes, d_flags); });
+  return NTRU_OK;
+}
+extern "C" int ntru_encrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int nbytes, const uint16_t *d_h, const uint8_t *d_r,
+                                            const uint8_t *d_bytes, int64_t B, uint16_t *d_e, uint16_t *d_quotE) {
+  if (int rc = fake_check_bytes(eng, N, nbytes, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_encrypt_bytes(N, q, nbytes, d_h, d_r, d_bytes, B, d_e, d_quotE); });
+  return NTRU_OK;
+}
+extern "C" int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *d_f, const uint8_t *d_fp,
+                                            const uint16_t *d_e, int64_t B, uint8_t *d_bytes, uint8_t *d_flags) {
+  if (int rc = fake_check_bytes(eng, N, nbytes, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { fake_decrypt_bytes(N, q, p, nbytes, d_f, d_fp, d_e, B, d_bytes, d_flags); });
+  return NTRU_OK;
+}
+static int fake_check_batch(ntru_engine *eng, int N, int64_t B) {
+  if (N < 2) return ntru_fail(NTRU_ERR_ARG, "fake device: need N >= 2");
+  if (B < 0) return ntru_fail(NTRU_ERR_ARG, "fake device: negative batch size");
+  if (!eng) return ntru_fail(NTRU_ERR_ARG, "engine is NULL");
+  return NTRU_OK;
+}
+extern "C" int ntru_check_encrypt_batch_dev(ntru_engine_t *eng, int N, int q, int nq, const uint16_t *d_r, const uint16_t *d_m, const uint16_t *d_h,
+                                            const uint16_t *d_quotE, const uint16_t *d_remE, int64_t B, uint8_t *d_flags) {
+  if (int rc = fake_check_batch(eng, N, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { const uint16_t *rows[] = {d_r, d_m, d_h, d_quotE, d_remE}; fake_check(N, q + nq, rows, 3, 2, B, d_flags); });
+  return NTRU_OK;
+}
+extern "C" int ntru_check_inverse_batch_dev(ntru_engine_t *eng, int N, int M, int n, const uint16_t *d_f, const uint16_t *d_fq, const uint16_t *d_quotI,
+                                            const uint16_t *d_remI, int64_t B, uint8_t *d_flags) {
+  if (int rc = fake_check_batch(eng, N, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] { const uint16_t *rows[] = {d_f, d_fq, d_quotI, d_remI}; fake_check(N, M + n, rows, 2, 2, B, d_flags); });
+  return NTRU_OK;
+}
+extern "C" int ntru_check_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int nq, int p, int np, const uint16_t *d_f, const uint16_t *d_fp,
+                                            const uint16_t *d_e, const uint16_t *d_quot1, const uint16_t *d_rem1, const uint16_t *d_quot2,
+                                            const uint16_t *d_rem2, int64_t B, uint8_t *d_flags) {
+  if (int rc = fake_check_batch(eng, N, B)) return rc;
+  if (B == 0) return NTRU_OK;
+  fake_enqueue(eng->stream, [=] {
+    const uint16_t *rows[] = {d_f, d_fp, d_e, d_quot1, d_rem1, d_quot2, d_rem2};
+    fake_check(N, q + nq + p + np, rows, 3, 4, B, d_flags);
+  });
+  return NTRU_OK;
+}

@@ -42,4 +42,52 @@ static inline void fake_verify(int N, int q, int p, const int8_t *f, const int8_
     flags[b] = (uint8_t)((fq[b * N] + h[b * N]) & 7);
   }
 }
+// The same with a key row per item (ntru_*_peritem_batch).
+static inline void fake_encrypt_peritem(int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *m, int64_t B, uint16_t *e, uint16_t *quot) {
+  for (int64_t b = 0; b < B; b++) fake_encrypt(N, q, h + b * N, r + b * N, m + b * N, 1, e + b * N, quot ? quot + b * N : nullptr);
+}
+static inline void fake_decrypt_peritem(int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e, int64_t B, uint8_t *value,
+                                        uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
+  for (int64_t b = 0; b < B; b++)
+    fake_decrypt(N, q, p, f + b * N, fp + b * N, e + b * N, 1, value + b * N, quot1 ? quot1 + b * N : nullptr, rem1 ? rem1 + b * N : nullptr,
+                 quot2 ? quot2 + b * N : nullptr);
+}
+// Byte messages: rows of nbytes bytes against rows of N coefficients.
+static inline void fake_bytes_to_rows(int N, int nbytes, const uint8_t *bytes, int64_t B, uint8_t *m) {
+  for (int64_t b = 0; b < B; b++)
+    for (int i = 0; i < N; i++) m[b * N + i] = (uint8_t)(bytes[b * nbytes + i % nbytes] + i);
+}
+static inline void fake_rows_to_bytes(int N, int nbytes, const uint8_t *value, int64_t B, uint8_t *bytes, uint8_t *flags) {
+  for (int64_t b = 0; b < B; b++) {
+    for (int j = 0; j < nbytes; j++) bytes[b * nbytes + j] = (uint8_t)(value[b * N + j] * 3 + value[b * N + N - 1 - j] + j);
+    if (flags) flags[b] = (uint8_t)((value[b * N] + value[b * N + N - 1]) & 3);
+  }
+}
+static inline void fake_encrypt_bytes(int N, int q, int nbytes, const uint16_t *h, const uint8_t *r, const uint8_t *bytes, int64_t B, uint16_t *e,
+                                      uint16_t *quot) {
+  for (int64_t b = 0; b < B; b++)
+    for (int i = 0; i < N; i++) {
+      const uint32_t v = (uint32_t)r[b * N + i] * 5u + bytes[b * nbytes + i % nbytes] * 3u + h[i] + (uint32_t)i;
+      e[b * N + i] = (uint16_t)(v & (uint32_t)(q - 1));
+      if (quot) quot[b * N + i] = (uint16_t)((v * 7u + 1u) & (uint32_t)(q - 1));
+    }
+}
+static inline void fake_decrypt_bytes(int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp, const uint16_t *e, int64_t B,
+                                      uint8_t *bytes, uint8_t *flags) {
+  for (int64_t b = 0; b < B; b++) {
+    for (int j = 0; j < nbytes; j++) bytes[b * nbytes + j] = (uint8_t)(e[b * N + j] + e[b * N + N - 1 - j] * 3 + (f[j] + 1) * 11 + fp[j] * 13 + p + j);
+    if (flags) flags[b] = (uint8_t)((e[b * N] + fp[N - 1] + q) & 3);
+  }
+}
+// Witness checks: k rows of N entries, then k1 rows of N + 1 entries, into one flag byte per item.
+static inline void fake_check(int N, int salt, const uint16_t *const *rows, int k, int k1, int64_t B, uint8_t *flags) {
+  for (int64_t b = 0; b < B; b++) {
+    uint32_t v = (uint32_t)salt;
+    for (int a = 0; a < k + k1; a++) {
+      const int len = a < k ? N : N + 1;
+      v = v * 3u + rows[a][b * len] + 5u * rows[a][b * len + len - 1];
+    }
+    flags[b] = (uint8_t)v;
+  }
+}
 #endif

@@ -1,8 +1,8 @@
 // Host-side sanitizer driver: the real abi.hip + ntru_host.hip, compiled as plain C++ against the fake HIP runtime and the fake
 // device (fake_hip.cpp, fake_device.cpp), run under AddressSanitizer + UBSan and under ThreadSanitizer.  What is exercised: engine
 // life cycle, the three-stage chunk pipeline (pinned and pageable buffers, single chunk / many chunks / ragged last chunk / empty batch),
-// optional outputs, the shared scratch buffer across two user streams, ntru_multi_* (one host thread per shard, unequal and empty
-// shards), two engines driven from two threads, error paths.  Expected values come from the same formulas applied to the whole batch.
+// optional outputs, every regular host form, the shared scratch buffer across two user streams, ntru_multi_* (one host thread per
+// shard, unequal and empty shards), two engines driven from two threads, error paths.  Expected values come from the same formulas applied to the whole batch.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -93,6 +93,92 @@ static void per_item(ntru_engine_t *eng, int N, int q, int64_t B, bool pin) {
   CHECK(same, "sample_ternary (item offsets across chunks), B=%ld", (long)B);
 }
 
+// The regular host forms that round_trip and per_item do not reach: per-item keys, byte messages, witness checks, split_by_I, pack and
+// unpack.  Each goes through the same runner (one description per call, ntru_host.hip); optional outputs asked for or not.
+template <class T>
+static void fill(Buf<T> &b, uint32_t mod, int bias = 0) { for (size_t i = 0; i < b.n; i++) b.p[i] = (T)((int)(rnd() % mod) + bias); }
+template <class T>
+static bool same(const Buf<T> &a, const Buf<T> &b) { return memcmp(a.p, b.p, a.n * sizeof(T)) == 0; }
+
+static void regular_forms(ntru_engine_t *eng, int N, int q, int64_t B, bool pin, bool opt) {
+  const int p = 3, nbytes = N / 8;
+  {   // per-item keys
+    Buf<uint16_t> h(B * N, pin), e(B * N, pin), quot(B * N, pin), e_want(B * N, false), quot_want(B * N, false);
+    Buf<uint8_t> r(B * N, pin), m(B * N, pin);
+    fill(h, q); fill(r, 3); fill(m, 2);
+    OK(ntru_encrypt_peritem_batch(eng, N, q, h.p, r.p, m.p, B, e.p, opt ? quot.p : nullptr));
+    fake_encrypt_peritem(N, q, h.p, r.p, m.p, B, e_want.p, quot_want.p);
+    CHECK(same(e, e_want) && (!opt || same(quot, quot_want)), "encrypt_peritem, B=%ld pin=%d opt=%d", (long)B, pin, opt);
+    Buf<int8_t> f(B * N, pin);
+    Buf<uint8_t> fp(B * N, pin), value(B * N, pin), q2(B * N, pin), value_want(B * N, false), q2_want(B * N, false);
+    Buf<uint16_t> q1(B * N, pin), r1(B * N, pin), q1_want(B * N, false), r1_want(B * N, false);
+    fill(f, 3, -1); fill(fp, 3);
+    OK(ntru_decrypt_peritem_batch(eng, N, q, p, f.p, fp.p, e.p, B, value.p, opt ? q1.p : nullptr, opt ? r1.p : nullptr, opt ? q2.p : nullptr));
+    fake_decrypt_peritem(N, q, p, f.p, fp.p, e.p, B, value_want.p, q1_want.p, r1_want.p, q2_want.p);
+    CHECK(same(value, value_want) && (!opt || (same(q1, q1_want) && same(r1, r1_want) && same(q2, q2_want))), "decrypt_peritem, B=%ld pin=%d opt=%d",
+          (long)B, pin, opt);
+  }
+  {   // byte messages
+    Buf<uint8_t> bytes(B * nbytes, pin), m(B * N, pin), m_want(B * N, false), back(B * nbytes, pin), back_want(B * nbytes, false), fl(B, pin), fl_want(B, false);
+    fill(bytes, 256);
+    OK(ntru_bytes_to_rows(eng, N, nbytes, bytes.p, B, m.p));
+    fake_bytes_to_rows(N, nbytes, bytes.p, B, m_want.p);
+    CHECK(same(m, m_want), "bytes_to_rows, B=%ld pin=%d", (long)B, pin);
+    OK(ntru_rows_to_bytes(eng, N, nbytes, m.p, B, back.p, opt ? fl.p : nullptr));
+    fake_rows_to_bytes(N, nbytes, m.p, B, back_want.p, fl_want.p);
+    CHECK(same(back, back_want) && (!opt || same(fl, fl_want)), "rows_to_bytes, B=%ld pin=%d opt=%d", (long)B, pin, opt);
+    Buf<uint16_t> h(N, false), e(B * N, pin), quot(B * N, pin), e_want(B * N, false), quot_want(B * N, false);
+    Buf<uint8_t> r(B * N, pin), fp(N, false);
+    Buf<int8_t> f(N, false);
+    fill(h, q); fill(r, 3); fill(f, 3, -1); fill(fp, 3);
+    OK(ntru_encrypt_bytes_batch(eng, N, q, nbytes, h.p, r.p, bytes.p, B, e.p, opt ? quot.p : nullptr));
+    fake_encrypt_bytes(N, q, nbytes, h.p, r.p, bytes.p, B, e_want.p, quot_want.p);
+    CHECK(same(e, e_want) && (!opt || same(quot, quot_want)), "encrypt_bytes, B=%ld pin=%d opt=%d", (long)B, pin, opt);
+    OK(ntru_decrypt_bytes_batch(eng, N, q, p, nbytes, f.p, fp.p, e.p, B, back.p, opt ? fl.p : nullptr));
+    fake_decrypt_bytes(N, q, p, nbytes, f.p, fp.p, e.p, B, back_want.p, fl_want.p);
+    CHECK(same(back, back_want) && (!opt || same(fl, fl_want)), "decrypt_bytes, B=%ld pin=%d opt=%d", (long)B, pin, opt);
+  }
+  if (opt) {   // witness checks (no optional arrays): three or two rows of N entries, four or two of N + 1
+    Buf<uint16_t> a0(B * N, pin), a1(B * N, pin), a2(B * N, pin), b0(B * (N + 1), pin), b1(B * (N + 1), pin), b2(B * (N + 1), pin), b3(B * (N + 1), pin);
+    Buf<uint8_t> fl(B, pin), fl_want(B, false);
+    for (Buf<uint16_t> *x : {&a0, &a1, &a2, &b0, &b1, &b2, &b3}) fill(*x, q);
+    const uint16_t *enc[] = {a0.p, a1.p, a2.p, b0.p, b1.p}, *dec[] = {a0.p, a1.p, a2.p, b0.p, b1.p, b2.p, b3.p}, *inv[] = {a0.p, a1.p, b0.p, b1.p};
+    OK(ntru_check_encrypt_batch(eng, N, q, 11, a0.p, a1.p, a2.p, b0.p, b1.p, B, fl.p));
+    fake_check(N, q + 11, enc, 3, 2, B, fl_want.p);
+    CHECK(same(fl, fl_want), "check_encrypt, B=%ld pin=%d", (long)B, pin);
+    OK(ntru_check_decrypt_batch(eng, N, q, 11, p, 2, a0.p, a1.p, a2.p, b0.p, b1.p, b2.p, b3.p, B, fl.p));
+    fake_check(N, q + 11 + p + 2, dec, 3, 4, B, fl_want.p);
+    CHECK(same(fl, fl_want), "check_decrypt, B=%ld pin=%d", (long)B, pin);
+    OK(ntru_check_inverse_batch(eng, N, q, 11, a0.p, a1.p, b0.p, b1.p, B, fl.p));
+    fake_check(N, q + 11, inv, 2, 2, B, fl_want.p);
+    CHECK(same(fl, fl_want), "check_inverse, B=%ld pin=%d", (long)B, pin);
+    CHECK(ntru_check_inverse_batch(eng, N, q, 11, a0.p, a1.p, b0.p, b1.p, -1, fl.p) != 0 && strstr(ntru_last_error(), "witness check: negative batch size"),
+          "the witness checks' own batch-size message");
+    // split_by_I: rows of 2 N in; pack: rows of os field elements out; unpack: row lengths from the bit width
+    Buf<uint16_t> wide(B * 2 * N, pin), lo(B * N, pin), hi(B * N, pin);
+    fill(wide, q);
+    OK(ntru_split_by_I(eng, N, q, wide.p, B, lo.p, hi.p));
+    bool ok = true;
+    for (int64_t i = 0; i < B * N && ok; i++) ok = lo.p[i] == (uint16_t)((wide.p[2 * i] + 1) % q) && hi.p[i] == (uint16_t)((wide.p[2 * i + 1] + 2) % q);
+    CHECK(ok, "split_by_I, B=%ld pin=%d", (long)B, pin);
+    int bits, per, al, os;
+    OK(ntru_pack_params(q - 1, N, &bits, &per, &al, &os));
+    Buf<uint64_t> packed(B * os * 4, pin);
+    OK(ntru_pack_batch(eng, q - 1, N, a0.p, B, packed.p));
+    ok = true;
+    for (int64_t b = 0; b < B && ok; b++) for (int j = 0; j < os * 4 && ok; j++) ok = packed.p[b * os * 4 + j] == (uint64_t)a0.p[b * N + j % N] * 0x10001ull + j;
+    CHECK(ok, "pack_batch, B=%ld pin=%d", (long)B, pin);
+    Buf<uint16_t> unpacked(B * os * per, pin);
+    OK(ntru_unpack_batch(eng, q - 1, per * bits, packed.p, os, B, unpacked.p));
+    ok = true;
+    for (int64_t b = 0; b < B && ok; b++) for (int j = 0; j < os * per && ok; j++) ok = unpacked.p[b * os * per + j] == (uint16_t)(packed.p[(b * os + j / per) * 4] + j);
+    CHECK(ok, "unpack_batch, B=%ld pin=%d", (long)B, pin);
+    OK(ntru_unpack_batch(eng, q - 1, per * bits, nullptr, 0, B, nullptr));       // packed_size == 0: nothing to move
+    OK(ntru_pack_batch(eng, q - 1, N, nullptr, 0, nullptr));
+    CHECK(ntru_pack_batch(eng, q - 1, N, nullptr, B, packed.p) != 0 && strstr(ntru_last_error(), "ntru_pack_batch: NULL buffer"), "pack without data");
+  }
+}
+
 // ntru_pipeline_batch: device-only intermediates (r, e), optional outputs, several chunks
 static void pipeline(ntru_engine_t *eng, int N, int q, int64_t B, bool pin) {
   const int p = 3;
@@ -161,6 +247,32 @@ static void multi(int N, int q) {
     std::vector<uint8_t> d3(B * N);
     fake_decrypt(N, q, 3, f.data(), fp.data(), e.data(), B, vw.data(), d1.data(), d2.data(), d3.data());
     CHECK(v == vw, "multi decrypt (value only), B=%ld", (long)B);
+    if (B > 1000) continue;
+    // the per-item calls: every array moves with its shard, flags by one byte per item
+    std::vector<int8_t> fi(B * N), g(B * N);
+    std::vector<uint16_t> fq(B * N), hh(B * N), o1(B * N), o2(B * N), o5(B * N), o6(B * N), w1(B * N), w2(B * N), w5(B * N), w6(B * N);
+    std::vector<uint8_t> fpi(B * N), o3(B * N), o4(B * N), fl(B), w3(B * N), w4(B * N), wf(B);
+    for (int64_t i = 0; i < B * N; i++) { fi[i] = (int8_t)((int)(rnd() % 3) - 1); g[i] = (int8_t)((int)(rnd() % 3) - 1); fq[i] = (uint16_t)(rnd() % q);
+                                           hh[i] = (uint16_t)(rnd() % q); fpi[i] = (uint8_t)(rnd() % 3); }
+    OK(ntru_multi_verify_keys_batch(mu, N, q, 3, fi.data(), g.data(), fq.data(), fpi.data(), hh.data(), B, o1.data(), o2.data(), o3.data(), o4.data(),
+                                    o5.data(), o6.data(), fl.data()));
+    fake_verify(N, q, 3, fi.data(), g.data(), fq.data(), fpi.data(), hh.data(), B, w1.data(), w2.data(), w3.data(), w4.data(), w5.data(), w6.data(), wf.data());
+    CHECK(o1 == w1 && o2 == w2 && o3 == w3 && o4 == w4 && o5 == w5 && o6 == w6 && fl == wf, "multi verify_keys, B=%ld", (long)B);
+    OK(ntru_multi_polymul_split(mu, N, q, fq.data(), hh.data(), B, o1.data(), o2.data()));
+    fake_polymul(N, q, fq.data(), hh.data(), B, w1.data(), w2.data());
+    CHECK(o1 == w1 && o2 == w2, "multi polymul_split, B=%ld", (long)B);
+    OK(ntru_multi_public_key_batch(mu, N, q, 3, fq.data(), g.data(), B, o1.data()));
+    fake_public_key(N, q, 3, fq.data(), g.data(), B, w1.data());
+    CHECK(o1 == w1, "multi public_key, B=%ld", (long)B);
+    OK(ntru_multi_invert_key_batch(mu, N, q, 3, fi.data(), B, nullptr, o3.data(), fl.data()));       // fp only
+    bool same_fp = true;
+    for (int64_t i = 0; i < B * N && same_fp; i++) same_fp = o3[i] == (uint8_t)((fi[i] + 4) % 3);
+    for (int64_t b = 0; b < B && same_fp; b++) same_fp = fl[b] == (uint8_t)(fi[b * N] & 1);
+    CHECK(same_fp, "multi invert_key (fp only), B=%ld", (long)B);
+    CHECK(ntru_multi_invert_key_batch(mu, N, q, 3, fi.data(), B, nullptr, nullptr, fl.data()) != 0 &&
+          strstr(ntru_last_error(), "device shard 0: ntru_invert_key_batch: NULL buffer"), "multi invert_key without fq and fp");
+    CHECK(ntru_multi_public_key_batch(mu, N, q, 3, fq.data(), nullptr, B, o1.data()) != 0 &&
+          strstr(ntru_last_error(), "ntru_multi_public_key_batch: NULL buffer"), "the multi forms' own NULL check");
   }
   ntru_multi_destroy(mu);
 }
@@ -197,6 +309,14 @@ int main() {
     for (int64_t B : {(int64_t)1, (int64_t)(1 << 15) + 9, (int64_t)2 * (1 << 15) + 1}) per_item(eng, N, q, B, pin);
 #endif
   round_trip(eng, N, q, 1000, false, false);
+  // B = 1, one chunk, four even chunks, four chunks with a ragged last one (8197 = 3 * 2050 + 2047)
+  for (bool pin : {false, true})
+#ifdef HOSTCHECK_QUICK
+    for (int64_t B : {(int64_t)1, (int64_t)8197}) regular_forms(eng, N, q, B, pin, B == 1 ? !pin : pin);
+#else
+    for (int64_t B : {(int64_t)1, (int64_t)1000, (int64_t)8200, (int64_t)8197})
+      for (bool opt : {true, false}) regular_forms(eng, N, q, B, pin, opt);
+#endif
   for (bool pin : {false, true})
     for (int64_t B : {(int64_t)1, (int64_t)9001, (int64_t)4 * (1 << 15) + 3}) pipeline(eng, N, q, B, pin);
   {   // plain device buffers
