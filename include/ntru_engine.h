@@ -177,6 +177,44 @@ int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const 
                                  const uint16_t *d_rows, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K, int64_t G,
                                  uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2);
 
+/* ---- packed ciphertexts: the three calls above and decryptBits on ciphertexts that arrive in the circuits' wire format,
+ *      packOutput(mod - 1, N, e) (index.js:572-596) -- what CombineArray makes public and what ntru_encrypt_pack_batch_dev,
+ *      ntru_pipeline_batch(packed) and ntru_keygen_batch(packed_h) emit -- without unpacking them first.
+ *      packed: [B][output_size][4] uint64_t with (bits, per, arr_len, output_size) = ntru_pack_params(mod - 1, N, ...): a row is
+ *      output_size field elements of four little-endian limbs, coefficient i is the bits-wide field at bit (i % per) * bits of element
+ *      i / per (fields may straddle limbs).  Fields with index >= N and the bits of an element above per * bits are IGNORED, whatever
+ *      they hold, as unpackInput's mask (index.js:598-620) ignores them.  Any 8-byte aligned address will do.
+ *   ntru_sum_groups_packed   ntru_sum_groups on the unpacked rows: the same arguments, groups, weights, domain, exactness and checks, and
+ *                          the same bytes in out, dense [G][N] (a raw field is below 2^bits <= 65536, so the sums are exact for fields that
+ *                          are not below mod as well).  One kernel reads the packed rows once, 32 output_size bytes per row
+ *                          (k_sum_groups_packed; groups that are split over wavefronts are completed by k_sum_groups_finish).
+ *                          _dev: d_offsets is a DEVICE array that is neither read on the host nor waited for; no synchronisation;
+ *                          scratch bounded by N and the grid; nothing allocated per call.  G == 0 launches nothing.
+ *                          host form: validates offsets and weights (NTRU_ERR_ARG before any launch), streams the packed rows through the
+ *                          chunked pipeline and accumulates a group larger than a chunk across chunks.
+ *   ntru_tally_decrypt_packed_batch   ntru_tally_decrypt_batch with packed rows: ntru_sum_groups_packed modulo q into sum (dense [G][N],
+ *                          needed as the intermediate), then the decrypt of ntru_tally_decrypt_batch.
+ *   ntru_decrypt_packed_batch   ntru_decrypt_batch of the unpacked rows: row b of value, quot1, rem1, quot2 (the last three may be NULL)
+ *                          is bit-identical to ntru_decrypt_batch on unpacked row b.  The rows are unpacked (k_unpack_rows) into the
+ *                          engine-owned scratch buffer in passes of at most 65536 rows and decrypted by the kernels ntru_decrypt_batch_dev
+ *                          picks; the _dev form does not synchronise and allocates nothing per call. */
+int ntru_sum_groups_packed(ntru_engine_t *eng, int N, int mod, const uint64_t *packed, const uint16_t *weights,
+                           const int64_t *offsets, int64_t K, int64_t G, uint16_t *out);
+int ntru_sum_groups_packed_dev(ntru_engine_t *eng, int N, int mod, const uint64_t *d_packed, const uint16_t *d_weights,
+                               const int64_t *d_offsets, int64_t K, int64_t G, uint16_t *d_out);
+int ntru_tally_decrypt_packed_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
+                                    const uint64_t *packed, const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G,
+                                    uint16_t *sum, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2);
+int ntru_tally_decrypt_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
+                                        const uint64_t *d_packed, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K,
+                                        int64_t G, uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
+                                        uint8_t *d_quot2);
+int ntru_decrypt_packed_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint64_t *packed,
+                              int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2);
+int ntru_decrypt_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
+                                  const uint64_t *d_packed, int64_t B, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
+                                  uint8_t *d_quot2);
+
 /* ---- on-device ternary sampler: generateCustomArray(N, n1, n2) (index.js:461-488) for B items, so that encryptBits'
  *      randomness r never crosses PCIe.  Row b (item index first_item + b) gets n1 ones, n2 entries equal to `other`
  *      (2 = p-1 for r after the index.js:89 map) and zeros, shuffled exactly like the reference: for i = N-1 .. 1:

@@ -33,6 +33,7 @@
 #include <string>
 
 #include "kernels_common.h"
+#include "sum_groups_common.h"
 
 typedef unsigned long long u64;
 
@@ -48,39 +49,6 @@ typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef u32 u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
-
-// The groups of one launch.  off != NULL: group g is rows [off[g], off[g + 1]); else rows [(g0 + g) K, (g0 + g + 1) K).  Both
-// clamped to the window [wlo, whi) (the host form's chunk; everything for the _dev form); row r lies at rows + (r - wlo) N.
-struct Groups {
-  const long *off;
-  long K, g0, G, wlo, whi;
-};
-
-__device__ __forceinline__ long g_start(const Groups &gr, long g) {
-  const long s = gr.off ? gr.off[g] : (gr.g0 + g) * gr.K;
-  return s < gr.wlo ? gr.wlo : (s > gr.whi ? gr.whi : s);
-}
-
-// rows [base, end) in blocks of R; blocks 0 .. nb - 1 exist (block 0 always does)
-struct Cut {
-  long base, end, R, nb;
-};
-__device__ __forceinline__ Cut cut_of(const Groups &gr, long Pb) {
-  Cut c;
-  c.base = g_start(gr, 0);
-  c.end = g_start(gr, gr.G);
-  const long T = c.end - c.base;
-  c.R = T > Pb ? (T + Pb - 1) / Pb : 1;
-  c.nb = T > 0 ? (T + c.R - 1) / c.R : 1;
-  return c;
-}
-
-__device__ __forceinline__ u32 mod_u64(u64 x, u32 M) {
-  if ((x >> 32) == 0) return (u32)x % M;
-  u32 r = (u32)(x >> 32) % M;                       // two 16-bit Horner steps below: r < M <= 65536, so (r << 16) | . fits u32
-  r = ((r << 16) | ((u32)x >> 16)) % M;
-  return ((r << 16) | ((u32)x & 0xffffu)) % M;
-}
 
 // The 8 coefficients at p (2-byte aligned), as u32, from the aligned 16 bytes at or just below p and the dword behind them.  The
 // caller has checked that p + 10 elements lie inside the array, so a batch of these loads has no branch between them.
@@ -268,7 +236,9 @@ __global__ void __launch_bounds__(FIN_COLS * FIN_SLICES) k_sum_groups_finish(int
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 
-int check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t K, int64_t G, const char *who) {
+}  // namespace
+
+int ntru_check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t K, int64_t G, const char *who) {
   if (N < 2 || N > NTRU_MAX_N)
     return fail(NTRU_ERR_ARG, std::string(who) + ": need 2 <= N <= " + std::to_string(NTRU_MAX_N) + ", got N = " + std::to_string(N));
   if (mod < 2 || mod > 65536) return fail(NTRU_ERR_ARG, std::string(who) + ": need 2 <= mod <= 65536, got " + std::to_string(mod));
@@ -279,66 +249,64 @@ int check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t
   return NTRU_OK;
 }
 
-long blocks_of(const ntru_engine *eng, int N) {
-  const int NT = (N + SG_TILE - 1) / SG_TILE;
-  const long pb = (long)eng->cus * SG_WAVES_PER_CU / NT;
-  return pb < 1 ? 1 : (pb > 32768 ? 32768 : pb);
-}
+namespace {
 
-// Enqueues the sums of the groups `gr` of the rows at d_rows (row gr.wlo first) into d_out (group 0 of gr first).
-int launch_sum(ntru_engine *eng, int N, int mod, const uint16_t *d_rows, const uint16_t *d_weights, const Groups &gr, uint16_t *d_out) {
+// Enqueues the sums of the groups `w` of the dense rows at d_rows (row w.wlo first) into d_out (group 0 of w first).
+int launch_sum(ntru_engine *eng, int N, int mod, const void *d_rows, const uint16_t *d_weights, const SumWindow &w, uint16_t *d_out) {
   HIP_TRY(hipSetDevice(eng->device));
   const int NT = (N + SG_TILE - 1) / SG_TILE;
-  long Pb = blocks_of(eng, N);
-  if (!gr.off) {                                      // uniform groups: the host knows the row count
-    long T = std::min(gr.whi, (gr.g0 + gr.G) * gr.K) - std::max(gr.wlo, gr.g0 * gr.K);
-    if (T < 1) T = 1;
-    if (Pb > T) Pb = T;
-  }
+  const long Pb = sum_row_blocks(eng, NT, SG_WAVES_PER_CU, w);
   ScratchHold hold(eng, (size_t)Pb * 8 + (size_t)Pb * 2 * N * 4);
   if (hold.rc) return hold.rc;
   long *meta = (long *)hold.p;
   u32 *part = (u32 *)(hold.p + (size_t)Pb * 8);
+  const Groups gr = groups_of(w);
   const bool pow2 = is_pow2(mod);
   const dim3 grid((unsigned)((Pb * NT + SG_THREADS / 64 - 1) / (SG_THREADS / 64)));
-#define SG_LAUNCH(P2, WT)                                                                                                       \
-  hipLaunchKernelGGL((k_sum_groups<P2, WT>), grid, dim3(SG_THREADS), 0, eng->stream, N, (u32)mod, gr, d_rows, d_weights, NT, Pb, \
-                     part, meta, d_out)
+#define SG_LAUNCH(P2, WT)                                                                                                              \
+  hipLaunchKernelGGL((k_sum_groups<P2, WT>), grid, dim3(SG_THREADS), 0, eng->stream, N, (u32)mod, gr, (const u16 *)d_rows, d_weights, NT, \
+                     Pb, part, meta, d_out)
   if (pow2) { if (d_weights) SG_LAUNCH(true, true); else SG_LAUNCH(true, false); }
   else { if (d_weights) SG_LAUNCH(false, true); else SG_LAUNCH(false, false); }
 #undef SG_LAUNCH
   HIP_TRY(hipGetLastError());
-  if (Pb > 1) {
-    const dim3 fgrid((unsigned)((N + FIN_COLS - 1) / FIN_COLS), (unsigned)std::min<long>(FIN_Y, Pb - 1));
-    if (pow2)
-      hipLaunchKernelGGL(k_sum_groups_finish<true>, fgrid, dim3(FIN_COLS * FIN_SLICES), 0, eng->stream, N, (u32)mod, gr, Pb, part, meta,
-                         d_out);
-    else
-      hipLaunchKernelGGL(k_sum_groups_finish<false>, fgrid, dim3(FIN_COLS * FIN_SLICES), 0, eng->stream, N, (u32)mod, gr, Pb, part, meta,
-                         d_out);
-    HIP_TRY(hipGetLastError());
-  }
+  if (int rc = ntru_launch_sum_finish(eng, N, mod, w, Pb, part, meta, d_out)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sum_groups<%d,%d>", (int)pow2, d_weights ? 1 : 0);
   return NTRU_OK;
 }
 
 }  // namespace
 
+// (behind launch_sum: the kernels keep the order in the code object that they had)
+int ntru_launch_sum_finish(ntru_engine *eng, int N, int mod, const SumWindow &w, long Pb, const uint32_t *d_part, const long *d_meta,
+                           uint16_t *d_out) {
+  if (Pb <= 1) return NTRU_OK;
+  const Groups gr = groups_of(w);
+  const dim3 fgrid((unsigned)((N + FIN_COLS - 1) / FIN_COLS), (unsigned)std::min<long>(FIN_Y, Pb - 1));
+  if (is_pow2(mod))
+    hipLaunchKernelGGL(k_sum_groups_finish<true>, fgrid, dim3(FIN_COLS * FIN_SLICES), 0, eng->stream, N, (u32)mod, gr, Pb, d_part, d_meta,
+                       d_out);
+  else
+    hipLaunchKernelGGL(k_sum_groups_finish<false>, fgrid, dim3(FIN_COLS * FIN_SLICES), 0, eng->stream, N, (u32)mod, gr, Pb, d_part, d_meta,
+                       d_out);
+  HIP_TRY(hipGetLastError());
+  return NTRU_OK;
+}
+
 extern "C" int ntru_sum_groups_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_rows, const uint16_t *d_weights,
                                    const int64_t *d_offsets, int64_t K, int64_t G, uint16_t *d_out) {
-  if (int rc = check_sum_args(eng, N, mod, !d_offsets, K, G, "ntru_sum_groups")) return rc;
+  if (int rc = ntru_check_sum_args(eng, N, mod, !d_offsets, K, G, "ntru_sum_groups")) return rc;
   if (G == 0) return NTRU_OK;
   if (!d_rows || !d_out) return fail(NTRU_ERR_ARG, "ntru_sum_groups: NULL buffer");
-  Groups gr;
-  gr.off = (const long *)d_offsets; gr.K = d_offsets ? 0 : K; gr.g0 = 0; gr.G = G; gr.wlo = 0; gr.whi = 0x7fffffffffffffffL;
-  return launch_sum(eng, N, mod, d_rows, d_weights, gr, d_out);
+  const SumWindow w = {d_offsets, d_offsets ? 0 : K, 0, G, 0, 0x7fffffffffffffffL};
+  return launch_sum(eng, N, mod, d_rows, d_weights, w, d_out);
 }
 
 extern "C" int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
                                             const uint16_t *d_rows, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K,
                                             int64_t G, uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
                                             uint8_t *d_quot2) {
-  if (int rc = check_sum_args(eng, N, q, !d_offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
+  if (int rc = ntru_check_sum_args(eng, N, q, !d_offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
   if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
   if (G == 0) return NTRU_OK;
   if (!d_f || !d_fp || !d_rows || !d_sum || !d_value) return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_batch: NULL buffer (d_sum is needed as the intermediate)");
@@ -351,34 +319,35 @@ extern "C" int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, in
 // A chunk is a window of rows: the groups that lie inside it are stored, the group that reaches into it from the chunk before is summed
 // on its own and added to what is already there (ntru_add_batch_dev), the group that leaves it stores its part for the next chunk.
 
-extern "C" int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_t *rows, const uint16_t *weights,
-                               const int64_t *offsets, int64_t K, int64_t G, uint16_t *out) {
-  if (int rc = check_sum_args(eng, N, mod, !offsets, K, G, "ntru_sum_groups")) return rc;
+int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, const void *rows, size_t row_bytes, const uint16_t *weights,
+                         const int64_t *offsets, int64_t K, int64_t G, uint16_t *out, ntru_sum_launcher launch_sum) {
+  if (int rc = ntru_check_sum_args(eng, N, mod, !offsets, K, G, who)) return rc;
   if (G == 0) return NTRU_OK;
-  if (!out) return fail(NTRU_ERR_ARG, "ntru_sum_groups: NULL buffer");
+  const std::string name(who);
+  if (!out) return fail(NTRU_ERR_ARG, name + ": NULL buffer");
   if (offsets) {
-    if (offsets[0] < 0) return fail(NTRU_ERR_ARG, "ntru_sum_groups: offsets[0] is negative");
+    if (offsets[0] < 0) return fail(NTRU_ERR_ARG, name + ": offsets[0] is negative");
     for (int64_t g = 0; g < G; g++)
-      if (offsets[g + 1] < offsets[g]) return fail(NTRU_ERR_ARG, "ntru_sum_groups: offsets decrease at group " + std::to_string(g));
+      if (offsets[g + 1] < offsets[g]) return fail(NTRU_ERR_ARG, name + ": offsets decrease at group " + std::to_string(g));
   }
   const int64_t lo = offsets ? offsets[0] : 0, hi = offsets ? offsets[G] : G * K, B = hi - lo;
-  if (B > 0 && !rows) return fail(NTRU_ERR_ARG, "ntru_sum_groups: NULL buffer");
+  if (B > 0 && !rows) return fail(NTRU_ERR_ARG, name + ": NULL buffer");
   for (int64_t r = 0; weights && r < B; r++)
-    if (weights[lo + r] >= mod) return fail(NTRU_ERR_ARG, "ntru_sum_groups: weight of row " + std::to_string(lo + r) + " is not below mod");
-  const size_t row = (size_t)N * 2, out_bytes = (size_t)G * row;
+    if (weights[lo + r] >= mod) return fail(NTRU_ERR_ARG, name + ": weight of row " + std::to_string(lo + r) + " is not below mod");
+  const size_t out_row = (size_t)N * 2, out_bytes = (size_t)G * out_row;
   if (B == 0) { memset(out, 0, out_bytes); return NTRU_OK; }
   HIP_TRY(hipSetDevice(eng->device));
   const size_t off_at = Pipeline::up(out_bytes), tmp_at = off_at + Pipeline::up(offsets ? (size_t)(G + 1) * 8 : 0);
-  if (int rc = ntru_grow_dev(&eng->shared_dev, tmp_at + row)) return rc;
+  if (int rc = ntru_grow_dev(&eng->shared_dev, tmp_at + out_row)) return rc;
   char *dev = (char *)eng->shared_dev.p;
   uint16_t *d_out = (uint16_t *)dev, *d_tmp = (uint16_t *)(dev + tmp_at);
-  const long *d_off = offsets ? (const long *)(dev + off_at) : nullptr;
+  const int64_t *d_off = offsets ? (const int64_t *)(dev + off_at) : nullptr;
   HIP_TRY(hipMemset(d_out, 0, out_bytes));                               // empty groups; every other row is stored by some chunk
   if (offsets) HIP_TRY(hipMemcpy(dev + off_at, offsets, (size_t)(G + 1) * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipDeviceSynchronize());
   auto start_of = [&](int64_t g) { return offsets ? offsets[g] : g * K; };
   Pipeline P(eng);
-  const int ir = P.in(rows + lo * N, row), iw = weights ? P.in(weights + lo, 2) : -1;
+  const int ir = P.in((const char *)rows + (size_t)lo * row_bytes, row_bytes), iw = weights ? P.in(weights + lo, 2) : -1;
   int rc = P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) {
     const int64_t a = lo + o, b = a + n;
     // first group that ends behind a, last group that starts before b: both hold rows of the window
@@ -388,9 +357,10 @@ extern "C" int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_
     x = 0; y = G - 1;
     while (x < y) { const int64_t m = (x + y + 1) >> 1; if (start_of(m) < b) x = m; else y = m - 1; }
     const int64_t g_last = x;
-    Groups gr;
+    SumWindow gr;
     gr.off = d_off; gr.K = K; gr.wlo = a; gr.whi = b;
-    const uint16_t *dr = (const uint16_t *)d[ir], *dw = iw >= 0 ? (const uint16_t *)d[iw] : nullptr;
+    const void *dr = d[ir];
+    const uint16_t *dw = iw >= 0 ? (const uint16_t *)d[iw] : nullptr;
     int64_t g0 = g_first;
     if (start_of(g_first) < a) {                                         // reaches in from the chunk before: add to its part
       gr.g0 = g_first; gr.G = 1;
@@ -409,10 +379,15 @@ extern "C" int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_
   return NTRU_OK;
 }
 
+extern "C" int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_t *rows, const uint16_t *weights,
+                               const int64_t *offsets, int64_t K, int64_t G, uint16_t *out) {
+  return ntru_sum_groups_host(eng, "ntru_sum_groups", N, mod, rows, (size_t)N * 2, weights, offsets, K, G, out, launch_sum);
+}
+
 extern "C" int ntru_tally_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
                                         const uint16_t *rows, const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G,
                                         uint16_t *sum, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
-  if (int rc = check_sum_args(eng, N, q, !offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
+  if (int rc = ntru_check_sum_args(eng, N, q, !offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
   if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
   if (G == 0) return NTRU_OK;
   if (!f || !fp || !sum || !value) return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_batch: NULL buffer (sum is needed as the intermediate)");

@@ -14,6 +14,8 @@
 //   ciphertext_sum.hip       segmented, weighted sums of ciphertext rows + tally decrypt (kernels, *_dev and host-pointer entry points)
 //   message_bytes.hip        byte messages as packed bits: bytes <-> coefficient rows, encrypt / decrypt / pipeline on bytes (kernels, *_dev
 //                            entry points and ntru_pipeline_bytes_batch)
+//   packed_ciphertexts.hip   ciphertexts as packOutput(q - 1, N, e) rows: sums straight from the packed rows, unpack to dense rows, tally
+//                            and decrypt on them (kernels, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -174,6 +176,27 @@ NTRU_HIDDEN int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int
                                              const uint16_t *d_fq, const uint8_t *d_fp, const uint16_t *d_h, int64_t B,
                                              uint16_t *d_quot_fq, uint16_t *d_rem_fq, uint8_t *d_quot_fp, uint8_t *d_rem_fp,
                                              uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags);
+
+// ---- sums of rows in groups (ciphertext_sum.hip; packed_ciphertexts.hip sums packed rows through the same finish kernel and host form)
+// The groups of one launch as the host hands them on: off != NULL (DEVICE, G + 1 row indices): group g is rows [off[g], off[g + 1]);
+// else rows [(g0 + g) K, (g0 + g + 1) K); both clamped to the window [wlo, whi), whose first row is the first row of the array passed.
+struct SumWindow {
+  const int64_t *off;
+  int64_t K, g0, G, wlo, whi;
+};
+// Enqueues the sums of the groups `w` of the rows at d_rows (dense uint16_t rows or packed rows) into d_out [w.G][N].
+typedef int (*ntru_sum_launcher)(ntru_engine *eng, int N, int mod, const void *d_rows, const uint16_t *d_weights, const SumWindow &w,
+                                 uint16_t *d_out);
+// the domain and argument checks of ntru_sum_groups under the name `who`
+NTRU_HIDDEN int ntru_check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t K, int64_t G, const char *who);
+// k_sum_groups_finish on the partial rows a row kernel left for Pb row blocks (sum_groups_common.h); nothing to do for Pb == 1
+NTRU_HIDDEN int ntru_launch_sum_finish(ntru_engine *eng, int N, int mod, const SumWindow &w, long Pb, const uint32_t *d_part,
+                                       const long *d_meta, uint16_t *d_out);
+// The host-pointer form of a sum: validates offsets and weights, streams the rows (row_bytes each) through the chunked pipeline, one
+// window of rows per chunk, and accumulates a group larger than a chunk across chunks.
+NTRU_HIDDEN int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, const void *rows, size_t row_bytes,
+                                     const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G, uint16_t *out,
+                                     ntru_sum_launcher launch);
 
 // ---- host-pointer entry points (ntru_host.hip; keygen_batch, ciphertext_sum, message_bytes) --------------------------------------------------------------
 // True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).

@@ -1,0 +1,77 @@
+// sum_groups_common.h -- what the kernels that sum rows in groups share (ciphertext_sum.hip: dense rows; packed_ciphertexts.hip: rows of
+// packed field elements): the groups of one launch, their cut into row blocks, and the layout of the partial rows that
+// k_sum_groups_finish completes.
+//
+// A launch covers the rows [first offset, last offset), cut into Pb equal ROW BLOCKS.  A group that crosses a block boundary leaves one
+// partial row per block it meets in `part` (u32 [Pb][2][N]): slot 0 of a block for the group that entered through the block's start,
+// slot 1 for the group that leaves through its end, and meta[block] (long [Pb]) records the group of slot 1, or -1.  Partial rows are
+// reduced below mod unless mod is a power of two.  k_sum_groups_finish (ciphertext_sum.hip, ntru_launch_sum_finish) adds them up.
+//
+// The types sit in an unnamed namespace: each translation unit's kernels take its own copy, and the kernels' symbols stay what they were
+// when ciphertext_sum.hip held these lines.  Across translation units the host passes the same six values as a SumWindow
+// (engine_internal.h).
+#ifndef NTRU_SUM_GROUPS_COMMON_H
+#define NTRU_SUM_GROUPS_COMMON_H
+
+#include "kernels_common.h"
+
+typedef unsigned long long u64;
+
+namespace {
+
+// The groups of one launch.  off != NULL: group g is rows [off[g], off[g + 1]); else rows [(g0 + g) K, (g0 + g + 1) K).  Both
+// clamped to the window [wlo, whi) (the host form's chunk; everything for the _dev form); row r lies at rows + (r - wlo) N.
+struct Groups {
+  const long *off;
+  long K, g0, G, wlo, whi;
+};
+
+__device__ __forceinline__ long g_start(const Groups &gr, long g) {
+  const long s = gr.off ? gr.off[g] : (gr.g0 + g) * gr.K;
+  return s < gr.wlo ? gr.wlo : (s > gr.whi ? gr.whi : s);
+}
+
+// rows [base, end) in blocks of R; blocks 0 .. nb - 1 exist (block 0 always does)
+struct Cut {
+  long base, end, R, nb;
+};
+__device__ __forceinline__ Cut cut_of(const Groups &gr, long Pb) {
+  Cut c;
+  c.base = g_start(gr, 0);
+  c.end = g_start(gr, gr.G);
+  const long T = c.end - c.base;
+  c.R = T > Pb ? (T + Pb - 1) / Pb : 1;
+  c.nb = T > 0 ? (T + c.R - 1) / c.R : 1;
+  return c;
+}
+
+// x mod M for an accumulator of the sums that are not taken modulo a power of two
+__device__ __forceinline__ u32 mod_u64(u64 x, u32 M) {
+  if ((x >> 32) == 0) return (u32)x % M;
+  u32 r = (u32)(x >> 32) % M;                       // two 16-bit Horner steps below: r < M <= 65536, so (r << 16) | . fits u32
+  r = ((r << 16) | ((u32)x >> 16)) % M;
+  return ((r << 16) | ((u32)x & 0xffffu)) % M;
+}
+
+inline Groups groups_of(const SumWindow &w) {
+  Groups gr;
+  gr.off = (const long *)w.off; gr.K = w.K; gr.g0 = w.g0; gr.G = w.G; gr.wlo = w.wlo; gr.whi = w.whi;
+  return gr;
+}
+
+// Row blocks of a launch whose row needs `tiles` wavefronts: from the grid (waves_per_cu x CUs), and for uniform groups, whose row
+// count the host knows, no more than there are rows.
+inline long sum_row_blocks(const ntru_engine *eng, int tiles, int waves_per_cu, const SumWindow &w) {
+  long pb = (long)eng->cus * waves_per_cu / tiles;
+  pb = pb < 1 ? 1 : (pb > 32768 ? 32768 : pb);
+  if (!w.off) {
+    long T = std::min<long>(w.whi, (w.g0 + w.G) * w.K) - std::max<long>(w.wlo, w.g0 * w.K);
+    if (T < 1) T = 1;
+    if (pb > T) pb = T;
+  }
+  return pb;
+}
+
+}  // namespace
+
+#endif

@@ -85,6 +85,10 @@ _SIGS = {
     "ntru_multi_engines": _sig("p"),
     **_both("ntru_sum_groups", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_batch", "p iii ppppp ll ppppp"),
+    # ciphertexts as packOutput(q - 1, N, e) rows: the methods are in packed.py
+    **_both("ntru_sum_groups_packed", "p ii ppp ll p"),
+    **_both("ntru_tally_decrypt_packed_batch", "p iii ppppp ll ppppp"),
+    **_both("ntru_decrypt_packed_batch", "p iii ppp l pppp"),
     "ntru_keygen_workspace_bytes": _sig("i l Z"),
     **_both("ntru_keygen_batch", "p iiiii p u i l pppppppp"),
 }

@@ -262,6 +262,27 @@ export function sumCiphertexts(rows, q, offsets = null, weights = null) {
   return offsets == null ? sums[0] : sums;
 }
 
+// Rows of packOutput(q - 1, N, e) field elements, BigUint64Array[B * outputSize * 4] -> the dense rows Uint16Array[B * N]: unpackInput of
+// every row with the pad dropped, whatever the pad and the bits above an element's fields hold.
+function unpackRows(N, q, packed, B) {
+  const [bits, per, , outputSize] = engine().packParams(q - 1, N);
+  const wide = new Uint16Array(B * outputSize * per), dense = new Uint16Array(B * N);
+  if (B) engine().unpackBatch(q - 1, per * bits, packed, outputSize, B, wide);
+  for (let b = 0; b < B; b++) dense.set(wide.subarray(b * outputSize * per, b * outputSize * per + N), b * N);
+  return dense;
+}
+
+// sumCiphertexts on B ciphertexts in the circuits' wire format (packed as above; weights: Array or Uint16Array of B, or null): the sums
+// of the groups as ONE dense Uint16Array[G * N], not trimmed.  Composed from unpackBatch and sumGroups: the same results as the engine's
+// ntru_sum_groups_packed, which reads the packed rows once, but not that call (INTEGRATION.md, "Packed ciphertexts").
+export function sumPackedCiphertexts(packed, N, q, B, offsets = null, weights = null) {
+  const w = weights ? Uint16Array.from(weights, x => ((x % q) + q) % q) : null;
+  const { off, K, G } = tallyGroups(offsets, B);
+  const out = new Uint16Array(G * N);
+  engine().sumGroups(N, q, unpackRows(N, q, packed, B), w, off, K, G, B, out);
+  return out;
+}
+
 const limbsToBigInt = (l, at) => l[at] | (l[at + 1] << 64n) | (l[at + 2] << 128n) | (l[at + 3] << 192n);
 
 // index.js:572-596 on the GPU: same object as the reference (`expected` is an Array of BigInt).
@@ -501,6 +522,12 @@ export default class NTRU {
     if (asynchronous) return engine().tallyDecryptBatchAsync(...args).then(() => res);
     engine().tallyDecryptBatch(...args);
     return res;
+  }
+
+  // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed
+  // from unpackBatch and tallyDecryptBatch (same results as ntru_tally_decrypt_packed_batch, not that call).
+  tallyPackedBatch(packed, B, offsets = null, weights = null, wantWitness = true) {
+    return this._tally(unpackRows(this.N, this.q, packed, B), B, offsets, weights, wantWitness, false);
   }
 
   // The same on device handles (devAlloc): offsetsDev holds G + 1 int64 row indices on the device (null: uniform groups of K rows); only

@@ -17,6 +17,7 @@ import secrets
 
 import numpy as np
 
+from . import packed as packed_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
 
@@ -447,6 +448,29 @@ class NTRU:
         total, value, q1, r1, q2 = self.engine.tally_decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), rows,
                                                                    offsets=offsets, weights=weights, want_witness=wantWitness)
         return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
+    def tallyPacked(self, packed, offsets=None, weights=None, wantWitness=True):
+        """tallyBatch on packed rows, summed straight from the field elements: the same dict, sum included, as dense [G][N] arrays."""
+        N, q, p = self.N, self.q, self.p
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.int64) % q
+        total, value, q1, r1, q2 = packed_calls.tally_decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N),
+                                                                           expandArray(self.fp, N), packed, offsets=offsets,
+                                                                           weights=weights, want_witness=wantWitness)
+        return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    def decryptPackedBatch(self, packed, wantWitness=True):
+        """decryptBits for B packed ciphertexts.  Returns {"value", "quotient1", "remainder1", "quotient2"} as [B][N] arrays: row b
+        equals the witness arrays of decryptBits(unpacked row b)."""
+        N, q, p = self.N, self.q, self.p
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")
+        value, q1, r1, q2 = packed_calls.decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N), expandArray(self.fp, N),
+                                                              packed, want_witness=wantWitness)
+        return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
