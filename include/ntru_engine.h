@@ -245,13 +245,36 @@ int ntru_encrypt_batch_dev(ntru_engine_t *eng, int N, int q, const uint16_t *d_h
 /* ---- decryptBits (index.js:111-140) for B ciphertexts under one private key.
  *      f[N] in {-1,0,1}; fp[N] in [0,p); e[B][N] in [0,q).
  *      value = remainder2; quot1 / rem1 / quot2 = quotient1 / remainder1 / quotient2 (each may be NULL).
- *      The centred lift is the reference's `x > q/2 ? (x+1)%p : x%p` verbatim. */
+ *      The centred lift is the reference's `x > q/2 ? (x+1)%p : x%p` verbatim unless the engine is in
+ *      NTRU_LIFT_CENTRED (ntru_engine_set_lift below). */
 int ntru_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
                        const uint16_t *e, int64_t B, uint8_t *value, uint16_t *quot1, uint16_t *rem1,
                        uint8_t *quot2);
 int ntru_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t *d_f, const uint8_t *d_fp,
                            const uint16_t *d_e, int64_t B, uint8_t *d_value, uint16_t *d_quot1,
                            uint16_t *d_rem1, uint8_t *d_quot2);
+/* The lift of decryptBits, a mode of the engine.  The reference maps a = f e mod q into mod p with `x > q/2 ? (x+1)%p : x%p`
+ * (index.js:117).  The representative of x > q/2 is x - q, so the `+ 1` is right only when -q = 1 (mod p): for p = 3 at q = 128,
+ * 2048, 8192, not at q = 256, 1024, 4096, 16384, 65536, and for hardly any q once p is 5 or 7.  Where it is wrong, decryptBits does
+ * not return the plaintext ("The lift").
+ *   NTRU_LIFT_REFERENCE   index.js:117 verbatim (the default of a new engine): bit-identical to the reference, and what the
+ *                         VerifyDecrypt circuit (which hard-codes `+ gt`) accepts as a witness.
+ *   NTRU_LIFT_CENTRED     x > q/2 ? (x - q) mod p : x % p, i.e. the addend (p - q % p) % p in place of 1.  quot1 / rem1 are what they
+ *                         were; value and quot2 come from the centred b.  Where the addend is 1 both modes give the same bytes.
+ * The threshold is strict in both modes (x = q/2 is lifted as positive).  The same kernels run in both modes: the addend is one
+ * kernel argument.  Honoured by everything that runs decryptBits: ntru_decrypt_batch[_dev], ntru_decrypt_batch_pitched_dev,
+ * ntru_decrypt_pack_batch_dev, ntru_decrypt_peritem_batch[_dev], ntru_decrypt_bytes_batch[_dev], ntru_tally_decrypt_batch[_dev],
+ * ntru_tally_decrypt_packed_batch[_dev], ntru_decrypt_packed_batch[_dev], the decrypt stage of ntru_pipeline_batch and
+ * ntru_pipeline_bytes_batch, ntru_multi_decrypt_batch (ntru_multi_set_lift).  ntru_check_decrypt_batch checks the circuit and
+ * ntru_verify_keys_batch has no lift: neither changes.
+ * The mode is read when a call enqueues and reaches the kernel by value: a _dev call enqueued before a later ntru_engine_set_lift
+ * keeps the mode it was enqueued with.  As with ntru_engine_set_stream and ntru_engine_set_kernel_path, do not change it while a
+ * host-form call on that engine is running.
+ * ntru_engine_set_lift: a NULL engine, then an unknown mode, is NTRU_ERR_ARG.  ntru_engine_get_lift(NULL) is NTRU_LIFT_REFERENCE. */
+#define NTRU_LIFT_REFERENCE 0
+#define NTRU_LIFT_CENTRED 1
+int ntru_engine_set_lift(ntru_engine_t *eng, int lift);
+int ntru_engine_get_lift(ntru_engine_t *eng);
 
 /* ---- byte messages as packed bits: encryptStr / decryptStr (index.js:80-86) and the stringToBits / bitsToString under them
  *      (index.js:538-556) on the device, for messages of any length and with one BIT per plaintext bit across the bus.
@@ -416,6 +439,8 @@ typedef struct ntru_multi ntru_multi_t;
 int ntru_multi_create(const int *device_ids, int n_dev, ntru_multi_t **out);
 void ntru_multi_destroy(ntru_multi_t *m);
 int ntru_multi_engines(const ntru_multi_t *m);
+/* ntru_engine_set_lift on every engine of `m` (a NULL `m`, then an unknown mode: NTRU_ERR_ARG, nothing changed). */
+int ntru_multi_set_lift(ntru_multi_t *m, int lift);
 int ntru_multi_encrypt_batch(ntru_multi_t *m, int N, int q, const uint16_t *h, const uint8_t *r, const uint8_t *mm, int64_t B,
                              uint16_t *e, uint16_t *quotE);
 int ntru_multi_decrypt_batch(ntru_multi_t *m, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint16_t *e,

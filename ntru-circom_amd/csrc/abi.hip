@@ -111,6 +111,7 @@ extern "C" int ntru_engine_create(int device, ntru_engine_t **out) {
   eng->cus = prop.multiProcessorCount;
   eng->path = 0;
   eng->sampler_rounds = 20;
+  eng->lift = NTRU_LIFT_REFERENCE;
   eng->last_kernel[0] = 0;
   eng->n_occ = 0;
   eng->cur_scratch = &eng->scratch_dev;
@@ -169,6 +170,16 @@ extern "C" int ntru_engine_set_sampler_rounds(ntru_engine_t *eng, int rounds) {
 }
 
 extern "C" int ntru_engine_get_sampler_rounds(ntru_engine_t *eng) { return eng ? eng->sampler_rounds : 0; }
+
+extern "C" int ntru_engine_set_lift(ntru_engine_t *eng, int lift) {
+  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
+  if (lift != NTRU_LIFT_REFERENCE && lift != NTRU_LIFT_CENTRED)
+    return fail(NTRU_ERR_ARG, "lift must be NTRU_LIFT_REFERENCE (0: index.js:117 verbatim, the default) or NTRU_LIFT_CENTRED (1)");
+  eng->lift = lift;
+  return NTRU_OK;
+}
+
+extern "C" int ntru_engine_get_lift(ntru_engine_t *eng) { return eng ? eng->lift : NTRU_LIFT_REFERENCE; }
 
 extern "C" const char *ntru_engine_last_kernel(ntru_engine_t *eng) { return eng ? eng->last_kernel : ""; }
 

@@ -73,6 +73,7 @@ struct ntru_engine {
   int path;                 // ntru_engine_set_kernel_path: 0 auto, 1 MAC kernels, 2 add path, 3 add path without dot8, 4 matrix cores as two
                             // workgroups per CU, 5 matrix cores with the lock-step decrypt
   int sampler_rounds;       // ntru_engine_set_sampler_rounds: 20 (RFC 8439, default), 12 or 8 rounds of the sampler's ChaCha block function
+  int lift;                 // ntru_engine_set_lift: NTRU_LIFT_REFERENCE (default) or NTRU_LIFT_CENTRED; the decrypt launchers read it
   char last_kernel[64];     // name of the kernel the last *_dev call launched (reporting only)
   HostSlot slot[NTRU_HOST_SLOTS];
   hipStream_t st_up, st_comp, st_down;   // the three stage streams of the host path (created at first use)
@@ -128,6 +129,11 @@ static inline dim3 elementwise_grid(const ntru_engine *eng, long total, bool str
   const int per_cu = streaming ? 2 : 8;
   long blocks = (total + 255) / 256, cap = (long)eng->cus * per_cu;
   return dim3((unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks)));
+}
+// What decryptBits' lift adds to x > q/2 before the reduction mod p: index.js:117's 1, or -q mod p in NTRU_LIFT_CENTRED.  Read when a
+// call enqueues, handed to the kernel by value.
+static inline uint32_t ntru_lift_addend(const ntru_engine *eng, int q, int p) {
+  return eng->lift == NTRU_LIFT_CENTRED ? (uint32_t)((p - q % p) % p) : 1u;
 }
 // (N, q, B) of the packed kernels: q a power of two <= 65536, 2 <= N <= NTRU_MAX_N
 NTRU_HIDDEN int ntru_check_common(const ntru_engine *eng, int N, int q, long B);

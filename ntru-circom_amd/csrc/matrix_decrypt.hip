@@ -30,7 +30,7 @@
 // (First version: DPP gather + ds_or_b32 into an image of the packed rows: bit-exact, 3.65 ms per 2^20 against 1.83 ms for the
 // plain value-only kernel -- 1248 LDS atomics per row block with 4 active lanes each.)
 template <int GROUPS, bool PACK = false>
-static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, const int8_t *__restrict__ f,
+static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, u32 lift_add, const int8_t *__restrict__ f,
                                                       const uint8_t *__restrict__ fp,
                                                       const u16 *__restrict__ e, long B,
                                                       uint8_t *__restrict__ value, u16 *__restrict__ quot1,
@@ -53,7 +53,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
   unsigned char *blp = stLo + 32 * g.pitchA;             // [8 row groups][32 NT columns]: 4 rows x 2 bits per byte
   // GROUPS = 2 keeps a third key array, TF64 = the 64 f plane of product 1 (the four-wave kernels derive it from f in the loop)
   u32 *TF = (u32 *)(lds + m3_bytes + GROUPS * gbytes), *TP = TF + 4 * g.tpitch, *TF64 = TP + 4 * g.tpitch;
-  unsigned char *lift_lut = (unsigned char *)(TP + 4 * g.tpitch * GROUPS);   // [q]: centred lift followed by mod p, index.js:117 verbatim
+  unsigned char *lift_lut = (unsigned char *)(TP + 4 * g.tpitch * GROUPS);   // [q]: centred lift followed by mod p: index.js:117 with lift_add in place of its 1
   // PACK: 2-bit image of product 2's values, [8 row groups][pcols] bytes, pcols = 126 pack_os + 16 >= 32 NT (zero beyond N).  It lives
   // in the e_hi stage behind the mod-p tables (dead between product 1's last loop and the next trip's staging: no LDS of its own --
   // 7 KB more would cost the second workgroup of the CU); it is turned into packed dwords at the top of the next trip, and a barrier
@@ -98,7 +98,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
   build_toeplitz_array(TP, g, [&](int i) { return (int)fp[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   if (GROUPS == 2)   // 64 f: the two low bits of every digit of f in bits 6-7 (f in {-1,0,1}: 0xC0, 0, 0x40)
     build_toeplitz_array(TF64, g, [&](int i) { return (int)(((u32)f[i] << 6) & 0xC0u); }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
-  for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)mod_small(2 * x > q ? x + 1 : x, p);
+  for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)mod_small(2 * x > q ? x + lift_add : x, p);
   if (GROUPS == 2) build_m3((int)threadIdx.x, GROUPS * BLOCK_THREADS, g.N);
   auto phase = [&]() { if (GROUPS == 2) __syncthreads(); };   // a boundary of the lock-step schedule
   if (GROUPS == 2 && group == 1) __syncthreads();                   // group 1 runs one phase behind group 0
@@ -342,28 +342,28 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, con
   }
 }
 
-__global__ __launch_bounds__(BLOCK_THREADS, 2) void k_decrypt_m(MGeom g, u32 q, u32 p, const int8_t *__restrict__ f,
+__global__ __launch_bounds__(BLOCK_THREADS, 2) void k_decrypt_m(MGeom g, u32 q, u32 p, u32 lift_add, const int8_t *__restrict__ f,
                                                              const uint8_t *__restrict__ fp,
                                                              const u16 *__restrict__ e, long B,
                                                              uint8_t *__restrict__ value, u16 *__restrict__ quot1,
                                                              u16 *__restrict__ rem1, uint8_t *__restrict__ quot2) {
-  decrypt_m_body<1>(g, q, p, f, fp, e, B, value, quot1, rem1, quot2);
+  decrypt_m_body<1>(g, q, p, lift_add, f, fp, e, B, value, quot1, rem1, quot2);
 }
 
-__global__ __launch_bounds__(2 * BLOCK_THREADS, 1) void k_decrypt_m8(MGeom g, u32 q, u32 p, const int8_t *__restrict__ f,
+__global__ __launch_bounds__(2 * BLOCK_THREADS, 1) void k_decrypt_m8(MGeom g, u32 q, u32 p, u32 lift_add, const int8_t *__restrict__ f,
                                                                   const uint8_t *__restrict__ fp,
                                                                   const u16 *__restrict__ e, long B,
                                                                   uint8_t *__restrict__ value, u16 *__restrict__ quot1,
                                                                   u16 *__restrict__ rem1, uint8_t *__restrict__ quot2) {
-  decrypt_m_body<2>(g, q, p, f, fp, e, B, value, quot1, rem1, quot2);
+  decrypt_m_body<2>(g, q, p, lift_add, f, fp, e, B, value, quot1, rem1, quot2);
 }
 
 // decryptBits + packOutput(p - 1, N, value) in one kernel (decrypt_m_body<.., PACK>); `value` may be NULL.
-__global__ __launch_bounds__(BLOCK_THREADS, 2) void k_decrypt_mp(MGeom g, u32 q, u32 p, const int8_t *__restrict__ f,
+__global__ __launch_bounds__(BLOCK_THREADS, 2) void k_decrypt_mp(MGeom g, u32 q, u32 p, u32 lift_add, const int8_t *__restrict__ f,
                                                               const uint8_t *__restrict__ fp,
                                                               const u16 *__restrict__ e, long B,
                                                               uint8_t *__restrict__ value, unsigned long long *__restrict__ packed, int pack_os) {
-  decrypt_m_body<1, true>(g, q, p, f, fp, e, B, value, nullptr, nullptr, nullptr, packed, pack_os);
+  decrypt_m_body<1, true>(g, q, p, lift_add, f, fp, e, B, value, nullptr, nullptr, nullptr, packed, pack_os);
 }
 
 NTRU_STAMPS_READER(ntru_debug_read_stamps_dec)
@@ -379,7 +379,7 @@ int ntru_launch_decrypt_pack_matrix(ntru_engine *eng, int N, int q, int p, const
   const size_t m3_end = ((((size_t)4 * N + 4) & ~(size_t)3) + (size_t)4 * N + 1 + 15) & ~(size_t)15, img = ((size_t)8 * (126 * out_size + 16) + 15) & ~(size_t)15;
   if (lds > 160 * 1024 || m3_end + img > (size_t)32 * mg.pitchA || 126 * out_size + 16 < 32 * mg.NT) return NTRU_NOT_TAKEN;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_mp");
-  return launch_resident(eng, k_decrypt_mp, (long)((B + 31) / 32), BLOCK_THREADS, lds, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
+  return launch_resident(eng, k_decrypt_mp, (long)((B + 31) / 32), BLOCK_THREADS, lds, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value,
                          (unsigned long long *)d_packed, out_size);
 }
 
@@ -399,12 +399,12 @@ int ntru_launch_decrypt_matrix(ntru_engine *eng, int N, int q, int p, int ld, co
     const size_t lds8 = 2 * ((size_t)64 * mg.pitchA + (size_t)256 * mg.NT) + m3 + (size_t)48 * mg.tpitch + (((size_t)q + 15) & ~(size_t)15);
     if (lds8 <= 160 * 1024) {
       snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m8");
-      return launch_resident(eng, k_decrypt_m8, (nrb + 1) / 2, 2 * BLOCK_THREADS, lds8, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B,
+      return launch_resident(eng, k_decrypt_m8, (nrb + 1) / 2, 2 * BLOCK_THREADS, lds8, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B,
                              d_value, d_quot1, d_rem1, d_quot2);
     }
   }
   if (lds > 160 * 1024) return NTRU_NOT_TAKEN;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m");
-  return launch_resident(eng, k_decrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value, d_quot1,
+  return launch_resident(eng, k_decrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value, d_quot1,
                          d_rem1, d_quot2);
 }

@@ -9,7 +9,7 @@
 //                    k_verify_keys_m's product 1 alone, with e = (low + high + m) mod q and quotE = -high mod q (m has degree < N:
 //                    it never reaches the quotient).
 //   k_decrypt_pi_m   both reversed arrays (f ternary, fp) at item start; product 1 = the digit planes of e against f gives quot1 /
-//                    rem1; its epilogue lifts rem1 to a in {0, 1, 2} (index.js:117 verbatim) and writes a as a natural-order byte
+//                    rem1; its epilogue lifts rem1 to a in {0, 1, 2} (index.js:117; the engine's lift addend for its 1) and writes a as a natural-order byte
 //                    image into the wave's LDS, from which each lane reads its own 16-byte chunk back -- the row layout, the route
 //                    of the Newton round's e; product 2 = one plane, a against fp, reduced mod 3: value = rem2 and quot2.
 // Range: 128 <= N <= 1024 (64 with kernel path 4), q <= 8192, p == 3 for decrypt (peritem_applies).  Outside it the entry points
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(O
 // p == 3.  ONE: q <= 256, a single (centred) digit plane of e.  quot1 / rem1 / quot2 may be NULL (empty descriptors).
 template <bool ONE>
 __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_decrypt_pi_m(
-    PGeom g, u32 q, const int8_t *__restrict__ f, const uint8_t *__restrict__ fp, const u16 *__restrict__ e, long B,
+    PGeom g, u32 q, u32 lift_add, const int8_t *__restrict__ f, const uint8_t *__restrict__ fp, const u16 *__restrict__ e, long B,
     uint8_t *__restrict__ value, u16 *__restrict__ quot1, u16 *__restrict__ rem1, uint8_t *__restrict__ quot2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   constexpr int NPL = ONE ? 1 : 2;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(3
         const u32 rv = (lo + hi) & (q - 1);
         if (want_r1) __builtin_amdgcn_raw_buffer_store_b16((u16)rv, rs_r, 2 * kl, 2 * ko, 0);
         if (want_q1) __builtin_amdgcn_raw_buffer_store_b16((u16)((0u - hi) & (q - 1)), rs_q, 2 * kl, 2 * ko, 0);
-        nat[ko + kl] = (unsigned char)(2 * rv > q ? (rv + 1) % 3u : rv % 3u);     // index.js:117, strict >
+        nat[ko + kl] = (unsigned char)(2 * rv > q ? (rv + lift_add) % 3u : rv % 3u);     // index.js:117 (lift_add for its 1), strict >
       });
       wave_lds_fence();
       const int ch = pi_chunk_of(opaque(lane));
@@ -164,11 +164,11 @@ __global__ void k_pi_signed_modq(const int8_t *__restrict__ in, long n, u32 q, u
 __global__ void k_pi_add_bytes(u16 *__restrict__ e, const uint8_t *__restrict__ m, long n, u32 q) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) e[i] = (u16)(((u32)e[i] + m[i]) & (q - 1));
 }
-// the centred lift of index.js:117 verbatim
-__global__ void k_pi_lift(const u16 *__restrict__ rem, long n, u32 q, u32 p, u16 *__restrict__ out) {
+// the centred lift of index.js:117, lift_add in place of its 1
+__global__ void k_pi_lift(const u16 *__restrict__ rem, long n, u32 q, u32 p, u32 lift_add, u16 *__restrict__ out) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const u32 x = rem[i];
-    out[i] = (u16)(2 * x > q ? mod_small(x + 1, p) : mod_small(x, p));
+    out[i] = (u16)(2 * x > q ? mod_small(x + lift_add, p) : mod_small(x, p));
   }
 }
 
@@ -228,7 +228,7 @@ int decrypt_composed(ntru_engine *eng, int N, int q, int p, const int8_t *d_f, c
     uint16_t *const q1 = d_quot1 ? d_quot1 + off : q1t, *const r1 = d_rem1 ? d_rem1 + off : r1t;
     if (int rc = launch_elementwise(eng, k_pi_signed_modq, el, d_f + off, el, (u32)q, fa)) return rc;
     if (int rc = ntru_polymul_split_dev(eng, N, q, fa, d_e + off, n, q1, r1)) return rc;
-    if (int rc = launch_elementwise(eng, k_pi_lift, el, (const u16 *)r1, el, (u32)q, (u32)p, fa)) return rc;
+    if (int rc = launch_elementwise(eng, k_pi_lift, el, (const u16 *)r1, el, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), fa)) return rc;
     if (int rc = launch_elementwise(eng, k_pi_widen, el, d_fp + off, el, fp16)) return rc;
     if (int rc = ntru_polymul_split_dev(eng, N, p, fp16, fa, n, q2, r2)) return rc;
     if (int rc = launch_elementwise(eng, k_pi_narrow, el, (const u16 *)r2, el, d_value + off)) return rc;
@@ -266,6 +266,6 @@ extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   if (p != 3 || !peritem_applies(eng, N, q)) return decrypt_composed(eng, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1, d_rem1, d_quot2);
   const PGeom pg = make_pgeom(N);
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_pi_m");
-  return launch_peritem(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, B, pi_wave_bytes(pg, 2), pg, (u32)q, d_f, d_fp, d_e,
+  return launch_peritem(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, B, pi_wave_bytes(pg, 2), pg, (u32)q, ntru_lift_addend(eng, q, 3), d_f, d_fp, d_e,
                         (long)B, d_value, d_quot1, d_rem1, d_quot2);
 }

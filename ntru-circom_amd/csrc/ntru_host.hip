@@ -158,6 +158,13 @@ extern "C" void ntru_multi_destroy(ntru_multi_t *m) {
 
 extern "C" int ntru_multi_engines(const ntru_multi_t *m) { return m ? (int)m->eng.size() : 0; }
 
+extern "C" int ntru_multi_set_lift(ntru_multi_t *m, int lift) {
+  if (!m) return ntru_fail(NTRU_ERR_ARG, "multi-device engine is NULL");
+  if (lift != NTRU_LIFT_REFERENCE && lift != NTRU_LIFT_CENTRED) return ntru_engine_set_lift(m->eng[0], lift);   // its message; nothing changed
+  for (ntru_engine_t *e : m->eng) (void)ntru_engine_set_lift(e, lift);
+  return NTRU_OK;
+}
+
 namespace {
 // fn(engine, first item, items) on one thread per engine; the first failure (lowest shard) is what the caller sees
 template <class F>

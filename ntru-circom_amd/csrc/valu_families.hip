@@ -239,7 +239,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_encrypt(Geom g, u32 q, const 
 
 // decryptBits, index.js:111-140: a = f*e mod q; split; lift; c = fp*b mod p; split.
 template <int K>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt(Geom g, u32 q, u32 p, const int8_t *__restrict__ f,
+__global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt(Geom g, u32 q, u32 p, u32 lift_add, const int8_t *__restrict__ f,
                                                            const uint8_t *__restrict__ fp,
                                                            const u16 *__restrict__ e, long B,
                                                            uint8_t *__restrict__ value, u16 *__restrict__ quot1,
@@ -269,14 +269,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt(Geom g, u32 q, u32 p,
       if (rem1) store_pairs<K>(rem1 + row, g, L.sub, r1);
       if (want_q1) store_pairs<K>(quot1 + row, g, L.sub, q1);
     }
-    // centred lift, index.js:117 verbatim: x > q/2 ? (x+1)%p : x%p ; zero beyond N so the padding stays zero
+    // centred lift, index.js:117: x > q/2 ? (x+1)%p : x%p, with lift_add in place of its 1 ; zero beyond N so the padding stays zero
     wave_lds_fence();
     if (L.active) {
 #pragma unroll
       for (int t = 0; t < K; t++) {
         int k = 2 * K * L.sub + 2 * t;
         u32 x0 = r1[t].x, x1 = r1[t].y;
-        u32 b0 = mod_small(2 * x0 > q ? x0 + 1 : x0, p), b1 = mod_small(2 * x1 > q ? x1 + 1 : x1, p);
+        u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
         b0 = k < g.N ? b0 : 0; b1 = k + 1 < g.N ? b1 : 0;
         a32[K * L.sub + t] = b0 | (b1 << 16);
       }
@@ -685,7 +685,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 7) void k_encrypt_t(Geom g, u32 q, c
 // decryptBits on the add path: product 1 steps over f (shared, codes built once) with a per-item window of e;
 // product 2 steps over the lifted message (per item, in registers) with the shared window of fp.  Needs p == 3.
 template <int K, int ME>
-__global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 p,
+__global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 p, u32 lift_add,
                                                              const int8_t *__restrict__ f,
                                                              const uint8_t *__restrict__ fp,
                                                              const u16 *__restrict__ e, long B,
@@ -721,7 +721,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
       if (want_q1) store_pair(quot1 + lane0, sp, t, qv);
       const int k = 2 * K * L.sub + 2 * t;
       const u32 x0 = rv.x, x1 = rv.y;
-      u32 b0 = mod_small(2 * x0 > q ? x0 + 1 : x0, p), b1 = mod_small(2 * x1 > q ? x1 + 1 : x1, p);
+      u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
       b0 = k < g.N ? b0 : 0; b1 = k + 1 < g.N ? b1 : 0;
       av_b[t] = b0 | (b1 << 16);
       wb |= step_bits(b0, 2 * t) | step_bits(b1, 2 * t + 1);
@@ -918,11 +918,12 @@ static __device__ __forceinline__ uint2 load_block_masks(F val, const Geom &g, i
 
 // decryptBits with both products stepping over the shared key (f, then fp); two items per wave.  p must be 3.
 template <int K, int ME, bool D8>
-__global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u32 p, const int8_t *__restrict__ f,
+__global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u32 lift_add, const int8_t *__restrict__ f,
                                                              const uint8_t *__restrict__ fp,
                                                              const u16 *__restrict__ e, long B,
                                                              uint8_t *__restrict__ value, u16 *__restrict__ quot1,
                                                              u16 *__restrict__ rem1, uint8_t *__restrict__ quot2) {
+  constexpr u32 p = 3u;                                                 // the launcher's precondition; lift_add has taken its argument's place
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   uint2 *masks_f = (uint2 *)lds;
   uint2 *masks_fp = masks_f + g.nl;
@@ -986,7 +987,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u
       if (want_q1) store_pair(quot1 + lane0, sp, t, qv);
       const int k = 2 * (K * sub + t);
       const u32 x0 = rv.x, x1 = rv.y;
-      u32 b0 = mod_small(2 * x0 > q ? x0 + 1 : x0, p), b1 = mod_small(2 * x1 > q ? x1 + 1 : x1, p);
+      u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
       b0 = k < N ? b0 : 0; b1 = k + 1 < N ? b1 : 0;
       P[t] = b0 | (b1 << 16);
     });
@@ -1390,7 +1391,7 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
       L.blocks = (ngroups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
       DISPATCH_K_SHARED(KS, me, d8, {
         note_kernel(eng, DD ? "k_decrypt_s+dot8" : "k_decrypt_s", KK, MM);
-        return launch_resident(eng, k_decrypt_s<KK, MM, DD>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B,
+        return launch_resident(eng, k_decrypt_s<KK, MM, DD>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B,
                                d_value, d_quot1, d_rem1, d_quot2);
       });
     }
@@ -1400,14 +1401,14 @@ int ntru_launch_decrypt_valu(ntru_engine *eng, int N, int q, int p, const int8_t
                           (size_t)L.g.eo_len * 8 + (size_t)L.g.nl * 4, &L)) return rc;
     DISPATCH_K_ADD(L.K, me, {
       note_kernel(eng, "k_decrypt_t", KK, MM);
-      return launch_resident(eng, k_decrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value,
+      return launch_resident(eng, k_decrypt_t<KK, MM>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value,
                              d_quot1, d_rem1, d_quot2);
     });
   }
   if (int rc = plan(eng, N, B, 2, false, &L)) return rc;
   DISPATCH_K(L.K, {
     note_kernel(eng, "k_decrypt", KK, -1);
-    return launch_resident(eng, k_decrypt<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, d_f, d_fp, d_e, (long)B, d_value, d_quot1,
+    return launch_resident(eng, k_decrypt<KK>, L.blocks, BLOCK_THREADS, L.lds, L.g, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value, d_quot1,
                            d_rem1, d_quot2);
   });
 }

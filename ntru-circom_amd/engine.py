@@ -62,6 +62,9 @@ _SIGS = {
     "ntru_engine_supports": _sig("i i"),
     "ntru_engine_set_sampler_rounds": _sig("p i"),
     "ntru_engine_get_sampler_rounds": _sig("p"),
+    # the lift of decryptBits, a mode of the engine: the functions are in lift.py
+    "ntru_engine_set_lift": _sig("p i"),
+    "ntru_engine_get_lift": _sig("p"),
     **_both("ntru_sample_ternary", "p iiii p u l p"),
     "ntru_pack_params": _sig("i i IIII"),
     **_both("ntru_pack_batch", "p ii p l p"),
@@ -83,6 +86,7 @@ _SIGS = {
     "ntru_multi_create": _sig("p i P"),
     "ntru_multi_destroy": _sig("p", "-"),
     "ntru_multi_engines": _sig("p"),
+    "ntru_multi_set_lift": _sig("p i"),
     **_both("ntru_sum_groups", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_batch", "p iii ppppp ll ppppp"),
     # ciphertexts as packOutput(q - 1, N, e) rows: the methods are in packed.py

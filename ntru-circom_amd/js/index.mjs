@@ -7,7 +7,8 @@
 //     deepStrictEqual on a plain Array; circomkit takes number arrays as signals);
 //   * inputs are never mutated; everything is synchronous; errors are `throw new Error(msg)` with the
 //     reference's messages; expandArray overflow surfaces as RangeError (index.js:535);
-//   * constructor options / public mutable fields N,p,q,df,dg,dr,f,fp,fq,g,h,I (index.js:9-27).
+//   * constructor options / public mutable fields N,p,q,df,dg,dr,f,fp,fq,g,h,I (index.js:9-27); one additive option, lift
+//     ('reference', the default, or 'centred': see "the lift" in the class).
 // All polynomial products and splits run on the GPU through the N-API addon -> C ABI (include/ntru_engine.h).
 // There is no JavaScript arithmetic fallback: without the addon or a GPU the first call throws.
 //
@@ -319,6 +320,32 @@ export default class NTRU {
     this.I = (new Array(this.N + 1)).fill(0);                    // index.js:25-27
     this.I[0] = 1;
     this.I[this.I.length - 1] = -1;
+    if (this.lift !== undefined && this.lift !== 'reference' && this.lift !== 'centred') {
+      throw new Error(`lift: unknown mode ${String(this.lift)} ('reference' or 'centred')`);
+    }
+  }
+
+  // ---- the lift (additive; INTEGRATION.md "The lift").  new NTRU({..., lift: 'centred'}) decrypts with the true centred lift,
+  // x > q/2 ? (x - q) mod p : x % p, in place of index.js:117's x > q/2 ? (x + 1) % p : x % p, which returns the plaintext only where
+  // -q = 1 (mod p) -- not at q = 4096 with p = 3, nor at almost any q with p = 5 or 7.  Without the option (or with 'reference') every
+  // method below runs exactly what it ran before the option existed.  The engine's ntru_engine_set_lift has no export in the addon yet
+  // (its export list is fixed), so the centred mode is composed here from existing exports: the first stage with the witness on
+  // (remainder1 does not depend on the lift), the lift on typed arrays in JavaScript, c = fp b through polymulSplit(N, p, ...) with fp
+  // repeated per row.  decryptBits, decryptStr, decryptBatch and tallyBatch do that; the forms that cannot be composed this way throw.
+  get _centred() { return this.lift === 'centred'; }
+  _refuseCentred(name) {
+    if (this._centred) throw new Error(`${name}: not available with the option lift: 'centred' (the addon exports no native path for it yet)`);
+  }
+  // remainder1 rows Uint16Array[B*N] -> { value, quotient2 } of the centred b, Uint8Array[B*N] each
+  _centredSecondStage(r1, B) {
+    const { N, p, q } = this, add = (p - q % p) % p;
+    const fp = expandArray(this.fp, N, 0);
+    const b = new Uint16Array(B * N), fpRows = new Uint16Array(B * N);
+    for (let i = 0; i < B * N; i++) { const x = r1[i]; b[i] = 2 * x > q ? (x + add) % p : x % p; }   // strict >, like index.js:117
+    for (let r = 0; r < B; r++) fpRows.set(fp, r * N);
+    const quot = new Uint16Array(B * N), rem = new Uint16Array(B * N);
+    engine().polymulSplit(N, p, fpRows, b, B, quot, rem);
+    return { value: Uint8Array.from(rem), quotient2: Uint8Array.from(quot) };
   }
 
   calculateNq() { return Math.ceil(Math.log2(this.q * this.q * this.N)); }   // index.js:201-203
@@ -362,9 +389,11 @@ export default class NTRU {
     const { N, p, q } = this;
     const f = this.f.map(x => x === -1 ? q - 1 : x);             // TypeError when f is null, like the reference
     const ePad = expandArray(e, N, 0), fpPad = expandArray(this.fp, N, 0);
-    const value = new Uint8Array(N), q1 = new Uint16Array(N), r1 = new Uint16Array(N), q2 = new Uint8Array(N);
+    let value = new Uint8Array(N), q2 = new Uint8Array(N);
+    const q1 = new Uint16Array(N), r1 = new Uint16Array(N);
     engine().decryptBatch(N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(fpPad),
       Uint16Array.from(ePad), 1, value, q1, r1, q2);
+    if (this._centred) ({ value, quotient2: q2 } = this._centredSecondStage(r1, 1));
     return {
       value: trimPolynomial(Array.from(value)),
       inputs: {
@@ -495,6 +524,7 @@ export default class NTRU {
   // e: Uint16Array[B*N] -> { value, quotient1, remainder1, quotient2 }
   decryptBatch(e, B, wantWitness = true, out = {}) {
     const { N, p, q } = this;
+    if (this._centred) return this._decryptBatchCentred(e, B, wantWitness, out);
     const value = out.value || new Uint8Array(B * N);
     const q1 = wantWitness ? (out.quotient1 || new Uint16Array(B * N)) : null;
     const r1 = wantWitness ? (out.remainder1 || new Uint16Array(B * N)) : null;
@@ -502,6 +532,18 @@ export default class NTRU {
     engine().decryptBatch(N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(expandArray(this.fp, N, 0)),
       e, B, value, q1, r1, q2);
     return { value, quotient1: q1, remainder1: r1, quotient2: q2 };
+  }
+
+  _decryptBatchCentred(e, B, wantWitness, out) {
+    const { N, p, q } = this;
+    const scratch = new Uint8Array(B * N), q1 = out.quotient1 || new Uint16Array(B * N), r1 = out.remainder1 || new Uint16Array(B * N);
+    engine().decryptBatch(N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(expandArray(this.fp, N, 0)),
+      e, B, scratch, q1, r1, null);
+    const second = this._centredSecondStage(r1, B);
+    const keep = (given, got) => { if (!given) return got; given.set(got); return given; };
+    const value = keep(out.value, second.value);
+    if (!wantWitness) return { value, quotient1: null, remainder1: null, quotient2: null };
+    return { value, quotient1: q1, remainder1: r1, quotient2: keep(out.quotient2, second.quotient2) };
   }
 
   // ---- tallies (additive): sums the ciphertexts rows: Uint16Array[B*N] in groups (offsets: G + 1 row indices, BigInt64Array or Array;
@@ -512,27 +554,34 @@ export default class NTRU {
   tallyBatchAsync(rows, B, offsets = null, weights = null, wantWitness = true) { return this._tally(rows, B, offsets, weights, wantWitness, true); }
   _tally(rows, B, offsets, weights, wantWitness, asynchronous) {
     const { N, p, q } = this;
+    if (asynchronous) this._refuseCentred('tallyBatchAsync');
+    const centred = this._centred, witness = wantWitness || centred;            // the centred second stage starts from remainder1
     const { off, K, G } = tallyGroups(offsets, B);
     const sum = new Uint16Array(G * N), value = new Uint8Array(G * N);
-    const q1 = wantWitness ? new Uint16Array(G * N) : null, r1 = wantWitness ? new Uint16Array(G * N) : null;
-    const q2 = wantWitness ? new Uint8Array(G * N) : null;
+    const q1 = witness ? new Uint16Array(G * N) : null, r1 = witness ? new Uint16Array(G * N) : null;
+    const q2 = witness ? new Uint8Array(G * N) : null;
     const args = [N, q, p, Int8Array.from(expandArray(this.f, N, 0)), Uint8Array.from(expandArray(this.fp, N, 0)), rows, weights, off, K, G, B,
       sum, value, q1, r1, q2];
     const res = { sum, value, quotient1: q1, remainder1: r1, quotient2: q2 };
     if (asynchronous) return engine().tallyDecryptBatchAsync(...args).then(() => res);
     engine().tallyDecryptBatch(...args);
-    return res;
+    if (!centred) return res;
+    const second = this._centredSecondStage(r1, G);
+    if (!wantWitness) return { sum, value: second.value, quotient1: null, remainder1: null, quotient2: null };
+    return { sum, value: second.value, quotient1: q1, remainder1: r1, quotient2: second.quotient2 };
   }
 
   // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed
   // from unpackBatch and tallyDecryptBatch (same results as ntru_tally_decrypt_packed_batch, not that call).
   tallyPackedBatch(packed, B, offsets = null, weights = null, wantWitness = true) {
+    this._refuseCentred('tallyPackedBatch');
     return this._tally(unpackRows(this.N, this.q, packed, B), B, offsets, weights, wantWitness, false);
   }
 
   // The same on device handles (devAlloc): offsetsDev holds G + 1 int64 row indices on the device (null: uniform groups of K rows); only
   // enqueues.  sumGroupsDev is the sum alone for any modulus.
   tallyBatchDev(fDev, fpDev, rowsDev, B, G, sumDev, valueDev, { offsetsDev = null, K = 0, weightsDev = null, q1Dev = null, r1Dev = null, q2Dev = null } = {}) {
+    this._refuseCentred('tallyBatchDev');
     engine().tallyDecryptBatchDev(this.N, this.q, this.p, fDev, fpDev, rowsDev, weightsDev, offsetsDev, K, G, B, sumDev, valueDev, q1Dev, r1Dev, q2Dev);
   }
 
@@ -561,6 +610,7 @@ export default class NTRU {
   }
   decryptBatchPerKey(keys, e, B, wantWitness = true, out = {}) {
     const { N, p, q } = this;
+    this._refuseCentred('decryptBatchPerKey');
     const [f, fp] = this._perKeyRows(keys, B, ['f', 'fp']);
     const value = out.value || new Uint8Array(B * N);
     const q1 = wantWitness ? (out.quotient1 || new Uint16Array(B * N)) : null;
@@ -586,6 +636,7 @@ export default class NTRU {
   pipelineAsync(opts) { return this._pipeline(opts, true); }
   _pipeline({ m, B, sampleR = null, r = null, decrypt = false, pack = false, want = null, out = {} }, asynchronous) {
     const { N, p, q, dr } = this;
+    if (decrypt) this._refuseCentred(asynchronous ? 'pipelineAsync with decrypt: true' : 'pipeline with decrypt: true');
     if (!(m instanceof Uint8Array) || m.length < B * N) throw new TypeError('pipeline: m must be a Uint8Array of B*N plaintext coefficients');
     if ((sampleR === null) === (r === null)) throw new TypeError('pipeline: give either sampleR: {key, firstItem} or r');
     const w = want || (pack ? {} : (decrypt ? { value: true } : { e: true }));
@@ -619,6 +670,7 @@ export default class NTRU {
   sampleRDev(key, firstItem, B, rDev) { engine().sampleTernaryDev(this.N, this.dr, this.dr, this.p - 1, key, firstItem, B, rDev); }
   encryptBatchDev(hDev, rDev, mDev, B, eDev, quotDev = null) { engine().encryptBatchDev(this.N, this.q, hDev, rDev, mDev, B, eDev, quotDev); }
   decryptBatchDev(fDev, fpDev, eDev, B, valueDev, q1Dev = null, r1Dev = null, q2Dev = null) {
+    this._refuseCentred('decryptBatchDev');
     engine().decryptBatchDev(this.N, this.q, this.p, fDev, fpDev, eDev, B, valueDev, q1Dev, r1Dev, q2Dev);
   }
   // one key pair per item on device buffers: hDev [B*N] u16 / fDev [B*N] i8, fpDev [B*N] u8 (e.g. generateKeysBatchDev's outputs)
@@ -626,6 +678,7 @@ export default class NTRU {
     engine().encryptPeritemBatchDev(this.N, this.q, hDev, rDev, mDev, B, eDev, quotDev);
   }
   decryptBatchPerKeyDev(fDev, fpDev, eDev, B, valueDev, q1Dev = null, r1Dev = null, q2Dev = null) {
+    this._refuseCentred('decryptBatchPerKeyDev');
     engine().decryptPeritemBatchDev(this.N, this.q, this.p, fDev, fpDev, eDev, B, valueDev, q1Dev, r1Dev, q2Dev);
   }
   static packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes = false) { engine().packBatchDev(maxVal, dataLen, dataDev, B, outDev, bytes); }
@@ -697,6 +750,7 @@ export default class NTRU {
 
   decryptBatchAsync(e, B, wantWitness = true, out = {}) {
     const { N, p, q } = this;
+    this._refuseCentred('decryptBatchAsync');
     const value = out.value || new Uint8Array(B * N);
     const q1 = wantWitness ? (out.quotient1 || new Uint16Array(B * N)) : null;
     const r1 = wantWitness ? (out.remainder1 || new Uint16Array(B * N)) : null;
@@ -774,10 +828,12 @@ export default class NTRU {
 
   // e: Uint16Array[blocks*N] -> { data: Uint8Array (cut to `length`, or trailing zero bytes stripped), flags: Uint8Array[blocks] }
   decryptBytes(e, blocks, length = null) {
+    this._refuseCentred('decryptBytes');
     if (blocks === 0) return this._rowsToBytes(new Uint8Array(0), 0, length);
     return this._rowsToBytes(this.decryptBatch(e, blocks, false).value, blocks, length);
   }
   decryptBytesAsync(e, blocks, length = null) {
+    this._refuseCentred('decryptBytesAsync');
     if (blocks === 0) return Promise.resolve(this._rowsToBytes(new Uint8Array(0), 0, length));
     return this.decryptBatchAsync(e, blocks, false).then(o => this._rowsToBytes(o.value, blocks, length));
   }

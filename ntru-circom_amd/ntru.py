@@ -13,10 +13,12 @@ SURVEY.md section 8 assigns to the shim.  Key generation (index.js:30-79) runs o
 extendedEuclideanAlgorithm, dividePolynomials by an arbitrary divisor and products modulo more than 65536 run on the
 engine's generic family (ntru_generic_*), which follows the reference step by step, non-units included.
 """
+import contextlib
 import secrets
 
 import numpy as np
 
+from . import lift as lift_calls
 from . import packed as packed_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
@@ -268,12 +270,21 @@ def unpackInput(maxVal, packedBits, data, engine=None):
 # ---- the scheme class --------------------------------------------------------------------------------------
 
 class NTRU:
-    """index.js:7-207, hot-path methods.  Every return value is made of plain Python lists / ints."""
+    """index.js:7-207, hot-path methods.  Every return value is made of plain Python lists / ints.
+
+    lift="reference" (the default) decrypts with index.js:117 verbatim and never touches the engine's mode; lift="centred" runs every
+    decrypt-family method (decryptBits, decryptStr, decryptBytes, tallyBatch, tallyPacked, decryptPackedBatch, decryptBatchPerKey, the
+    decrypt stage of pipeline) with the engine in the centred mode and puts the engine back into the mode it had (lift.py), so
+    an engine shared by two instances is never left in the other's mode.  The centred mode returns the plaintext where the reference's
+    `+ 1` does not (q = 4096 with p = 3, p = 5 or 7 at almost every q).  The `params` of a witness do not depend on the mode;
+    VerifyDecrypt (checkWitnesses) accepts a centred witness only when the addend (p - q % p) % p is 1."""
 
     def __init__(self, options=None, engine=None, **kw):
         opts = dict(N=167, p=3, q=128, df=61, dg=20, dr=18, f=None, fp=None, fq=None, g=None, h=None)  # index.js:9-23
+        opts["lift"] = "reference"
         opts.update(options or {})
         opts.update(kw)
+        lift_calls.mode_number(opts["lift"])                                                          # ValueError for an unknown mode
         for k, v in opts.items():
             setattr(self, k, v)
         self.I = [1] + [0] * (self.N - 1) + [-1]                                                      # index.js:25-27
@@ -284,6 +295,12 @@ class NTRU:
         if self._engine is None:
             self._engine = default_engine()
         return self._engine
+
+    def _lifted(self):
+        """The engine in this instance's lift for the duration of a decrypt-family call; the default mode leaves the engine alone."""
+        if lift_calls.mode_number(self.lift) == lift_calls.REFERENCE:
+            return contextlib.nullcontext()
+        return lift_calls.using(self.engine, lift_calls.CENTRED)
 
     def calculateNq(self):
         """index.js:201-203"""
@@ -325,7 +342,8 @@ class NTRU:
             raise TypeError("Cannot read property 'map' of null")                  # what index.js:112 does
         e_pad = expandArray(e, N)
         f_signed = expandArray(self.f, N)
-        value, q1, r1, q2 = self.engine.decrypt_batch(N, q, p, f_signed, expandArray(self.fp, N), [e_pad])
+        with self._lifted():
+            value, q1, r1, q2 = self.engine.decrypt_batch(N, q, p, f_signed, expandArray(self.fp, N), [e_pad])
         value = value[0].tolist()
         return {
             "value": trimPolynomial(value),
@@ -431,7 +449,8 @@ class NTRU:
         N, q, p = self.N, self.q, self.p
         e = np.asarray(e).reshape(-1, N)
         f, fp = self._per_key_rows(keys, e.shape[0], ["f", "fp"])
-        value, q1, r1, q2 = self.engine.decrypt_peritem_batch(N, q, p, f, fp, e)
+        with self._lifted():
+            value, q1, r1, q2 = self.engine.decrypt_peritem_batch(N, q, p, f, fp, e)
         return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- tallies: decryptBits of sums of ciphertexts -----------------------------------------------------------------------------------
@@ -445,8 +464,9 @@ class NTRU:
         rows = np.asarray(rows).reshape(-1, N)
         if weights is not None:
             weights = np.asarray(weights, dtype=np.int64) % q
-        total, value, q1, r1, q2 = self.engine.tally_decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), rows,
-                                                                   offsets=offsets, weights=weights, want_witness=wantWitness)
+        with self._lifted():
+            total, value, q1, r1, q2 = self.engine.tally_decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), rows,
+                                                                       offsets=offsets, weights=weights, want_witness=wantWitness)
         return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
@@ -457,9 +477,10 @@ class NTRU:
             raise TypeError("Cannot read property 'map' of null")
         if weights is not None:
             weights = np.asarray(weights, dtype=np.int64) % q
-        total, value, q1, r1, q2 = packed_calls.tally_decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N),
-                                                                           expandArray(self.fp, N), packed, offsets=offsets,
-                                                                           weights=weights, want_witness=wantWitness)
+        with self._lifted():
+            total, value, q1, r1, q2 = packed_calls.tally_decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N),
+                                                                               expandArray(self.fp, N), packed, offsets=offsets,
+                                                                               weights=weights, want_witness=wantWitness)
         return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     def decryptPackedBatch(self, packed, wantWitness=True):
@@ -468,8 +489,9 @@ class NTRU:
         N, q, p = self.N, self.q, self.p
         if self.f is None:
             raise TypeError("Cannot read property 'map' of null")
-        value, q1, r1, q2 = packed_calls.decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N), expandArray(self.fp, N),
-                                                              packed, want_witness=wantWitness)
+        with self._lifted():
+            value, q1, r1, q2 = packed_calls.decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N), expandArray(self.fp, N),
+                                                                  packed, want_witness=wantWitness)
         return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
@@ -531,10 +553,12 @@ class NTRU:
         want = set(want) if want is not None else (set() if pack else ({"value"} if decrypt else {"e"}))
         pad = lambda a, dt: np.array(list(a) + [0] * (N - len(a)), dtype=dt)
         key, first = (sampleR if sampleR is not None else (None, 0))
-        return self.engine.pipeline_batch(N, self.q, self.p, pad(self.h, np.uint16), m,
-                                          f=pad(self.f, np.int8) if decrypt else None, fp=pad(self.fp, np.uint8) if decrypt else None,
-                                          key=key, first_item=first, n1=self.dr, n2=self.dr, r=r, want_r="r" in want and key is not None,
-                                          want_e="e" in want, want_value="value" in want, want_packed=pack)
+        with (self._lifted() if decrypt else contextlib.nullcontext()):
+            return self.engine.pipeline_batch(N, self.q, self.p, pad(self.h, np.uint16), m,
+                                              f=pad(self.f, np.int8) if decrypt else None, fp=pad(self.fp, np.uint8) if decrypt else None,
+                                              key=key, first_item=first, n1=self.dr, n2=self.dr, r=r,
+                                              want_r="r" in want and key is not None, want_e="e" in want, want_value="value" in want,
+                                              want_packed=pack)
 
     # -- byte messages of any length, as packed bits (the reference's encryptStr takes at most N bits, index.js:81) ------------------
     @property
@@ -575,7 +599,8 @@ class NTRU:
         if self.f is None:
             raise TypeError("Cannot read property 'map' of null")                  # what index.js:112 does
         e = np.asarray(e, dtype=np.uint16).reshape(-1, N)
-        out, flags = self.engine.decrypt_bytes_batch(N, self.q, self.p, W, expandArray(self.f, N), expandArray(self.fp, N), e)
+        with self._lifted():
+            out, flags = self.engine.decrypt_bytes_batch(N, self.q, self.p, W, expandArray(self.f, N), expandArray(self.fp, N), e)
         data = out.tobytes()
         if length is None:
             return data.rstrip(b"\x00"), flags
