@@ -19,10 +19,22 @@ A row:
                                           witnesses of a call (the mutated ones come on top)
             keygen                        df, dg of a parameter set whose first draws hold non-units, and first = a first_item at which
                                           the B items from first, first - 1 and first - 2 on hold one (item 316 at N = 17)
+            sum_groups_packed             layout = the lane layout N gives the row's field width (packed_layout below): "side" (U <= 32,
+                                          several rows side by side in a wave), "row" (32 < U <= 64) or "tiles" (U > 64); weights as
+                                          for sum_groups.  The group layouts and the row counts are the runner's (B is not used): the
+                                          large launch takes its row count from the device's CU count
+            decrypt_packed                q is the scheme's modulus: one shape per field width, N with a field across a 64-bit limb
+                                          (where the width allows one) and a partial last element
   last    what ntru_engine_last_kernel() returns after the call
   rule    where the launcher writes a coarse name or none: the selection rule the shapes satisfy (nw = (N + 32) / 32 etc.)
   unreachable  set instead of shapes when no call the ABI accepts selects the instantiation, with the reason
+  addend_one_only  on a row of the decrypt family (LIFT_ENTRIES) whose selection rule admits no shape at which the centred lift's addend
+               (p - q % p) % p differs from 1, the reason; None on every other row.  The runners decrypt in both lift modes, and only at
+               such a shape do the modes give different values
 """
+import math
+
+import numpy as np
 
 ROWS = []
 
@@ -30,7 +42,7 @@ ROWS = []
 def _row(kernel, entry, shapes, last=None, rule=None, unreachable=None):
     ROWS.append({"kernel": kernel, "entry": entry,
                  "shapes": [dict(N=t[0], q=t[1], p=t[2], path=t[3], B=t[4], extra=dict(t[5]) if len(t) > 5 else {}) for t in shapes],
-                 "last": last, "rule": rule, "unreachable": unreachable})
+                 "last": last, "rule": rule, "unreachable": unreachable, "addend_one_only": None})
 
 
 # K of the vector-ALU families: the smallest odd K with ceil(N / 2K) <= 64
@@ -62,7 +74,7 @@ _row("k_encrypt<15>", "encrypt", [(1665, 2048, 0, 0, 3), (1920, 2048, 0, 0, 3)],
 
 # ---- decrypt (p = 3 unless stated) ----------------------------------------------------------------------------------------------
 _row("k_decrypt_m8", "decrypt", [(513, 2048, 3, 0, 95), (864, 4096, 3, 0, 97)], "k_decrypt_m8")
-_row("k_decrypt_m", "decrypt", [(2, 2048, 3, 4, 33), (1024, 8192, 3, 0, 95)], "k_decrypt_m")
+_row("k_decrypt_m", "decrypt", [(2, 2048, 3, 4, 33), (1024, 8192, 3, 0, 95), (128, 4096, 3, 4, 33)], "k_decrypt_m")
 # shared stepping: paths 2 and 3, odd N, K = ceil(N / 64) made odd in 9..13; ME = K for q <= 4096, 7 at q = 8192 (not for K = 13);
 # the dot8 second product where the item takes 32 lanes (ceil(N / 2K) == 32), K >= 11 and path != 3
 _row("k_decrypt_s<9, 9, false>", "decrypt", [(449, 2048, 3, 2, 3), (575, 4096, 3, 2, 3)], "k_decrypt_s<9,9>")
@@ -76,7 +88,7 @@ _row("k_decrypt_s<13, 13, true>", "decrypt", [(807, 2048, 3, 2, 3), (831, 4096, 
 # per-item stepping: path 2 only, the add path's rule (even N where the shared stepping would take odd N)
 _row("k_decrypt_t<1, 2>", "decrypt", [(65, 2048, 3, 2, 5), (128, 16384, 3, 2, 5)], "k_decrypt_t<1,2>")
 _row("k_decrypt_t<1, 1>", "decrypt", [(65, 32768, 3, 2, 5), (128, 32768, 3, 2, 5)], "k_decrypt_t<1,1>")
-_row("k_decrypt_t<3, 6>", "decrypt", [(193, 2048, 3, 2, 5), (384, 8192, 3, 2, 5)], "k_decrypt_t<3,6>")
+_row("k_decrypt_t<3, 6>", "decrypt", [(193, 2048, 3, 2, 5), (384, 8192, 3, 2, 5), (193, 4096, 3, 2, 5)], "k_decrypt_t<3,6>")
 _row("k_decrypt_t<3, 3>", "decrypt", [(193, 16384, 3, 2, 5), (384, 16384, 3, 2, 5)], "k_decrypt_t<3,3>")
 _row("k_decrypt_t<5, 10>", "decrypt", [(385, 2048, 3, 2, 5), (640, 4096, 3, 2, 5)], "k_decrypt_t<5,10>")
 _row("k_decrypt_t<5, 5>", "decrypt", [(385, 8192, 3, 2, 5), (640, 8192, 3, 2, 5)], "k_decrypt_t<5,5>")
@@ -173,7 +185,7 @@ _row("(anonymous namespace)::k_generic", "generic_multiply", [(1, 1 << 20, 0, 0,
 _row("k_encrypt_pi_m<true>", "encrypt_peritem", [(64, 256, 0, 4, 7), (128, 32, 0, 0, 7)], "k_encrypt_pi_m", "q <= 256")
 _row("k_encrypt_pi_m<false>", "encrypt_peritem", [(128, 512, 0, 0, 7), (1024, 8192, 0, 0, 7)], "k_encrypt_pi_m", "512 <= q <= 8192")
 _row("k_decrypt_pi_m<true>", "decrypt_peritem", [(64, 256, 3, 4, 7), (128, 32, 3, 0, 7)], "k_decrypt_pi_m", "q <= 256, p == 3")
-_row("k_decrypt_pi_m<false>", "decrypt_peritem", [(128, 512, 3, 0, 7), (1024, 8192, 3, 0, 7)], "k_decrypt_pi_m",
+_row("k_decrypt_pi_m<false>", "decrypt_peritem", [(128, 512, 3, 0, 7), (1024, 8192, 3, 0, 7), (128, 4096, 3, 0, 7)], "k_decrypt_pi_m",
      "512 <= q <= 8192, p == 3")
 # the composed path: N below the matrix range, q above it, a kernel path without the matrix kernels, p != 3 (decrypt)
 _COMPOSED = [(2, 2048, 3, 0, 7), (127, 2048, 3, 0, 7), (128, 16384, 3, 0, 7), (128, 2048, 3, 1, 7)]
@@ -211,6 +223,87 @@ _KEYGEN = [(7, 32, 3, 0, 16, dict(df=2, dg=2, first=125)), (17, 32, 3, 0, 8, dic
 for _k in ("k_sample_ternary_listed", "k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
     _row(_NS + _k, "keygen", _KEYGEN, "k_keygen", "ntru_keygen_batch_dev with a non-unit among the first draws")
 
+# ---- packed ciphertexts (packed_ciphertexts.hip) ------------------------------------------------------------------------------------------
+SP_BATCH, SP_WAVES_PER_CU = 4, 8      # row steps in flight and waves per CU of k_sum_groups_packed, as the kernel file sets them
+
+
+def packed_layout(bits, N):
+    """How k_sum_groups_packed lays a row of `bits`-wide fields out, restated from per = 252 // bits: os elements of `slices` units, U
+    units a row, `side` rows side by side in a wave, NT wavefronts (tiles of 64 units) a row."""
+    per = 252 // bits
+    os_ = max(-(-N // per), 3)
+    slices = (per + 31) // 32 if per > 36 else 1
+    U = os_ * slices
+    return {"per": per, "os": os_, "slices": slices, "U": U, "side": 64 // U if U <= 32 else 1, "NT": 1 if U <= 64 else -(-U // 64),
+            "layout": "side" if U <= 32 else ("row" if U <= 64 else "tiles")}
+
+
+def packed_shape_ns(bits):
+    """{layout: N}, one N per lane layout the width reaches at N <= 1920.  "side" at the smallest row, N = 2 per + 1: os = 3, the third
+    element holds one coefficient (nv = 1; for the sliced widths whole units lie behind N), and an unsliced width has side = 21, the
+    deepest cross-lane tree and no power of two.  "row" and "tiles" at the smallest N that gives them."""
+    per = 252 // bits
+    slices = packed_layout(bits, 2)["slices"]
+    out = {"side": 2 * per + 1}
+    for name, above in (("row", 32), ("tiles", 64)):
+        N = (above // slices) * per + 1                     # os = above // slices + 1 elements: the first U above the bound
+        if N <= 1920:
+            out[name] = N
+    return out
+
+
+def _coprime_from(x, R):
+    while math.gcd(x, R) != 1:
+        x += 1
+    return x
+
+
+def many_rows_per_block(bits, N, cus):
+    """(first row, T, R, Pb, offsets) of one launch of k_sum_groups_packed on a device of `cus` CUs in which every row block holds R
+    rows, R = SP_BATCH side + side + 1: the four-step loop, the one-step loop and a last step of fewer than `side` rows all run inside a
+    block (launches of at most Pb rows have one row per block, and k_sum_groups_finish does all the adding).  Pb as launch_sum_packed
+    computes it (sum_row_blocks), R as cut_of does.  The offsets start behind row 0 and hold a group across several block boundaries,
+    empty groups, and groups of sizes coprime to R, which lie wholly inside a block (stored from the registers through the lane tree)
+    and across one boundary at every phase."""
+    lay = packed_layout(bits, N)
+    Pb = max(1, min(32768, cus * SP_WAVES_PER_CU // lay["NT"]))
+    side = lay["side"]
+    R = SP_BATCH * side + side + 1
+    T = (R - 1) * Pb + 1
+    first = 3
+    sizes = [3 * R + 1, 0, 0]
+    cycle = [R - 1, _coprime_from(R // 2, R), 1, 0, R + 1, _coprime_from(2 * side + 1, R)]
+    total, i = sum(sizes), 0
+    while total < T:
+        sizes.append(min(cycle[i % len(cycle)], T - total))
+        total += sizes[-1]
+        i += 1
+    off = first + np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    assert off[-1] - off[0] == T and T > Pb and -(-T // Pb) == R, (T, Pb, R)
+    size = np.diff(off)
+    lo, hi = (off[:-1] - first) // R, (off[1:] - 1 - first) // R            # first and last block of a group that is not empty
+    inside, across = (size > 0) & (lo == hi), (size > 0) & (hi == lo + 1)
+    assert (size == 0).any() and inside.any() and across.any() and (hi > lo + 2).any(), (bits, N, cus)
+    assert (size[inside] >= SP_BATCH * side + side).any(), (bits, N, cus)     # a group inside a block runs the four-step loop and the other
+    assert side == 1 or (size[inside] % side != 0).any(), (bits, N, cus)      # and one ends on a step of fewer than `side` rows
+    return first, T, R, Pb, off
+
+
+for _bits in range(1, 17):
+    for _P2 in (True, False):
+        if _bits == 1 and not _P2:
+            continue                                        # mod = 2 is a power of two
+        # no power of two: the largest modulus of the width, and the smallest, which a raw field exceeds by almost a factor of two
+        _mods = [1 << _bits] if _P2 else sorted({(1 << _bits) - 1, (1 << (_bits - 1)) + 1}, reverse=True)
+        for _WT in (False, True):
+            _row(_NS + "k_sum_groups_packed<%d, %s, %s>" % (_bits, str(_P2).lower(), str(_WT).lower()), "sum_groups_packed",
+                 [(_N, _mod, 0, 0, 0, dict(layout=_lay, weights=_WT)) for _lay, _N in packed_shape_ns(_bits).items() for _mod in _mods],
+                 "k_sum_groups_packed<%d,%d,%d>" % (_bits, _P2, _WT))
+# a field across a 64-bit limb needs a width that does not divide 64; the third element is partial at every shape
+_row(_NS + "k_unpack_rows", "decrypt_packed",
+     [(2 * (252 // _bits) + 64 // _bits + 2, 1 << _bits, 3, 0, 5) for _bits in range(1, 17)], None,
+     "every ntru_decrypt_packed_batch_dev call: every field width the decrypt entry admits (q = 2 .. 65536)")
+
 BY_KERNEL = {r["kernel"]: r for r in ROWS}
 assert len(BY_KERNEL) == len(ROWS), "duplicate row"
 # every string ntru_engine_last_kernel() may return after a call of the scheme entry points: the rows of these entries only (the
@@ -218,3 +311,22 @@ assert len(BY_KERNEL) == len(ROWS), "duplicate row"
 SCHEME_ENTRIES = ("encrypt", "decrypt", "decrypt_pack", "verify_keys", "polymul_split", "public_key", "generic_multiply")
 LAST_KERNELS = {r["last"] for r in ROWS if r["last"] and r["entry"] in SCHEME_ENTRIES} | {"k_invert_key", "k_sample_ternary", "k_encrypt_wp"}
 assert len(LAST_KERNELS) == 84, len(LAST_KERNELS)
+
+# ---- the lift (both modes on every row of the decrypt family) ---------------------------------------------------------------------------------
+LIFT_ENTRIES = ("decrypt", "decrypt_pack", "decrypt_peritem")
+
+
+def lift_addend(q, p):
+    """What the centred lift adds to x > q/2 in place of the reference's 1."""
+    return (p - q % p) % p
+
+
+# These kernels need p = 3, where the addend is 1 for q = 2^odd and 2 for q = 2^even, and their mask interval ME admits one q only:
+# 65535 / (q - 1) - 1 must reach ME and stay below the next interval of the same K.
+for _k, _why in (("k_decrypt_s<9, 7, false>", "ME = 7 below K = 9: q = 8192 only"),
+                 ("k_decrypt_s<11, 7, false>", "ME = 7 below K = 11: q = 8192 only"),
+                 ("k_decrypt_s<11, 7, true>", "ME = 7 below K = 11: q = 8192 only"),
+                 ("k_decrypt_t<1, 1>", "ME = 1 and not 2: q = 32768 only"),
+                 ("k_decrypt_t<5, 5>", "ME = 5 and not 10: q = 8192 only"),
+                 ("k_decrypt_t<7, 7>", "ME = 7 and not 14: q = 8192 only")):
+    BY_KERNEL[_k]["addend_one_only"] = _why

@@ -19,9 +19,10 @@ def _kernel_tus():
 
 
 KERNEL_TUS = _kernel_tus()
-assert len(KERNEL_TUS) >= 12 and len(set(KERNEL_TUS)) == len(KERNEL_TUS), KERNEL_TUS
+assert len(KERNEL_TUS) >= 13 and len(set(KERNEL_TUS)) == len(KERNEL_TUS), KERNEL_TUS
 # the shipped library: (EXTRA, fewest wide stores the scan must see).  Counted once on the default build's ISA: 173 dwordx3 / dwordx4
-# stores in the twelve translation units (matrix_rowimage 108, keygen_sampler_pack 54, ciphertext_sum 8, message_bytes 3).
+# stores in the thirteen translation units (matrix_rowimage 108, keygen_sampler_pack 54, ciphertext_sum 8, message_bytes 3;
+# packed_ciphertexts has none).
 BUILDS = {"default": ("", 173)}
 
 
@@ -53,7 +54,8 @@ def test_no_kernel_spills_to_scratch(build, asm_dirs):
     bad = [(n, s) for n, s in zip(names, scratch) if s]
     assert not bad, bad
     for must in ("k_encrypt_t", "k_decrypt_s", "k_encrypt", "k_decrypt", "k_verify_keys", "k_polymul_split", "k_encrypt_wp", "k_decrypt_mp",
-                 "k_check_decrypt", "k_keygen_scatter", "k_decrypt_pi_m", "k_sum_groups_finish", "k_rows_to_bytes"):
+                 "k_check_decrypt", "k_keygen_scatter", "k_decrypt_pi_m", "k_sum_groups_finish", "k_rows_to_bytes", "k_sum_groups_packed",
+                 "k_unpack_rows"):
         assert any(must in n for n in names), must
 
 
@@ -130,7 +132,7 @@ def test_every_kernel_instantiation_has_a_variant_row(build, asm_dirs):
     out = subprocess.run(["/usr/bin/c++filt"], input="\n".join(mangled), capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stderr
     compiled = {_instantiation(d) for d in out.stdout.split("\n") if d.strip()}
-    assert len(compiled) >= 124, len(compiled)               # 100 of the first seven files, 24 of the five newer ones
+    assert len(compiled) >= 187, len(compiled)               # 100 of the first seven files, 24 of the five newer ones, 63 packed
     rows = [r["kernel"] for r in kv.ROWS]
     assert len(rows) == len(set(rows)), "duplicate rows"
     assert not compiled - set(rows), ("compiled without a row", sorted(compiled - set(rows)))

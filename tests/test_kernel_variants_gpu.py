@@ -2,7 +2,8 @@
 CPU oracle, on the operand values and batch sizes where kernels go wrong; p != 3 on every kernel that takes p; and a dispatch sweep
 over every N of kernel paths 0-3, so that a launcher cannot ask for an instantiation that does not exist.  The rows of the per-item
 scheme, the segmented sums, the byte codec, the witness checks and key generation run against the references their own test modules
-use (tests/peritem_ref.py, ciphertext_sum_ref.py, message_bytes_ref.py, witness_circuit.py, keygen_ref.py)."""
+use (tests/peritem_ref.py, ciphertext_sum_ref.py, message_bytes_ref.py, witness_circuit.py, keygen_ref.py, packed_ref.py).  Every
+row of the decrypt family runs each call in both lift modes: the default against the oracle, the centred one against tests/lift_ref.py."""
 import numpy as np
 import pytest
 
@@ -10,7 +11,9 @@ import __graft_entry__ as ge
 import ciphertext_sum_ref as sum_ref
 import kernel_variants as kv
 import keygen_ref
+import lift_ref
 import message_bytes_ref as bytes_ref
+import packed_ref
 import peritem_ref
 import witness_circuit as wc
 from oracle import ntru_keygen as kg
@@ -18,6 +21,7 @@ from oracle import ntru_oracle as orc
 
 pytestmark = pytest.mark.gpu
 pkg = ge.load_package()
+lift = pkg.lift
 
 WAVES_PER_BLOCK = 4
 P3_ONLY = ("k_decrypt_s", "k_decrypt_t", "k_decrypt_m", "k_verify_keys_t", "k_verify_keys_m")
@@ -96,8 +100,10 @@ def batch_sizes(kernel, shape):
         return sorted({B, *PERITEM_B})
     if entry in ("bytes_to_rows", "rows_to_bytes"):
         return sorted({1, 3, B})
-    if entry == "sum_groups":
+    if entry in ("sum_groups", "sum_groups_packed"):
         return [B]                                   # the group layouts are the runner's
+    if entry == "decrypt_packed":
+        return sorted({1, B})
     if entry.startswith("check_") or entry == "keygen":
         return sorted({1, B})
     out = {1, B}
@@ -146,15 +152,49 @@ def decrypt_key(rng, N, p, variant):
     return f, fp
 
 
+LIFT_DIFFERED = []               # per call of in_both_lift_modes since the test last cleared it: did the two modes' outputs differ
+
+
+def in_both_lift_modes(eng, q, p, call, centred_want, ctx, same_in_both=()):
+    """call() once in the default mode and once inside lift.using(eng, "centred").  The centred outputs are compared here with
+    centred_want() (tests/lift_ref.py); the default outputs are returned for the caller's comparison with the oracle, and the kernel
+    must be the same one.  The outputs at the indices `same_in_both` (quotient1, remainder1) do not depend on the lift; where the
+    centred addend is 1 nothing does.  Where it is not 1 the two references say which outputs differ, so the byte comparisons hold
+    the kernel to it: whether they did goes into LIFT_DIFFERED, and test_variant_row_equals_oracle asserts that every shape with such
+    an addend told the modes apart (a single call need not: B = 1 with e = q - 1 and f = -1 has remainder1 = N, below q/2)."""
+    got = call()
+    kernel = eng.last_kernel()
+    with lift.using(eng, "centred"):
+        assert lift.get_lift(eng) == 1
+        centred = call()
+        assert eng.last_kernel() == kernel, (ctx, kernel, eng.last_kernel())
+    assert lift.get_lift(eng) == 0, ctx
+    assert_equal(centred, centred_want(), (ctx, "centred"))
+    for i in same_in_both:
+        if i < len(got):
+            assert got[i].tobytes() == centred[i].tobytes(), (ctx, "output %d depends on the lift mode" % i)
+    differ = any(g.tobytes() != c.tobytes() for g, c in zip(got, centred))
+    if lift_ref.addend(q, p, lift_ref.CENTRED) == 1:
+        assert not differ, (ctx, "addend 1: the modes must give the same bytes")
+    LIFT_DIFFERED.append(differ)
+    return got
+
+
 def run_decrypt(eng, N, q, p, B, rng, variant, witness=True):
     f, fp = decrypt_key(rng, N, p, variant)
     e = e_rows(rng, N, q, B)
-    with Dev(eng) as d:
-        outs = [d.out((B, N), dt) for dt in (np.uint8, np.uint16, np.uint16, np.uint8)]
-        if not witness:
-            outs[1:] = [None] * 3
-        eng.decrypt_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, *outs)
-        got = [d.get(o, (B, N), dt) for o, dt in zip(outs, (np.uint8, np.uint16, np.uint16, np.uint8)) if o]
+    dts = (np.uint8, np.uint16, np.uint16, np.uint8)
+
+    def call():
+        with Dev(eng) as d:
+            outs = [d.out((B, N), dt) for dt in dts]
+            if not witness:
+                outs[1:] = [None] * 3
+            eng.decrypt_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, *outs)
+            return [d.get(o, (B, N), dt) for o, dt in zip(outs, dts) if o]
+
+    centred = lambda: list(lift_ref.decrypt(N, q, p, f, fp, e, lift_ref.CENTRED))[:4 if witness else 1]
+    got = in_both_lift_modes(eng, q, p, call, centred, ("decrypt", N, q, p, B, variant), same_in_both=(1, 2))
     want = orc.decrypt_batch(N, q, p, f, fp, e, want_witness=witness)
     return got, [w for w in want if w is not None]
 
@@ -163,11 +203,19 @@ def run_decrypt_pack(eng, N, q, p, B, rng, variant, fused=True):
     f, fp = decrypt_key(rng, N, p, variant)
     e = e_rows(rng, N, q, B)
     os_ = orc.pack_params(p - 1, N)["outputSize"]
-    with Dev(eng) as d:
-        dv = None if fused else d.out((B, N), np.uint8)
-        dp = d.out((B, os_, 4), np.uint64)
-        eng.decrypt_pack_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, dv, dp)
-        got = [d.get(dp, (B, os_, 4), np.uint64)] + ([] if fused else [d.get(dv, (B, N), np.uint8)])
+
+    def call():
+        with Dev(eng) as d:
+            dv = None if fused else d.out((B, N), np.uint8)
+            dp = d.out((B, os_, 4), np.uint64)
+            eng.decrypt_pack_batch_dev(N, q, p, d.up(f), d.up(fp), d.up(e), B, dv, dp)
+            return [d.get(dp, (B, os_, 4), np.uint64)] + ([] if fused else [d.get(dv, (B, N), np.uint8)])
+
+    def centred():
+        value = lift_ref.decrypt(N, q, p, f, fp, e, lift_ref.CENTRED)[0]
+        return [orc.pack_batch(p - 1, N, value)] + ([] if fused else [value])
+
+    got = in_both_lift_modes(eng, q, p, call, centred, ("decrypt_pack", N, q, p, B, variant))
     value = orc.decrypt_batch(N, q, p, f, fp, e, want_witness=False)[0]
     return got, [orc.pack_batch(p - 1, N, value)] + ([] if fused else [value])
 
@@ -365,7 +413,10 @@ def run_decrypt_peritem(eng, N, q, p, B, rng, variant):
     witness = variant != 1
     want = peritem_ref.oracle_decrypt(N, q, p, f, fp, e)
     peritem_ref.assert_lift_edges_met(N, q, f, want[2])
-    return decrypt_peritem_call(eng, N, q, p, f, fp, e, witness), list(want if witness else want[:1])
+    centred = lambda: list(lift_ref.decrypt_peritem(N, q, p, f, fp, e, lift_ref.CENTRED))[:4 if witness else 1]
+    got = in_both_lift_modes(eng, q, p, lambda: decrypt_peritem_call(eng, N, q, p, f, fp, e, witness), centred,
+                             ("decrypt_peritem", N, q, p, B, variant), same_in_both=(1, 2))
+    return got, list(want if witness else want[:1])
 
 
 def csr_offsets(B):
@@ -397,6 +448,91 @@ def run_sum_groups(eng, N, mod, B, rng, variant, extra):
         assert eng.last_kernel() == "k_sum_groups<%d,%d>" % (mod & (mod - 1) == 0, weighted), eng.last_kernel()
         want.append(sum_ref.np_sum(rows, mod, offsets=off, K=K, weights=w).astype(np.uint16))
     return got, want
+
+
+# ---- packed ciphertexts (packed_ciphertexts.hip) -----------------------------------------------------------------------------------------
+
+_packed_pool = {}                 # (bits, N) -> (rows, packed) of the width last used: shared by the rows and moduli of that width
+_packed_want = {}                 # the unweighted reference sums of the large launch: they do not depend on the variant
+
+
+def packed_pool(bits, N, nrows):
+    """nrows raw rows and their packed form with every ignored bit set.  Row 0 is all ones, the others are random fields below 2^bits
+    (not below mod).  The dense rows are packed_ref.unpack_rows of the packed ones, unpacked once: np_sum_packed is np_sum on them."""
+    if (bits, N) not in _packed_pool or len(_packed_pool[bits, N][0]) < nrows:
+        for k in [k for k in _packed_pool if k[0] != bits]:
+            del _packed_pool[k]
+        for k in [k for k in _packed_want if k[0] != bits]:
+            del _packed_want[k]
+        rng = np.random.default_rng(1000 * bits + N)
+        rows = rng.integers(0, 1 << bits, (nrows, N), dtype=np.uint16)
+        rows[0] = (1 << bits) - 1
+        mod = 1 << bits                                  # the format depends on the width alone
+        packed = packed_ref.set_ignored_bits(mod, N, packed_ref.pack_rows(mod, rows))
+        assert np.array_equal(packed_ref.unpack_rows(mod, N, packed), rows)
+        assert packed_ref.params(mod - 1, N)[0] == bits
+        _packed_pool[bits, N] = (rows, packed)
+    return _packed_pool[bits, N]
+
+
+def run_sum_groups_packed(eng, N, mod, rng, variant, extra):
+    """k_sum_groups_packed against packed_ref.np_sum_packed, bit for bit.  The small layouts of run_sum_groups (one row per block:
+    k_sum_groups_finish does the adding) and one launch with many rows per block (many_rows_per_block).  variant: the weights (all
+    mod - 1, zero, random) and, at 2, the packed base 8 bytes off 16-byte alignment, weights and output 2 bytes off 4-byte alignment."""
+    bits = (mod - 1).bit_length()
+    lay = kv.packed_layout(bits, N)
+    assert lay["layout"] == extra["layout"], (lay, extra)
+    weighted = extra["weights"]
+    pow2 = mod & (mod - 1) == 0
+    import torch
+    first, T, R, Pb, big_off = kv.many_rows_per_block(bits, N, torch.cuda.get_device_properties(0).multi_processor_count)
+    side = lay["side"]
+    # sized from this card's CU count: were the launch cut into more blocks than assumed, every block would hold one row again
+    assert -(-T // Pb) == R and R > kv.SP_BATCH * side + side, (T, Pb, R, side)
+    rows, packed = packed_pool(bits, N, first + T + 2)                      # two rows behind the last offset
+    layouts = [(K * G, K, None) for K in (1, 3, 40) for G in (1, 2)] + [(47, None, csr_offsets(47)), (first + T + 2, None, big_off)]
+    shift = 2 if variant == 2 else 0
+    got, want = [], []
+    for nrows, K, off in layouts:
+        w = None
+        if weighted:
+            w = [np.full(nrows, mod - 1), np.zeros(nrows), rng.integers(0, mod, nrows)][variant].astype(np.uint16)
+        G = nrows // K if off is None else len(off) - 1
+        with Dev(eng) as d:
+            do = d.out((G, N), np.uint16, shift)
+            pkg.sum_groups_packed_dev(eng, N, mod, d.up(packed[:nrows], 8 if variant == 2 else 0), do, G,
+                                      d_offsets=None if off is None else d.up(off), K=K, d_weights=None if w is None else d.up(w, shift))
+            got.append(d.get(do, (G, N), np.uint16))
+        assert eng.last_kernel() == "k_sum_groups_packed<%d,%d,%d>" % (bits, pow2, weighted), eng.last_kernel()
+        key = (bits, N, mod)
+        if off is big_off and w is None and key in _packed_want:
+            want.append(_packed_want[key])
+            continue
+        want.append(sum_ref.np_sum(rows[:nrows], mod, offsets=off, K=K, weights=w).astype(np.uint16))
+        if off is big_off and w is None:
+            _packed_want[key] = want[-1]
+    return got, want
+
+
+def run_decrypt_packed(eng, N, q, p, B, rng, variant):
+    """k_unpack_rows through ntru_decrypt_packed_batch_dev: packed rows of raw fields with every ignored bit set, against the oracle's
+    decrypt of packed_ref.unpack_rows; the four outputs, and at variant 1 the value alone."""
+    witness = variant != 1
+    f, fp = decrypt_key(rng, N, p, variant)
+    e = rows_cycle(B, [lambda b: np.full(N, q - 1), lambda b: rng.integers(0, q, N), lambda b: np.zeros(N)]).astype(np.uint16)
+    packed = packed_ref.set_ignored_bits(q, N, packed_ref.pack_rows(q, e))
+    assert not np.array_equal(packed, packed_ref.pack_rows(q, e))
+    dense = packed_ref.unpack_rows(q, N, packed)
+    assert np.array_equal(dense, e)
+    dts = (np.uint8, np.uint16, np.uint16, np.uint8)
+    with Dev(eng) as d:
+        outs = [d.out((B, N), dt) for dt in dts]
+        if not witness:
+            outs[1:] = [None] * 3
+        pkg.decrypt_packed_batch_dev(eng, N, q, p, d.up(f), d.up(fp), d.up(packed), B, *outs)
+        got = [d.get(o, (B, N), dt) for o, dt in zip(outs, dts) if o]
+    want = orc.decrypt_batch(N, q, p, f, fp, dense, want_witness=witness)
+    return got, [w for w in want if w is not None]
 
 
 def message_bytes(rng, nbytes, B):
@@ -514,6 +650,10 @@ def run_shape(eng, entry, s, B, rng, variant):
         return run_decrypt_peritem(eng, N, q, p, B, rng, variant)
     if entry == "sum_groups":
         return run_sum_groups(eng, N, q, B, rng, variant, s["extra"])
+    if entry == "sum_groups_packed":
+        return run_sum_groups_packed(eng, N, q, rng, variant, s["extra"])
+    if entry == "decrypt_packed":
+        return run_decrypt_packed(eng, N, q, p, B, rng, variant)
     if entry == "bytes_to_rows":
         return run_bytes_to_rows(eng, N, s["extra"]["nbytes"], B, rng, variant)
     if entry == "rows_to_bytes":
@@ -573,6 +713,7 @@ def test_variant_row_equals_oracle(eng, row):
     try:
         for s in row["shapes"]:
             eng.set_kernel_path(s["path"])
+            del LIFT_DIFFERED[:]
             for B in batch_sizes(row["kernel"], s):
                 for variant in range(3):
                     got, want = run_shape(eng, row["entry"], s, B, rng, variant)
@@ -584,6 +725,9 @@ def test_variant_row_equals_oracle(eng, row):
                     if row["entry"] == "encrypt_pack":
                         assert eng.last_kernel() == "k_encrypt_wp", ctx
                     assert_equal(got, want, ctx)
+            if row["entry"] in kv.LIFT_ENTRIES:
+                # every call ran in both lift modes; at an addend other than 1 the shape's calls told them apart
+                assert LIFT_DIFFERED and any(LIFT_DIFFERED) == (kv.lift_addend(s["q"], s["p"]) != 1), (row["kernel"], s, LIFT_DIFFERED)
     finally:
         eng.set_kernel_path(0)
         eng.set_sampler_rounds(20)

@@ -253,3 +253,19 @@ def test_the_real_library_exports_and_checks():
     assert lib.ntru_engine_get_lift(None) == 0
     header = open(ge.ROOT + "/include/ntru_engine.h").read()
     assert "#define NTRU_LIFT_REFERENCE 0" in header and "#define NTRU_LIFT_CENTRED 1" in header
+
+
+def test_every_decrypt_row_of_the_variant_table_has_a_shape_that_tells_the_modes_apart():
+    """tests/test_kernel_variants_gpu.py decrypts every shape in both lift modes; only where the centred addend is not 1 can a wrong
+    addend show.  Exactly the rows whose selection rule admits no such q say so (addend_one_only), and no other row lacks the shape."""
+    import kernel_variants as kv
+    family = [r for r in kv.ROWS if r["entry"] in kv.LIFT_ENTRIES]
+    assert len(family) == 32
+    for q, p in ((2048, 3), (8192, 3), (32768, 3), (4096, 3), (16384, 3), (65536, 5)):
+        assert kv.lift_addend(q, p) == ref.addend(q, p, ref.CENTRED)
+    without = {r["kernel"] for r in family if all(ref.addend(s["q"], s["p"], ref.CENTRED) == 1 for s in r["shapes"])}
+    noted = {r["kernel"] for r in kv.ROWS if r["addend_one_only"]}
+    assert without == noted == {"k_decrypt_s<9, 7, false>", "k_decrypt_s<11, 7, false>", "k_decrypt_s<11, 7, true>", "k_decrypt_t<1, 1>",
+                                "k_decrypt_t<5, 5>", "k_decrypt_t<7, 7>"}
+    for k in noted:                                     # their rule: p = 3 and a single q = 2^odd
+        assert {(s["q"], s["p"]) for s in kv.BY_KERNEL[k]["shapes"]} in ({(8192, 3)}, {(32768, 3)})

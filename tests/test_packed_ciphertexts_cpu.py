@@ -199,3 +199,59 @@ def test_sum_ref_is_the_checker_of_the_dense_sums():
     """np_sum_packed is np_sum on the unpacked rows: the checker of tests/test_ciphertext_sum_gpu.py, unchanged."""
     rows = np.random.default_rng(1).integers(0, 4096, (40, 821), dtype=np.uint16)
     assert np.array_equal(ref.np_sum_packed(4096, 821, ref.pack_rows(4096, rows), K=8), sum_ref.np_sum(rows, 4096, K=8))
+
+
+def test_variant_rows_reach_every_lane_layout_of_every_width(lib):
+    """The 62 sum rows of tests/kernel_variants.py: each has one shape per lane layout its width reaches at N <= 1920, and every shape
+    gives the layout it claims.  U and side are restated here from 252 // bits, the format from the library's own ntru_pack_params; the
+    large launch of each shape has blocks of more than SP_BATCH side + side rows whatever the CU count."""
+    import kernel_variants as kv
+    src = open(os.path.join(ge.PKG_DIR, "csrc", "packed_ciphertexts.hip")).read()
+    assert re.search(r"SP_BATCH = (\d+);", src).group(1) == str(kv.SP_BATCH)
+    assert re.search(r"SP_WAVES_PER_CU = (\d+);", src).group(1) == str(kv.SP_WAVES_PER_CU)
+    rows = [r for r in kv.ROWS if r["entry"] == "sum_groups_packed"]
+    assert len(rows) == 62
+    tiles_widths = set()
+    for r in rows:
+        m = re.fullmatch(r"\(anonymous namespace\)::k_sum_groups_packed<(\d+), (true|false), (true|false)>", r["kernel"])
+        bits, pow2, weighted = int(m.group(1)), m.group(2) == "true", m.group(3) == "true"
+        assert r["last"] == "k_sum_groups_packed<%d,%d,%d>" % (bits, pow2, weighted)
+        mods = {s["q"] for s in r["shapes"]}
+        assert mods == ({1 << bits} if pow2 else {(1 << bits) - 1, (1 << (bits - 1)) + 1}), r["kernel"]
+        per = 252 // bits
+        slices = -(-per // 32) if per > 36 else 1
+        seen = {}
+        for s in r["shapes"]:
+            N, mod = s["N"], s["q"]
+            assert 2 <= N <= 1920 and (mod & (mod - 1) == 0) == pow2 and s["extra"]["weights"] == weighted
+            b, pr, al, os_ = (C.c_int() for _ in range(4))
+            assert lib.ntru_pack_params(mod - 1, N, C.byref(b), C.byref(pr), C.byref(al), C.byref(os_)) == 0
+            assert (b.value, pr.value) == (bits, per), (r["kernel"], s)
+            U = os_.value * slices
+            layout = "side" if U <= 32 else ("row" if U <= 64 else "tiles")
+            assert layout == s["extra"]["layout"], (r["kernel"], s, U)
+            lay = kv.packed_layout(bits, N)
+            side = 64 // U if U <= 32 else 1
+            assert (lay["os"], lay["U"], lay["side"], lay["NT"]) == (os_.value, U, side, 1 if U <= 64 else -(-U // 64))
+            seen.setdefault(layout, set()).add(N)
+            if layout == "side":
+                assert os_.value == 3 and N == 2 * per + 1 and (side == 21) == (slices == 1)
+            else:                                   # the smallest N of the layout: one coefficient fewer is one element fewer
+                assert kv.packed_layout(bits, N - 1)["layout"] != layout
+            for cus in (256, 304, 80, 20):
+                first, T, R, Pb, off = kv.many_rows_per_block(bits, N, cus)
+                assert first > 0 and R > kv.SP_BATCH * side + side and (R - 1) * Pb < T <= R * Pb
+        assert all(len(ns) == 1 for ns in seen.values())
+        reachable = {"side", "row"} | ({"tiles"} if (64 // slices) * per + 1 <= 1920 else set())
+        assert set(seen) == reachable, (r["kernel"], seen)
+        if "tiles" in seen:
+            tiles_widths.add(bits)
+    assert tiles_widths == {3, 5, 6, 9, 10, 11, 12, 13, 14, 15, 16}
+    unpack = kv.BY_KERNEL["(anonymous namespace)::k_unpack_rows"]
+    assert [s["q"] for s in unpack["shapes"]] == [1 << b for b in range(1, 17)]
+    for s in unpack["shapes"]:
+        bits = s["q"].bit_length() - 1
+        per = 252 // bits
+        assert s["N"] % per and s["N"] > 2 * per                                             # a partial last element
+        straddles = [j for j in range(min(per, s["N"])) if j * bits // 64 != (j * bits + bits - 1) // 64]
+        assert bool(straddles) == (64 % bits != 0), s

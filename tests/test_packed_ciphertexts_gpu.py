@@ -1,5 +1,7 @@
 """Sums, tallies and decrypts of ciphertexts that arrive as packOutput(q - 1, N, e) rows, on the GPU, byte for byte: against the
-restatement (tests/packed_ref.py) and against the dense calls on the unpacked rows, at one shape per path of the kernel (packed_ref.SHAPES), with every bit set that a reader must ignore."""
+restatement (tests/packed_ref.py) and against the dense calls on the unpacked rows, at one shape per path of the kernel (packed_ref.SHAPES), with every bit set that a reader must ignore.
+Every instantiation of the sum kernel, and its launches with many rows per block, are the variant table's (tests/kernel_variants.py); here
+one tally rides on such a launch, and one decrypt takes more than one pass of unpacking."""
 import ctypes as C
 import json
 import os
@@ -8,7 +10,9 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+import kernel_variants as kv
 import packed_ref as ref
+from oracle import ntru_oracle as orc
 
 pytestmark = pytest.mark.gpu
 pkg = ge.load_package()
@@ -206,6 +210,60 @@ def test_decrypt_and_tally_equal_the_dense_calls(eng, N, q, B):
         assert ei.value.code == 2 and "d_sum" in str(ei.value)
     finally:
         d.free()
+    if (N, q) == (167, 2048):
+        tally_with_many_rows_per_block(eng, N, q, p, f, fp)
+
+
+def tally_with_many_rows_per_block(eng, N, q, p, f, fp):
+    """One tally whose packed sum has row blocks of R > SP_BATCH side + side rows (kernel_variants.many_rows_per_block, sized from the
+    CU count): the sums come out of the kernel's own loops and lane tree, not of k_sum_groups_finish on one-row partials."""
+    import torch
+    bits = (q - 1).bit_length()
+    first, T, R, Pb, off = kv.many_rows_per_block(bits, N, torch.cuda.get_device_properties(0).multi_processor_count)
+    side = kv.packed_layout(bits, N)["side"]
+    assert side == 8 and -(-T // Pb) == R and R > kv.SP_BATCH * side + side, (T, Pb, R, side)
+    B, G = first + T + 2, off.size - 1
+    g, rows, packed = rows_of(N, q, bits, B, 5 * N)
+    w = g.integers(0, q, B, dtype=np.uint16)
+    t_want = eng.tally_decrypt_batch(N, q, p, f, fp, rows, offsets=off, weights=w)
+    assert t_want[0].tobytes() == ref.np_sum_packed(q, N, packed, offsets=off, weights=w).tobytes()
+    dts = (np.uint16, np.uint8, np.uint16, np.uint16, np.uint8)
+    d = Dev(eng)
+    try:
+        outs = [d.put(np.zeros((G, N), dt)) for dt in dts]
+        pkg.tally_decrypt_packed_batch_dev(eng, N, q, p, d.put(f), d.put(fp), d.put(packed), outs[0], outs[1], G, d_offsets=d.put(off),
+                                           d_weights=d.put(w), d_quot1=outs[2], d_rem1=outs[3], d_quot2=outs[4])
+        for x, dt, a in zip(outs, dts, t_want):
+            assert eng.dev_download(x, (G, N), dt).tobytes() == a.tobytes()
+    finally:
+        d.free()
+
+
+def test_decrypt_takes_more_than_one_pass(eng):
+    """B = 65536 + 3: the rows are unpacked into scratch 65536 at a time, and the second pass reads and writes at offsets of its own.
+    Every row and every output row differs from the one 65536 before it, so a pass at the wrong offset cannot match; guard rows
+    behind every output stay as they were."""
+    N, q, p, B, FILL = 17, 32, 3, 65536 + 3, 0xA5
+    g, rows, packed = rows_of(N, q, 5, B, 65536)
+    f, fp = private_key(N, 7)
+    want = orc.decrypt_batch(N, q, p, f, fp, ref.unpack_rows(q, N, packed))
+    for a in (rows,) + tuple(want):
+        assert (a[65536:] != a[:3]).any(axis=1).all()
+    dts = (np.uint8, np.uint16, np.uint16, np.uint8)
+    d = Dev(eng)
+    try:
+        d_f, d_fp, d_packed = d.put(f), d.put(fp), d.put(packed)
+        for witness in (True, False):
+            outs = [d.put(np.full((B + 2, N), FILL, dt)) for dt in dts[:4 if witness else 1]]
+            pkg.decrypt_packed_batch_dev(eng, N, q, p, d_f, d_fp, d_packed, B, *outs)
+            for x, dt, a in zip(outs, dts, want):
+                got = eng.dev_download(x, (B + 2, N), dt)
+                assert got[:B].tobytes() == a.tobytes(), (witness, dt)
+                assert got[B:].tobytes() == np.full((2, N), FILL, dt).tobytes(), (witness, dt)
+    finally:
+        d.free()
+    for a, b in zip(want, pkg.decrypt_packed_batch(eng, N, q, p, f, fp, packed)):
+        assert a.tobytes() == b.tobytes()
 
 
 def test_the_loop_closes(eng):
