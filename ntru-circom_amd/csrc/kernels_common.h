@@ -27,6 +27,9 @@ static __device__ __forceinline__ u32 as_u32(u16x2 v) { return __builtin_bit_cas
 // x mod a small runtime modulus; p = 3 (every NTRU parameter set) gets the constant-divisor sequence.
 static __device__ __forceinline__ u32 mod_small(u32 x, u32 m) { return m == 3u ? x % 3u : x % m; }
 
+// The centred lift followed by mod p, index.js:117: x > q/2 ? (x + 1) % p : x % p, with `add` in place of its 1 (ntru_lift_addend).
+static __device__ __forceinline__ u32 lift_value(u32 x, u32 q, u32 p, u32 add) { return mod_small(2 * x > q ? x + add : x, p); }
+
 // Order this wave's LDS writes before its later LDS reads (regions touched here are private to one wave).
 static __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");

@@ -98,7 +98,7 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, u32
   build_toeplitz_array(TP, g, [&](int i) { return (int)fp[i]; }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
   if (GROUPS == 2)   // 64 f: the two low bits of every digit of f in bits 6-7 (f in {-1,0,1}: 0xC0, 0, 0x40)
     build_toeplitz_array(TF64, g, [&](int i) { return (int)(((u32)f[i] << 6) & 0xC0u); }, (int)threadIdx.x, GROUPS * BLOCK_THREADS);
-  for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)mod_small(2 * x > q ? x + lift_add : x, p);
+  for (u32 x = threadIdx.x; x < q; x += GROUPS * BLOCK_THREADS) lift_lut[x] = (unsigned char)lift_value(x, q, p, lift_add);
   if (GROUPS == 2) build_m3((int)threadIdx.x, GROUPS * BLOCK_THREADS, g.N);
   auto phase = [&]() { if (GROUPS == 2) __syncthreads(); };   // a boundary of the lock-step schedule
   if (GROUPS == 2 && group == 1) __syncthreads();                   // group 1 runs one phase behind group 0

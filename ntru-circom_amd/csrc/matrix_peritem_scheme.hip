@@ -168,7 +168,7 @@ __global__ void k_pi_add_bytes(u16 *__restrict__ e, const uint8_t *__restrict__ 
 __global__ void k_pi_lift(const u16 *__restrict__ rem, long n, u32 q, u32 p, u32 lift_add, u16 *__restrict__ out) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const u32 x = rem[i];
-    out[i] = (u16)(2 * x > q ? mod_small(x + lift_add, p) : mod_small(x, p));
+    out[i] = (u16)lift_value(x, q, p, lift_add);
   }
 }
 

@@ -20,6 +20,12 @@
 //     for the quotient) is T's value just before the lane's own block of i plus an in-block
 //     triangle; high = T - low; quotient = -high.  (tools/lane_model.py is the executable spec of this indexing.)
 //
+// Layout of the file: operand functors and staging; then what the families share, each stated once (window policies, triangle,
+// finish_pair, lift_pair, lane bookkeeping, the verifyKeysInputs flag helpers, the per-item-window LDS layout); the MAC family (1);
+// the ternary-stepping "add path" families (2: per-item stepping, 3: shared-key stepping, with the dot8 second product); the
+// launchers.  Two store forms stay: the MAC kernels' per-element predicates (store_pairs) and the add path's whole-block / tail
+// plan (StorePlan); the second in the MAC kernels costs a fifth more instructions and an occupancy step (EXPERIMENTS.md).
+//
 // No CPU fallback exists in this file: every entry point needs a HIP device.
 #include "kernels_common.h"
 
@@ -59,6 +65,15 @@ struct ValLds {            // an operand staged as u16 in LDS (per-item windows:
   __device__ __forceinline__ u32 operator()(int j) const { return p[j]; }
 };
 
+// Coefficients k, k + 1 of an operand row as a packed u16 pair, zero beyond N.  CLAMP: every lane loads, from a clamped index (no
+// branch, but an address of its own per element); otherwise only lanes inside the row load (one address per lane, immediate offsets).
+template <bool CLAMP = true, class F>
+static __device__ __forceinline__ u32 pair_at(F val, int k, int N) {
+  const int k0 = !CLAMP || k < N ? k : N - 1, k1 = !CLAMP || k + 1 < N ? k + 1 : N - 1;
+  const u32 v0 = k < N ? (val(k0) & 0xFFFFu) : 0u, v1 = k + 1 < N ? (val(k1) & 0xFFFFu) : 0u;
+  return v0 | (v1 << 16);
+}
+
 // Stage N coefficients of a per-item operand into LDS as u16 (lane `sub` of the item's `nl` lanes; coalesced).
 template <class F>
 static __device__ __forceinline__ void stage_raw(u16 *raw, int N, int nl, F val, int sub, bool active) {
@@ -89,6 +104,106 @@ static __device__ __forceinline__ void stage_a(u16 *a16, const Geom &g, F val, i
   for (int i = sub; i < n2; i += g.nl) a16[i] = i < g.N ? (u16)val(i) : (u16)0;
 }
 
+// ---- what the families share: window policies, triangle, finish, lift, stores, lane bookkeeping, key flags ----------------------
+static __device__ __forceinline__ u32 odd_pair(u32 e_u, u32 e_um1) { return __builtin_amdgcn_alignbit(e_u, e_um1, 16); }
+
+// The two window layouts and, for the add path (described further down), the two ways of holding step bits.  The MAC kernels
+// read PerItemWin's entries; per-item stepping (k_encrypt_t, k_decrypt_t, k_verify_keys_t) uses all of PerItemWin, shared-key
+// stepping (k_decrypt_s, described at build_cyclic_pairs below) all of SharedWin.  Everything in which they differ is stated here:
+//   1. window (Entry, even, odd, extra, stored_odd): LDS entries {E[u], O[u]} -- against entries E[u] alone with
+//      O[u] = odd_pair(E[u], E[u-1]), so that the refill of one block needs K + 1 next-window entries, not K.
+//   2. step bits (Code, bit2, put, hold, fetch): one code dword per block, step j tests its bits j and 16+j -- against two
+//      mask words per block (x: "into S1", y: "into S2") that each use bit j.  The block loop holds the current block's
+//      Code and looks one block ahead; each family keeps its own order of loads and readfirstlanes: the dword is made
+//      scalar when it becomes the held one -- against the held uint2 staying in VGPRs until its block begins.
+//   3. remainder (masks_rem): a power-of-two remainder is left to the caller, who adds to it first and then masks --
+//      against masked in the finish.  (Small moduli are reduced exactly in both.)
+struct PerItemWin {
+  using Entry = uint2;
+  using Code = u32;
+  static constexpr int extra = 0;                       // next-window entries a block pre-loads beyond K
+  static constexpr bool stored_odd = true;              // O[0] = (b[-1], b[0]) is stored: the linear product cuts b[-1]
+  static constexpr bool masks_rem = false;
+  static constexpr bool clamps_loads = true;            // of a block of the stepping operand (pair_at): loaded per item, in every lane
+  static constexpr int bit2(int J) { return 16 + J; }
+  static __device__ __forceinline__ u32 even(Entry v) { return v.x; }
+  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return v.y; }
+  static __device__ __forceinline__ void put(Code &c, u32 is1, u32 is2, int j) { c |= (is1 << j) | (is2 << (16 + j)); }
+  static __device__ __forceinline__ Code hold(Code c) { return __builtin_amdgcn_readfirstlane(c); }
+  // the held block's two step words, and the look-ahead load of block m + 1's Code (clamped at the last block)
+  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
+    w1 = held; w2 = held;
+    return codes[m + 1 < nblk ? m + 1 : m];
+  }
+};
+struct SharedWin {
+  using Entry = u32;
+  using Code = uint2;
+  static constexpr int extra = 1;
+  static constexpr bool stored_odd = false;             // derived from the entry before; none before index 0
+  static constexpr bool masks_rem = true;
+  static constexpr bool clamps_loads = false;           // loaded once per workgroup
+  static constexpr int bit2(int J) { return J; }
+  static __device__ __forceinline__ u32 even(Entry v) { return v; }
+  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return odd_pair(v, before); }
+  static __device__ __forceinline__ void put(Code &c, u32 is1, u32 is2, int j) { c.x |= is1 << j; c.y |= is2 << j; }
+  static __device__ __forceinline__ Code hold(Code c) { return c; }
+  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
+    w1 = __builtin_amdgcn_readfirstlane(held.x); w2 = __builtin_amdgcn_readfirstlane(held.y);
+    return codes[m + 1 < nblk ? m + 1 : m];
+  }
+};
+
+// In-block triangle of the LINEAR product: low[t] += the pairs of sum_{u<=j} a[k0+u] * b[j-u], j = 2t, 2t+1, for the lane's own
+// 2K outputs (k0 = 2K*sub).  win: the item's window array, av(s): the lane's s-th pair of a.  No coefficient exists before b[0].
+template <class Win, int K, class AV>
+static __device__ __forceinline__ void triangle(const typename Win::Entry *win, const Geom &g, AV av, u16x2 (&low)[K]) {
+  u32 ZE[K], ZO[K];
+  typename Win::Entry prev = {};
+#pragma unroll
+  for (int x = 0; x < K; x++) {
+    const typename Win::Entry v = win[g.off + x];
+    ZE[x] = Win::even(v); ZO[x] = Win::odd(v, prev); prev = v;
+  }
+  if constexpr (Win::stored_odd) ZO[0] &= 0xFFFF0000u;
+#pragma unroll
+  for (int s = 0; s < K; s++) {
+    const u16x2 ap = as_pair(av(s));
+#pragma unroll
+    for (int t = s; t < K; t++) {
+      low[t] = ap.xx * as_pair(ZE[t - s]) + low[t];
+      low[t] = ap.yy * as_pair(ZO[t - s]) + low[t];
+    }
+  }
+}
+
+// The finish of one output pair.  T: the cyclic product = remainder, low: the low half of the linear product, so high = T - low:
+//   rem = T mod `mod`      quot = (-high) mod `mod`  (0 if not wanted)
+// POW2: mod is a power of two (mask arithmetic on the wrapped u16 sums); otherwise sums are exact and `mod` small.
+// MASK_REM: whether a power-of-two remainder is masked here or left to a caller that adds to it first.
+template <bool POW2, bool MASK_REM>
+static __device__ __forceinline__ void finish_pair(u16x2 T, u16x2 low, bool want_quot, u32 mod, u16x2 &rem, u16x2 &quot) {
+  quot = (u16x2){0, 0};
+  if (want_quot) {
+    const u16x2 hi = T - low;
+    if (POW2) {
+      quot = ((u16x2){0, 0} - hi) & (u16)(mod - 1);
+    } else {
+      const u32 h0 = mod_small(hi.x, mod), h1 = mod_small(hi.y, mod);
+      quot = (u16x2){(u16)(h0 ? mod - h0 : 0), (u16)(h1 ? mod - h1 : 0)};
+    }
+  }
+  rem = POW2 ? (MASK_REM ? (T & (u16)(mod - 1)) : T) : (u16x2){(u16)mod_small(T.x, mod), (u16)mod_small(T.y, mod)};
+}
+
+// The centred lift of the finished pair at outputs k, k + 1 as a packed pair of the next product's operand; zero beyond N so that
+// the padding stays zero.
+static __device__ __forceinline__ u32 lift_pair(u16x2 rv, int k, int N, u32 q, u32 p, u32 add) {
+  const u32 b0 = lift_value(rv.x, q, p, add), b1 = lift_value(rv.y, q, p, add);    // unconditional: no branch around the division
+  return (k < N ? b0 : 0u) | ((k + 1 < N ? b1 : 0u) << 16);
+}
+
+// ---- MAC family (1) ---------------------------------------------------------------------------------------------------------------
 // The O(N^2) accumulate.  eo: this item's EO array, a32: its staged a-operand (packed pairs), sub: lane's index in item.
 template <int K>
 static __device__ __forceinline__ void mac_core(const uint2 *__restrict__ eo, const u32 *__restrict__ a32,
@@ -124,56 +239,19 @@ static __device__ __forceinline__ void mac_core(const uint2 *__restrict__ eo, co
   }
 }
 
-// In-block triangle: d[k0+j] = sum_{u<=j} a[k0+u] * b[j-u] for the lane's own 2K outputs (k0 = 2K*sub).
-template <int K>
-static __device__ __forceinline__ void diag_core(const uint2 *__restrict__ eo, const u32 *__restrict__ a32,
-                                                 const Geom &g, int sub, u16x2 (&d)[K]) {
-  u32 ZE[K], ZO[K];
-#pragma unroll
-  for (int x = 0; x < K; x++) { uint2 v = eo[g.off + x]; ZE[x] = v.x; ZO[x] = v.y; }
-  ZO[0] &= 0xFFFF0000u;                          // O[0] = (b[-1], b[0]): b[-1] does not exist in the linear product
-#pragma unroll
-  for (int t = 0; t < K; t++) d[t] = (u16x2){0, 0};
-#pragma unroll
-  for (int s = 0; s < K; s++) {
-    const u16x2 ap = as_pair(a32[K * sub + s]);
-#pragma unroll
-    for (int t = s; t < K; t++) {
-      d[t] = ap.xx * as_pair(ZE[t - s]) + d[t];
-      d[t] = ap.yy * as_pair(ZO[t - s]) + d[t];
-    }
-  }
-}
-
-// One product a*b with split by 1-x^N, results left in registers as K pairs per lane.
-//   rem  = (T + addend) mod `mod`      quot = (-high) mod `mod`
-// POW2: mod is a power of two (mask arithmetic on the wrapped u16 sums); otherwise sums are exact and `mod` small.
+// One product a*b with split by 1-x^N, results left in registers as K pairs per lane; the remainder of a power of two is left
+// unmasked for a caller that adds to it first (finish_pair).
 template <int K, bool POW2>
 static __device__ __forceinline__ void product_split(const uint2 *eo, const u32 *a32, const Geom &g, int sub,
                                                      bool want_quot, u32 mod, u16x2 (&rem)[K], u16x2 (&quot)[K]) {
   u16x2 T[K], low[K];
   mac_core<K>(eo, a32, g, sub, want_quot, T, low);
-  if (want_quot) {
-    u16x2 d[K];
-    diag_core<K>(eo, a32, g, sub, d);
+  if (want_quot) triangle<PerItemWin, K>(eo, g, [&](int s) { return a32[K * sub + s]; }, low);
 #pragma unroll
-    for (int t = 0; t < K; t++) {
-      u16x2 hi = T[t] - (low[t] + d[t]);
-      if (POW2) {
-        quot[t] = ((u16x2){0, 0} - hi) & (u16)(mod - 1);
-      } else {
-        u32 h0 = mod_small(hi.x, mod), h1 = mod_small(hi.y, mod);
-        quot[t] = (u16x2){(u16)(h0 ? mod - h0 : 0), (u16)(h1 ? mod - h1 : 0)};
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < K; t++) {
-    if (POW2) rem[t] = T[t];                       // masked by the caller after the optional addend
-    else rem[t] = (u16x2){(u16)mod_small(T[t].x, mod), (u16)mod_small(T[t].y, mod)};
-  }
+  for (int t = 0; t < K; t++) finish_pair<POW2, false>(T[t], low[t], want_quot, mod, rem[t], quot[t]);
 }
 
+// Store the lane's K output pairs into its item's row, element by element inside the row.
 template <int K, class OutT>
 static __device__ __forceinline__ void store_pairs(OutT *row, const Geom &g, int sub, const u16x2 (&v)[K]) {
 #pragma unroll
@@ -195,6 +273,64 @@ static __device__ __forceinline__ LaneId lane_id(const Geom &g) {
   L.grp = L.active ? L.lane / g.nl : 0;
   L.sub = L.active ? L.lane - L.grp * g.nl : 0;
   return L;
+}
+
+// This lane's item's part of a wave-wide ballot of `pred` (items occupy nl consecutive lanes of the wave).
+static __device__ __forceinline__ unsigned long long item_ballot(bool pred, const Geom &g, const LaneId &L) {
+  const unsigned long long msk = (g.nl >= 64 ? ~0ull : ((1ull << g.nl) - 1)) << (L.grp * g.nl);
+  return __ballot(pred && L.active) & msk;
+}
+// Does any active lane of this lane's item have `pred` set?
+static __device__ __forceinline__ bool item_any(bool pred, const Geom &g, const LaneId &L) { return item_ballot(pred, g, L) != 0; }
+
+// verifyKeysInputs' inverse check (index.js:159,162) on a remainder that arrives pair by pair: invalid iff
+// "length != 1 && [0] != 1".
+template <int K>
+struct InverseCheck {
+  bool nz_hi = false, first_not_one = false;          // some coefficient beyond index 0 is non-zero; coefficient 0 is not 1
+  __device__ __forceinline__ void note(int sub, int t, int N, u16x2 rv) {
+    const int k = 2 * K * sub + 2 * t;
+    nz_hi |= (k >= 1 && k < N && rv.x != 0) || (k + 1 < N && rv.y != 0);
+    if (t == 0) first_not_one = sub == 0 && rv.x != 1;
+  }
+  __device__ __forceinline__ bool invalid(const Geom &g, const LaneId &L) const {
+    return item_any(nz_hi, g, L) && item_any(first_not_one, g, L);
+  }
+};
+// 'invalid h' iff some index below h's TRIMMED length differs from the remainder (index.js:165).  hp: h's pair at outputs k, k + 1
+// (pair_at: zero beyond N).  Each lane notes its highest non-zero index (-1: none); over the item's lanes the highest lane that
+// holds one wins, and the zero polynomial has length 1.
+static __device__ __forceinline__ void note_top(int &top, int k, u32 hp) {
+  if (hp & 0xFFFFu) top = k;
+  if (hp >> 16) top = k + 1;
+}
+static __device__ __forceinline__ int item_trimmed_len(int top, const Geom &g, const LaneId &L) {
+  const unsigned long long bal = item_ballot(top >= 0, g, L);
+  const int src = bal ? 63 - __builtin_clzll(bal) : (int)L.lane;
+  const int top_src = __shfl(top, src);
+  return bal ? top_src + 1 : 1;
+}
+static __device__ __forceinline__ bool differs_below(int hl, int k, u32 hp, u16x2 rv) {
+  return (k < hl && (hp & 0xFFFFu) != rv.x) || (k + 1 < hl && (hp >> 16) != rv.y);
+}
+
+// The per-wave LDS region of the kernels whose window belongs to the item (k_polymul_split, k_verify_keys): G EO arrays, G staged
+// a-operands, G raw u16 rows.  Byte offsets inside the region and its size; the launcher sizes what the kernels carve up.
+struct PerItemLds { size_t a32, raw, raw_len, per_wave; };     // the EO arrays sit at offset 0; raw_len in u16 slots
+static __host__ __device__ __forceinline__ PerItemLds per_item_lds(const Geom &g) {
+  PerItemLds l;
+  l.raw_len = ((size_t)g.N + 1) & ~(size_t)1;                  // dword aligned
+  l.a32 = (size_t)g.G * g.eo_len * 8;
+  l.raw = l.a32 + (size_t)g.G * g.a_len * 4;
+  l.per_wave = l.raw + (size_t)g.G * l.raw_len * 2;
+  return l;
+}
+struct PerItemBufs { uint2 *eo; u32 *a32; u16 *raw; };         // this lane's item's three arrays
+static __device__ __forceinline__ PerItemBufs per_item_bufs(unsigned char *lds, const Geom &g, const LaneId &L) {
+  const PerItemLds l = per_item_lds(g);
+  unsigned char *wbase = lds + (size_t)L.wave * l.per_wave;
+  return {(uint2 *)wbase + (size_t)L.grp * g.eo_len, (u32 *)(wbase + l.a32) + (size_t)L.grp * g.a_len,
+          (u16 *)(wbase + l.raw) + (size_t)L.grp * l.raw_len};
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------
@@ -269,17 +405,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt(Geom g, u32 q, u32 p,
       if (rem1) store_pairs<K>(rem1 + row, g, L.sub, r1);
       if (want_q1) store_pairs<K>(quot1 + row, g, L.sub, q1);
     }
-    // centred lift, index.js:117: x > q/2 ? (x+1)%p : x%p, with lift_add in place of its 1 ; zero beyond N so the padding stays zero
     wave_lds_fence();
-    if (L.active) {
+    if (L.active) {                                   // the lifted message is the second product's broadcast operand
 #pragma unroll
-      for (int t = 0; t < K; t++) {
-        int k = 2 * K * L.sub + 2 * t;
-        u32 x0 = r1[t].x, x1 = r1[t].y;
-        u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
-        b0 = k < g.N ? b0 : 0; b1 = k + 1 < g.N ? b1 : 0;
-        a32[K * L.sub + t] = b0 | (b1 << 16);
-      }
+      for (int t = 0; t < K; t++) a32[K * L.sub + t] = lift_pair(r1[t], 2 * K * L.sub + 2 * t, g.N, q, p, lift_add);
     }
     wave_lds_fence();
     u16x2 r2[K], q2[K];
@@ -302,12 +431,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_polymul_split(Geom g, u32 mod
                                                                  u32 scale = 1) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const LaneId L = lane_id(g);
-  const size_t raw_len = ((size_t)g.N + 1) & ~(size_t)1;                 // u16 slots per staged operand (dword aligned)
-  const size_t per_wave = (size_t)g.G * ((size_t)g.eo_len * 8 + (size_t)g.a_len * 4 + raw_len * 2);
-  unsigned char *wbase = lds + (size_t)L.wave * per_wave;
-  uint2 *eo = (uint2 *)wbase + (size_t)L.grp * g.eo_len;
-  u32 *a32 = (u32 *)(wbase + (size_t)g.G * g.eo_len * 8) + (size_t)L.grp * g.a_len;
-  u16 *raw = (u16 *)(wbase + (size_t)g.G * ((size_t)g.eo_len * 8 + (size_t)g.a_len * 4)) + (size_t)L.grp * raw_len;
+  const auto [eo, a32, raw] = per_item_bufs(lds, g, L);
   const long ngroups = (B + g.G - 1) / g.G;
   for (long grp = (long)blockIdx.x * WAVES_PER_BLOCK + L.wave; grp < ngroups; grp += (long)gridDim.x * WAVES_PER_BLOCK) {
     const long item = grp * g.G + L.grp;
@@ -339,7 +463,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_polymul_split(Geom g, u32 mod
   }
 }
 
-
 // ================================================================================================================
 // Ternary-stepping kernels ("add path").
 //
@@ -352,21 +475,35 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_polymul_split(Geom g, u32 mod
 // top of a masked value before it could carry into its neighbour, so the accumulators are masked (mod q is free:
 // q | 2^16) every ME steps, ME <= limit chosen by the launcher; products with exact small sums never mask (ME = 0).
 //
-// Two families use this machinery, written once below (TernOps, add_steps, add_core, add_product_split) over the
-// policy types PerItemWin / SharedWin, which state what differs between them:
+// Two families use this machinery, written once below (step_code, load_block, TernOps, add_steps, add_core,
+// add_product_split) over the policy types PerItemWin / SharedWin above, which state what differs between them; triangle,
+// finish_pair, lift_pair and the stores are the ones the MAC kernels use:
 //   per-item stepping (k_encrypt_t, k_decrypt_t, k_verify_keys_t): the stepping operand belongs to the item; one item
 //     per wave (nl > 32), K <= 7 (2K step bits in half a dword) and (K+1)*(q-1) <= 65535;
 //   shared-key stepping (k_decrypt_s): every wave steps over the same key; two items per wave, K = 9 / 11 / 13.
 // Otherwise the MAC kernels above are used.
 // ================================================================================================================
 
-// bit j: step j adds into S1 (value 1); bit 16+j: step j adds into S2 (the other non-zero symbol).  Written with
-// 0/1 flags and immediate shifts so that no per-bit constant has to live in a VGPR (a select between two literal
-// masks would: 2 x 2K constants hoisted for the whole kernel).
-static __device__ __forceinline__ u32 step_bits(u32 v, int j) {
+// Enter step j of a block, with coefficient v, into the block's code: "adds into S1" (v = 1) or "adds into S2" (the other non-zero
+// symbol), at the bits Win::put states.  Written with 0/1 flags and immediate shifts so that no per-bit constant has to live in a
+// VGPR (a select between two literal masks would: 2 x 2K constants hoisted for the whole kernel).
+template <class Win>
+static __device__ __forceinline__ void step_code(typename Win::Code &code, u32 v, int j) {
   u32 is1 = v == 1u ? 1u : 0u, is2 = v > 1u ? 1u : 0u;
   asm volatile("" : "+v"(is1), "+v"(is2));              // opaque: keeps the optimiser from folding this back into selects
-  return (is1 << j) | (is2 << (16 + j));
+  Win::put(code, is1, is2, j);
+}
+
+// The lane's block of a stepping operand: numeric u16 pairs for the triangle + the block's code.
+template <class Win, int K, class F>
+static __device__ __forceinline__ typename Win::Code load_block(F val, int N, int sub, u32 (&av)[K]) {
+  typename Win::Code code = {};
+#pragma unroll
+  for (int t = 0; t < K; t++) {
+    av[t] = pair_at<Win::clamps_loads>(val, 2 * K * sub + 2 * t, N);
+    step_code<Win>(code, av[t] & 0xFFFFu, 2 * t); step_code<Win>(code, av[t] >> 16, 2 * t + 1);
+  }
+  return code;
 }
 
 // Lane-conditional snapshot L1 <- S1, L2 <- S2 as an exec-masked block of in-place full-rate v_mov (hipcc would turn
@@ -427,52 +564,6 @@ TERN_OPS(9)
 TERN_OPS(11)
 TERN_OPS(13)
 #undef TERN_OPS
-
-static __device__ __forceinline__ u32 odd_pair(u32 e_u, u32 e_um1) { return __builtin_amdgcn_alignbit(e_u, e_um1, 16); }
-
-// ---- the two add-path families ------------------------------------------------------------------------------------
-// Per-item stepping (k_encrypt_t, k_decrypt_t, k_verify_keys_t) and shared-key stepping (k_decrypt_s, described at
-// build_cyclic_pairs below) run the same steps, block loop and finish.  Everything in which they differ is stated by
-// these two policy types:
-//   1. step bits (Code, bit2, hold, fetch): one code dword per block, step j tests its bits j and 16+j -- against two
-//      mask words per block (x: "into S1", y: "into S2") that each use bit j.  The block loop holds the current block's
-//      Code and looks one block ahead; each family keeps its own order of loads and readfirstlanes: the dword is made
-//      scalar when it becomes the held one -- against the held uint2 staying in VGPRs until its block begins.
-//   2. window (Entry, even, odd, extra, stored_odd): LDS entries {E[u], O[u]} -- against entries E[u] alone with
-//      O[u] = odd_pair(E[u], E[u-1]), so that the refill of one block needs K + 1 next-window entries, not K.
-//   3. remainder (masks_rem): a power-of-two remainder is left to the caller, who adds to it first and then masks --
-//      against masked in the finish.  (Small moduli are reduced exactly in both.)
-struct PerItemWin {
-  using Entry = uint2;
-  using Code = u32;
-  static constexpr int extra = 0;                       // next-window entries a block pre-loads beyond K
-  static constexpr bool stored_odd = true;              // O[0] = (b[-1], b[0]) is stored: the linear product cuts b[-1]
-  static constexpr bool masks_rem = false;
-  static constexpr int bit2(int J) { return 16 + J; }
-  static __device__ __forceinline__ u32 even(Entry v) { return v.x; }
-  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return v.y; }
-  static __device__ __forceinline__ Code hold(Code c) { return __builtin_amdgcn_readfirstlane(c); }
-  // the held block's two step words, and the look-ahead load of block m + 1's Code (clamped at the last block)
-  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
-    w1 = held; w2 = held;
-    return codes[m + 1 < nblk ? m + 1 : m];
-  }
-};
-struct SharedWin {
-  using Entry = u32;
-  using Code = uint2;
-  static constexpr int extra = 1;
-  static constexpr bool stored_odd = false;             // derived from the entry before; none before index 0
-  static constexpr bool masks_rem = true;
-  static constexpr int bit2(int J) { return J; }
-  static __device__ __forceinline__ u32 even(Entry v) { return v; }
-  static __device__ __forceinline__ u32 odd(Entry v, Entry before) { return odd_pair(v, before); }
-  static __device__ __forceinline__ Code hold(Code c) { return c; }
-  static __device__ __forceinline__ Code fetch(const Code *codes, int m, int nblk, Code held, u32 &w1, u32 &w2) {
-    w1 = __builtin_amdgcn_readfirstlane(held.x); w2 = __builtin_amdgcn_readfirstlane(held.y);
-    return codes[m + 1 < nblk ? m + 1 : m];
-  }
-};
 
 // Steps J .. 2K-1 of one block (compile-time recursion so every bit index / register index is an immediate).
 // Step j adds into S1 if bit j of w1 is set, else into S2 if bit Win::bit2(j) of w2 is.  ME: mask both sets every ME
@@ -560,7 +651,7 @@ static __device__ __forceinline__ void store_pair(OutT *lane_row, const StorePla
 }
 
 // Runs one stepped product and hands each finished pair to `emit(t, rem_pair, quot_pair)` right away (so no result
-// arrays stay live: register pressure is what limits k_decrypt_s's occupancy).  Remainder / quotient as product_split.
+// arrays stay live: register pressure is what limits k_decrypt_s's occupancy).  Remainder / quotient as finish_pair states.
 // av(s): the lane's s-th pair of the stepping operand (numeric), only evaluated for the triangle after the main loop.
 // The per-item kernels call this with PerItemWin themselves: a forwarding tern_product_split in between changes the
 // register allocation of k_decrypt_t and k_verify_keys_t.  k_decrypt_s goes through shared_product_split below.
@@ -578,58 +669,13 @@ static __device__ __forceinline__ void add_product_split(const typename Win::Ent
   u16x2 low[K];
 #pragma unroll
   for (int t = 0; t < K; t++) low[t] = tern_combine<NEG>(L1[t], L2[t], fmask, qq);
-  if (want_quot) {
-    u32 ZE[K], ZO[K];
-    typename Win::Entry prev = {};                   // the linear product has no coefficient before index 0
-#pragma unroll
-    for (int x = 0; x < K; x++) {
-      const typename Win::Entry v = win[g.off + x];
-      ZE[x] = Win::even(v); ZO[x] = Win::odd(v, prev); prev = v;
-    }
-    if constexpr (Win::stored_odd) ZO[0] &= 0xFFFF0000u;
-#pragma unroll
-    for (int s = 0; s < K; s++) {
-      const u16x2 ap = as_pair(av(s));
-#pragma unroll
-      for (int t = s; t < K; t++) {
-        low[t] = ap.xx * as_pair(ZE[t - s]) + low[t];
-        low[t] = ap.yy * as_pair(ZO[t - s]) + low[t];
-      }
-    }
-  }
+  if (want_quot) triangle<Win, K>(win, g, av, low);
 #pragma unroll
   for (int t = 0; t < K; t++) {
-    const u16x2 T = tern_combine<NEG>(S1[t], S2[t], fmask, qq);
-    u16x2 qv = (u16x2){0, 0};
-    if (want_quot) {
-      const u16x2 hi = T - low[t];
-      if (POW2) {
-        qv = ((u16x2){0, 0} - hi) & (u16)(mod - 1);
-      } else {
-        const u32 h0 = mod_small(hi.x, mod), h1 = mod_small(hi.y, mod);
-        qv = (u16x2){(u16)(h0 ? mod - h0 : 0), (u16)(h1 ? mod - h1 : 0)};
-      }
-    }
-    const u16x2 rv = POW2 ? (Win::masks_rem ? (T & (u16)(mod - 1)) : T)
-                          : (u16x2){(u16)mod_small(T.x, mod), (u16)mod_small(T.y, mod)};
+    u16x2 rv, qv;
+    finish_pair<POW2, Win::masks_rem>(tern_combine<NEG>(S1[t], S2[t], fmask, qq), low[t], want_quot, mod, rv, qv);
     emit(t, rv, qv);
   }
-}
-
-
-// Load the lane's block of the stepping operand: numeric u16 pairs for the triangle + the block's code word.
-template <int K, class F>
-static __device__ __forceinline__ u32 load_block(F val, int N, int sub, u32 (&av)[K]) {
-  u32 word = 0;
-#pragma unroll
-  for (int t = 0; t < K; t++) {
-    const int k = 2 * K * sub + 2 * t;
-    const int k0 = k < N ? k : N - 1, k1 = k + 1 < N ? k + 1 : N - 1;          // clamped, then zeroed
-    const u32 v0 = k < N ? (val(k0) & 0xFFFFu) : 0u, v1 = k + 1 < N ? (val(k1) & 0xFFFFu) : 0u;
-    av[t] = v0 | (v1 << 16);
-    word |= step_bits(v0, 2 * t) | step_bits(v1, 2 * t + 1);
-  }
-  return word;
 }
 
 // encryptBits on the add path: stepping operand r in {0,1,2}, window h (shared).
@@ -651,7 +697,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 7) void k_encrypt_t(Geom g, u32 q, c
     const long row = item * N;
     {
       u32 av[K];
-      const u32 word = load_block<K>(ValU8{r + row}, N, sub, av);
+      const u32 word = load_block<PerItemWin, K>(ValU8{r + row}, N, sub, av);
       if (L.active) codes[sub] = word;
     }
     wave_lds_fence();
@@ -660,11 +706,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, 7) void k_encrypt_t(Geom g, u32 q, c
     auto r_pair = [&](int t) -> u32 {                                     // reloaded behind the hot loop (L1/L2 hit)
       int sub2 = sub;
       asm volatile("" : "+v"(sub2));
-      const uint8_t *rr = r + row;
-      const int k = 2 * K * sub2 + 2 * t;
-      const int k0 = k < N ? k : N - 1, k1 = k + 1 < N ? k + 1 : N - 1;
-      const u32 v0 = k < N ? rr[k0] : 0u, v1 = k + 1 < N ? rr[k1] : 0u;
-      return v0 | (v1 << 16);
+      return pair_at(ValU8{r + row}, 2 * K * sub2 + 2 * t, N);
     };
     add_product_split<PerItemWin, K, ME, false>(eo_h, codes, r_pair, g, sub, want_quot, q, [&](int t, u16x2 rv, u16x2 qv) {
       int sub2 = sub;
@@ -702,7 +744,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
   build_eo(eo_fp, g, ValU8{fp}, threadIdx.x, BLOCK_THREADS);
   u32 av_f[K];                                           // this lane's block of f, the same for every item
   {
-    const u32 wf = load_block<K>(ValTernary{f, q - 1}, g.N, L.sub, av_f);
+    const u32 wf = load_block<PerItemWin, K>(ValTernary{f, q - 1}, g.N, L.sub, av_f);
     if (L.wave == 0 && L.active) codes_f[L.sub] = wf;
   }
   __syncthreads();
@@ -714,17 +756,13 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
     const StorePlan sp = store_plan<K>(g, L.sub, L.active);
     const long lane0 = row + 2 * K * L.sub;
     u32 av_b[K], wb = 0;
-    // remainder1 / quotient1 stored pair by pair; centred lift, index.js:117 verbatim -> second stepping operand
+    // remainder1 / quotient1 stored pair by pair; the lifted pair is the second stepping operand
     add_product_split<PerItemWin, K, ME, true>(eo_e, codes_f, [&](int t) { return av_f[t]; }, g, L.sub, want_q1, q, [&](int t, u16x2 rv, u16x2 qv) {
       rv = rv & (u16)(q - 1);
       if (rem1) store_pair(rem1 + lane0, sp, t, rv);
       if (want_q1) store_pair(quot1 + lane0, sp, t, qv);
-      const int k = 2 * K * L.sub + 2 * t;
-      const u32 x0 = rv.x, x1 = rv.y;
-      u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
-      b0 = k < g.N ? b0 : 0; b1 = k + 1 < g.N ? b1 : 0;
-      av_b[t] = b0 | (b1 << 16);
-      wb |= step_bits(b0, 2 * t) | step_bits(b1, 2 * t + 1);
+      av_b[t] = lift_pair(rv, 2 * K * L.sub + 2 * t, g.N, q, p, lift_add);
+      step_code<PerItemWin>(wb, av_b[t] & 0xFFFFu, 2 * t); step_code<PerItemWin>(wb, av_b[t] >> 16, 2 * t + 1);
     });
     if (L.active) codes_b[L.sub] = wb;
     wave_lds_fence();
@@ -735,7 +773,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_decrypt_t(Geom g, u32 q, u32 
     wave_lds_fence();
   }
 }
-
 
 // ================================================================================================================
 // Shared-stepping add path (decrypt).  Both products of decryptBits can step over a SHARED key operand (f, then fp),
@@ -785,7 +822,6 @@ static __device__ __forceinline__ void shared_product_split(const u32 *E, const 
                                                             const Geom &g, int sub, bool want_quot, u32 mod, Emit emit) {
   add_product_split<SharedWin, K, ME, NEG>(E, masks, [&](int s) { return av[s]; }, g, sub, want_quot, mod, emit);
 }
-
 
 // ---- ternary x ternary product on v_dot8_u32_u4 (decrypt's c = fp * b mod 3) ---------------------------------------
 // Both operands are in {0,1,2}: 8 multiply-accumulates per instruction, no branches, exact sums (<= 4N).  Layout for
@@ -899,23 +935,6 @@ static __device__ __forceinline__ void dot8_product_mod3(const u32 *dwp, const u
   }
 }
 
-// The lane's block of a shared stepping operand: numeric pairs + the block's two step masks.
-template <int K, class F>
-static __device__ __forceinline__ uint2 load_block_masks(F val, const Geom &g, int sub, u32 (&av)[K]) {
-  uint2 mk = make_uint2(0u, 0u);
-#pragma unroll
-  for (int t = 0; t < K; t++) {
-    const int k = 2 * K * sub + 2 * t;
-    const u32 v0 = k < g.N ? (val(k) & 0xFFFFu) : 0u, v1 = k + 1 < g.N ? (val(k + 1) & 0xFFFFu) : 0u;
-    av[t] = v0 | (v1 << 16);
-    u32 a1 = v0 == 1u ? 1u : 0u, a2 = v0 > 1u ? 1u : 0u, b1 = v1 == 1u ? 1u : 0u, b2 = v1 > 1u ? 1u : 0u;
-    asm volatile("" : "+v"(a1), "+v"(a2), "+v"(b1), "+v"(b2));   // see step_bits
-    mk.x |= (a1 << (2 * t)) | (b1 << (2 * t + 1));
-    mk.y |= (a2 << (2 * t)) | (b2 << (2 * t + 1));
-  }
-  return mk;
-}
-
 // decryptBits with both products stepping over the shared key (f, then fp); two items per wave.  p must be 3.
 template <int K, int ME, bool D8>
 __global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u32 lift_add, const int8_t *__restrict__ f,
@@ -936,10 +955,10 @@ __global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u
   const int e_off0 = nblk + (L.wave * g.G + L.grp) * e_alloc + 1;
   if (L.wave == 0 && L.active && L.grp == 0) {                          // key-dependent tables, once per workgroup
     u32 av[K];
-    masks_f[L.sub] = load_block_masks<K>(ValTernary{f, q - 1}, g, L.sub, av);
+    masks_f[L.sub] = load_block<SharedWin, K>(ValTernary{f, q - 1}, g.N, L.sub, av);
 #pragma unroll
     for (int t = 0; t < K; t++) blk_f[K * L.sub + t] = av[t];
-    masks_fp[L.sub] = load_block_masks<K>(ValU8{fp}, g, L.sub, av);
+    masks_fp[L.sub] = load_block<SharedWin, K>(ValU8{fp}, g.N, L.sub, av);
 #pragma unroll
     for (int t = 0; t < K; t++) blk_fp[K * L.sub + t] = av[t];
   }
@@ -978,18 +997,14 @@ __global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u
       }
     }
     build_cyclic_pairs<K>(E, g, sub, L.active, P, false, 0u);
-    // remainder1 / quotient1 are stored and the centred lift (index.js:117 verbatim) is applied pair by pair; the lifted
+    // remainder1 / quotient1 are stored and the centred lift is applied pair by pair; the lifted
     // message replaces P: it is the window of product 2
     const StorePlan sp = store_plan<K>(g, sub, valid);
     const long lane0 = row + 2 * K * sub;                              // this lane's first output
     shared_product_split<K, ME, true>(E, masks_f, av_f, g, sub, want_q1, q, [&](int t, u16x2 rv, u16x2 qv) {
       if (rem1) store_pair(rem1 + lane0, sp, t, rv);
       if (want_q1) store_pair(quot1 + lane0, sp, t, qv);
-      const int k = 2 * (K * sub + t);
-      const u32 x0 = rv.x, x1 = rv.y;
-      u32 b0 = mod_small(2 * x0 > q ? x0 + lift_add : x0, p), b1 = mod_small(2 * x1 > q ? x1 + lift_add : x1, p);
-      b0 = k < N ? b0 : 0; b1 = k + 1 < N ? b1 : 0;
-      P[t] = b0 | (b1 << 16);
+      P[t] = lift_pair(rv, 2 * (K * sub + t), N, q, p, lift_add);
     });
     wave_lds_fence();                                                   // everyone is done reading E(e)
     if constexpr (D8) {
@@ -1015,13 +1030,6 @@ __global__ __launch_bounds__(BLOCK_THREADS, 4) void k_decrypt_s(Geom g, u32 q, u
   }
 }
 
-// Does any active lane of this lane's item have `pred` set?  (items occupy nl consecutive lanes of the wave)
-static __device__ __forceinline__ bool item_any(bool pred, const Geom &g, const LaneId &L) {
-  unsigned long long bal = __ballot(pred && L.active);
-  unsigned long long msk = (g.nl >= 64 ? ~0ull : ((1ull << g.nl) - 1)) << (L.grp * g.nl);
-  return (bal & msk) != 0;
-}
-
 // verifyKeysInputs, index.js:141-197, per-item key material; three products per item.
 template <int K>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys(
@@ -1031,12 +1039,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys(
     u16 *__restrict__ rem_h, uint8_t *__restrict__ flags) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const LaneId L = lane_id(g);
-  const size_t raw_len = ((size_t)g.N + 1) & ~(size_t)1;
-  const size_t per_wave = (size_t)g.G * ((size_t)g.eo_len * 8 + (size_t)g.a_len * 4 + raw_len * 2);
-  unsigned char *wbase = lds + (size_t)L.wave * per_wave;
-  uint2 *eo = (uint2 *)wbase + (size_t)L.grp * g.eo_len;
-  u32 *a32 = (u32 *)(wbase + (size_t)g.G * g.eo_len * 8) + (size_t)L.grp * g.a_len;
-  u16 *raw = (u16 *)(wbase + (size_t)g.G * ((size_t)g.eo_len * 8 + (size_t)g.a_len * 4)) + (size_t)L.grp * raw_len;
+  const auto [eo, a32, raw] = per_item_bufs(lds, g, L);
   const long ngroups = (B + g.G - 1) / g.G;
   for (long grp = (long)blockIdx.x * WAVES_PER_BLOCK + L.wave; grp < ngroups; grp += (long)gridDim.x * WAVES_PER_BLOCK) {
     const long item = grp * g.G + L.grp;
@@ -1052,15 +1055,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys(
     wave_lds_fence();
     product_split<K, true>(eo, a32, g, L.sub, true, q, r, qv);
     {
-      bool nz_hi = false;                             // any remainder coefficient beyond index 0 non-zero?
+      InverseCheck<K> inv;
 #pragma unroll
-      for (int t = 0; t < K; t++) {
-        r[t] = r[t] & (u16)(q - 1);
-        int k = 2 * K * L.sub + 2 * t;
-        nz_hi |= (k >= 1 && k < g.N && r[t].x != 0) || (k + 1 < g.N && r[t].y != 0);
-      }
-      bool first_not_one = item_any(L.sub == 0 && r[0].x != 1, g, L);
-      if (item_any(nz_hi, g, L) && first_not_one) fl |= NTRU_FLAG_INVALID_FQ;   // length !== 1 && [0] !== 1
+      for (int t = 0; t < K; t++) { r[t] = r[t] & (u16)(q - 1); inv.note(L.sub, t, g.N, r[t]); }
+      if (inv.invalid(g, L)) fl |= NTRU_FLAG_INVALID_FQ;
     }
     if (valid) { store_pairs<K>(rem_fq + row, g, L.sub, r); store_pairs<K>(quot_fq + row, g, L.sub, qv); }
     wave_lds_fence();
@@ -1077,14 +1075,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys(
     wave_lds_fence();
     product_split<K, false>(eo, a32, g, L.sub, true, p, r, qv);
     {
-      bool nz_hi = false;
+      InverseCheck<K> inv;
 #pragma unroll
-      for (int t = 0; t < K; t++) {
-        int k = 2 * K * L.sub + 2 * t;
-        nz_hi |= (k >= 1 && k < g.N && r[t].x != 0) || (k + 1 < g.N && r[t].y != 0);
-      }
-      bool first_not_one = item_any(L.sub == 0 && r[0].x != 1, g, L);
-      if (item_any(nz_hi, g, L) && first_not_one) fl |= NTRU_FLAG_INVALID_FP;
+      for (int t = 0; t < K; t++) inv.note(L.sub, t, g.N, r[t]);
+      if (inv.invalid(g, L)) fl |= NTRU_FLAG_INVALID_FP;
     }
     if (valid) { store_pairs<K>(rem_fp + row, g, L.sub, r); store_pairs<K>(quot_fp + row, g, L.sub, qv); }
     wave_lds_fence();
@@ -1096,29 +1090,17 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys(
     wave_lds_fence();
     product_split<K, true>(eo, a32, g, L.sub, true, q, r, qv);
     {
-      // 'invalid h' iff some index below h's trimmed length differs from the remainder (index.js:165)
-      int top = -1; bool differs_any[2 * K];
+      u32 hp[K]; int top = -1;
 #pragma unroll
       for (int t = 0; t < K; t++) {
         r[t] = r[t] & (u16)(q - 1);
-        int k = 2 * K * L.sub + 2 * t;
-        u32 h0 = k < g.N ? h[row + k] : 0, h1 = k + 1 < g.N ? h[row + k + 1] : 0;
-        if (h0) top = k;
-        if (h1) top = k + 1;
-        differs_any[2 * t] = k < g.N && h0 != r[t].x;
-        differs_any[2 * t + 1] = k + 1 < g.N && h1 != r[t].y;
+        hp[t] = pair_at<false>(ValU16{h + row}, 2 * K * L.sub + 2 * t, g.N);
+        note_top(top, 2 * K * L.sub + 2 * t, hp[t]);
       }
-      // degree of h over the item's lanes: highest lane holding a non-zero coefficient wins
-      unsigned long long bal = __ballot(top >= 0 && L.active);
-      unsigned long long msk = (g.nl >= 64 ? ~0ull : ((1ull << g.nl) - 1)) << (L.grp * g.nl);
-      bal &= msk;
-      int hl = 1;                                       // trimmed length of the zero polynomial is 1
-      int src = bal ? 63 - __builtin_clzll(bal) : (int)L.lane;
-      int top_src = __shfl(top, src);
-      if (bal) hl = top_src + 1;
+      const int hl = item_trimmed_len(top, g, L);
       bool bad = false;
 #pragma unroll
-      for (int j = 0; j < 2 * K; j++) bad |= differs_any[j] && (2 * K * L.sub + j) < hl;
+      for (int t = 0; t < K; t++) bad |= differs_below(hl, 2 * K * L.sub + 2 * t, hp[t], r[t]);
       if (item_any(bad, g, L)) fl |= NTRU_FLAG_INVALID_H;
     }
     if (valid) {
@@ -1156,7 +1138,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
       stage_raw(raw, N, g.nl, win, sub, L.active);
       {
         u32 av[K];
-        const u32 word = load_block<K>(ValTernary{step + row, neg}, N, sub, av);
+        const u32 word = load_block<PerItemWin, K>(ValTernary{step + row, neg}, N, sub, av);
         if (L.active) codes[sub] = word;
       }
       wave_lds_fence();
@@ -1165,23 +1147,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
       auto s_pair = [&](int t) -> u32 {                                   // reloaded behind the hot loop
         int sub2 = sub;
         asm volatile("" : "+v"(sub2));
-        const int8_t *sr = step + row;
-        const int k = 2 * K * sub2 + 2 * t;
-        const int k0 = k < N ? k : N - 1, k1 = k + 1 < N ? k + 1 : N - 1;
-        const int a0 = sr[k0], a1 = sr[k1];
-        const u32 v0 = k < N ? (a0 < 0 ? neg : (u32)a0) : 0u, v1 = k + 1 < N ? (a1 < 0 ? neg : (u32)a1) : 0u;
-        return v0 | (v1 << 16);
+        return pair_at(ValTernary{step + row, neg}, 2 * K * sub2 + 2 * t, N);
       };
       split(s_pair, emit);
       wave_lds_fence();
     };
-    // per-product bookkeeping shared by the two inverse checks (index.js:159,162): "length != 1 && [0] != 1"
-    bool nz_hi = false, first_not_one = false;
-    auto note_inverse = [&](int sub2, int t, u16x2 rv) {
-      const int k = 2 * K * sub2 + 2 * t;
-      nz_hi |= (k >= 1 && k < N && rv.x != 0) || (k + 1 < N && rv.y != 0);
-      if (t == 0) first_not_one = sub2 == 0 && rv.x != 1;
-    };
+    InverseCheck<K> inv;
     // ---- fq * f mod q
     product(ValU16{fq + row}, f, q - 1,
             [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
@@ -1192,11 +1163,11 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
               const long lane0 = row + 2 * K * sub2;
               store_pair(rem_fq + lane0, sp, t, rv);
               store_pair(quot_fq + lane0, sp, t, qv);
-              note_inverse(sub2, t, rv);
+              inv.note(sub2, t, N, rv);
             });
-    if (item_any(nz_hi, g, L) && item_any(first_not_one, g, L)) fl |= NTRU_FLAG_INVALID_FQ;
+    if (inv.invalid(g, L)) fl |= NTRU_FLAG_INVALID_FQ;
     // ---- fp * f mod p
-    nz_hi = false; first_not_one = false;
+    inv = InverseCheck<K>();
     product(ValU8{fp + row}, f, p - 1,
             [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, 0, false>(eo, codes, s_pair, g, sub, true, p, emit); },
             [&](int t, u16x2 rv, u16x2 qv) {
@@ -1205,26 +1176,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
               const long lane0 = row + 2 * K * sub2;
               store_pair(rem_fp + lane0, sp, t, rv);
               store_pair(quot_fp + lane0, sp, t, qv);
-              note_inverse(sub2, t, rv);
+              inv.note(sub2, t, N, rv);
             });
-    if (item_any(nz_hi, g, L) && item_any(first_not_one, g, L)) fl |= NTRU_FLAG_INVALID_FP;
+    if (inv.invalid(g, L)) fl |= NTRU_FLAG_INVALID_FP;
     // ---- (p*fq) * g mod q: the window is reduced mod q (same product; the unreduced p*fq of index.js:155 is host glue)
-    // 'invalid h' iff some index below h's trimmed length differs from the remainder (index.js:165): get that length first
-    int hl = 1;
-    {
-      int top = -1;
+    int top = -1;                                                  // h's trimmed length first: the product's emit compares below it
 #pragma unroll
-      for (int t = 0; t < K; t++) {
-        const int k = 2 * K * sub + 2 * t;
-        const int k0 = k < N ? k : N - 1, k1 = k + 1 < N ? k + 1 : N - 1;
-        if (k < N && h[row + k0]) top = k;
-        if (k + 1 < N && h[row + k1]) top = k + 1;
-      }
-      const unsigned long long bal = __ballot(top >= 0 && L.active);
-      const int src = bal ? 63 - __builtin_clzll(bal) : (int)L.lane;
-      const int top_src = __shfl(top, src);
-      if (bal) hl = top_src + 1;
-    }
+    for (int t = 0; t < K; t++) note_top(top, 2 * K * sub + 2 * t, pair_at(ValU16{h + row}, 2 * K * sub + 2 * t, N));
+    const int hl = item_trimmed_len(top, g, L);
     bool bad = false;
     product(ValU16x3m{fq + row, p, q - 1}, gg, q - 1,
             [&](auto s_pair, auto emit) { add_product_split<PerItemWin, K, ME, true>(eo, codes, s_pair, g, sub, true, q, emit); },
@@ -1235,15 +1194,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_verify_keys_t(
               const long lane0 = row + 2 * K * sub2;
               store_pair(rem_h + lane0, sp, t, rv);
               store_pair(quot_h + lane0, sp, t, qv);
-              const int k = 2 * K * sub2 + 2 * t;
-              const int k0 = k < N ? k : N - 1, k1 = k + 1 < N ? k + 1 : N - 1;
-              bad |= (k < hl && h[row + k0] != rv.x) || (k + 1 < hl && h[row + k1] != rv.y);
+              bad |= differs_below(hl, 2 * K * sub2 + 2 * t, pair_at(ValU16{h + row}, 2 * K * sub2 + 2 * t, N), rv);
             });
     if (item_any(bad, g, L)) fl |= NTRU_FLAG_INVALID_H;
     if (L.active && sub == 0) flags[item] = (uint8_t)fl;
   }
 }
-
 
 // ---- host side: launchers of the vector-ALU families ---------------------------------------------------------------------------
 
@@ -1272,8 +1228,7 @@ static int plan(const ntru_engine *eng, int N, long B, int shared_eo, bool per_i
   if (!K) return fail(NTRU_ERR_UNSUPPORTED, "N too large");
   L->K = K;
   L->g = make_geom(N, K);
-  const size_t raw_len = ((size_t)N + 1) & ~(size_t)1;
-  size_t per_wave = (size_t)L->g.G * ((size_t)L->g.a_len * 4 + (per_item_eo ? (size_t)L->g.eo_len * 8 + raw_len * 2 : 0));
+  const size_t per_wave = per_item_eo ? per_item_lds(L->g).per_wave : (size_t)L->g.G * L->g.a_len * 4;
   L->lds = (size_t)shared_eo * L->g.eo_len * 8 + WAVES_PER_BLOCK * per_wave;
   if (L->lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "parameter set needs more than 160 KiB of LDS");
   const long ngroups = (B + L->g.G - 1) / L->g.G;
@@ -1317,43 +1272,30 @@ static int shared_path_K(const ntru_engine *eng, int N, int q, int p, int *me) {
   return K;
 }
 
-#define DISPATCH_K_SHARED(Kv, MEv, D8v, ...)                                                        \
-  switch ((Kv) * 1000 + (MEv) * 10 + (D8v)) {                                                       \
-    case 13131: { constexpr int KK = 13, MM = 13; constexpr bool DD = true; __VA_ARGS__; } break;   \
-    case 13130: { constexpr int KK = 13, MM = 13; constexpr bool DD = false; __VA_ARGS__; } break;  \
-    case 11111: { constexpr int KK = 11, MM = 11; constexpr bool DD = true; __VA_ARGS__; } break;   \
-    case 11110: { constexpr int KK = 11, MM = 11; constexpr bool DD = false; __VA_ARGS__; } break;  \
-    case 11071: { constexpr int KK = 11, MM = 7; constexpr bool DD = true; __VA_ARGS__; } break;    \
-    case 11070: { constexpr int KK = 11, MM = 7; constexpr bool DD = false; __VA_ARGS__; } break;   \
-    case 9090: { constexpr int KK = 9, MM = 9; constexpr bool DD = false; __VA_ARGS__; } break;     \
-    case 9070: { constexpr int KK = 9, MM = 7; constexpr bool DD = false; __VA_ARGS__; } break;     \
-    default: return fail(NTRU_ERR_UNSUPPORTED, "no shared-step kernel for this (K, mask interval)"); \
+// The admitted (K, mask interval, dot8) tuples, one list per template family: VARIANT binds the constants KK, MM, DD for the
+// statement and the three switches below differ in the tuples they hold and the message of their default.
+#define VARIANT(Kc, Mc, Dc, ...)                                                                                           \
+  case (Kc) * 1000 + (Mc) * 10 + (Dc): {                                                                                   \
+    [[maybe_unused]] constexpr int KK = Kc, MM = Mc; [[maybe_unused]] constexpr bool DD = Dc; __VA_ARGS__;                 \
+  } break;
+#define DISPATCH_K_SHARED(Kv, MEv, D8v, ...)                                                                               \
+  switch ((Kv) * 1000 + (MEv) * 10 + (D8v)) {                                                                              \
+    VARIANT(13, 13, 1, __VA_ARGS__) VARIANT(13, 13, 0, __VA_ARGS__) VARIANT(11, 11, 1, __VA_ARGS__)                        \
+    VARIANT(11, 11, 0, __VA_ARGS__) VARIANT(11, 7, 1, __VA_ARGS__) VARIANT(11, 7, 0, __VA_ARGS__)                          \
+    VARIANT(9, 9, 0, __VA_ARGS__) VARIANT(9, 7, 0, __VA_ARGS__)                                                            \
+    default: return fail(NTRU_ERR_UNSUPPORTED, "no shared-step kernel for this (K, mask interval)");                       \
   }
-
-#define DISPATCH_K_ADD(Kv, MEv, ...)                                                                \
-  switch ((Kv) * 100 + (MEv)) {                                                                     \
-    case 714: { constexpr int KK = 7, MM = 14; __VA_ARGS__; } break;                                \
-    case 707: { constexpr int KK = 7, MM = 7; __VA_ARGS__; } break;                                 \
-    case 510: { constexpr int KK = 5, MM = 10; __VA_ARGS__; } break;                                \
-    case 505: { constexpr int KK = 5, MM = 5; __VA_ARGS__; } break;                                 \
-    case 306: { constexpr int KK = 3, MM = 6; __VA_ARGS__; } break;                                 \
-    case 303: { constexpr int KK = 3, MM = 3; __VA_ARGS__; } break;                                 \
-    case 102: { constexpr int KK = 1, MM = 2; __VA_ARGS__; } break;                                 \
-    case 101: { constexpr int KK = 1, MM = 1; __VA_ARGS__; } break;                                 \
-    default: return fail(NTRU_ERR_UNSUPPORTED, "no add-path kernel for this (K, mask interval)");   \
+#define DISPATCH_K_ADD(Kv, MEv, ...)                                                                                       \
+  switch ((Kv) * 1000 + (MEv) * 10) {                                                                                      \
+    VARIANT(7, 14, 0, __VA_ARGS__) VARIANT(7, 7, 0, __VA_ARGS__) VARIANT(5, 10, 0, __VA_ARGS__) VARIANT(5, 5, 0, __VA_ARGS__) \
+    VARIANT(3, 6, 0, __VA_ARGS__) VARIANT(3, 3, 0, __VA_ARGS__) VARIANT(1, 2, 0, __VA_ARGS__) VARIANT(1, 1, 0, __VA_ARGS__) \
+    default: return fail(NTRU_ERR_UNSUPPORTED, "no add-path kernel for this (K, mask interval)");                          \
   }
-
-#define DISPATCH_K(Kv, ...)                                                                       \
-  switch (Kv) {                                                                                     \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;                                                  \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; } break;                                                  \
-    case 5: { constexpr int KK = 5; __VA_ARGS__; } break;                                                  \
-    case 7: { constexpr int KK = 7; __VA_ARGS__; } break;                                                  \
-    case 9: { constexpr int KK = 9; __VA_ARGS__; } break;                                                  \
-    case 11: { constexpr int KK = 11; __VA_ARGS__; } break;                                                \
-    case 13: { constexpr int KK = 13; __VA_ARGS__; } break;                                                \
-    case 15: { constexpr int KK = 15; __VA_ARGS__; } break;                                                \
-    default: return fail(NTRU_ERR_UNSUPPORTED, "no kernel for this K");                             \
+#define DISPATCH_K(Kv, ...)                                                                                                \
+  switch ((Kv) * 1000) {                                                                                                   \
+    VARIANT(1, 0, 0, __VA_ARGS__) VARIANT(3, 0, 0, __VA_ARGS__) VARIANT(5, 0, 0, __VA_ARGS__) VARIANT(7, 0, 0, __VA_ARGS__) \
+    VARIANT(9, 0, 0, __VA_ARGS__) VARIANT(11, 0, 0, __VA_ARGS__) VARIANT(13, 0, 0, __VA_ARGS__) VARIANT(15, 0, 0, __VA_ARGS__) \
+    default: return fail(NTRU_ERR_UNSUPPORTED, "no kernel for this K");                                                    \
   }
 
 int ntru_launch_encrypt_valu(ntru_engine *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint8_t *d_m, int64_t B,

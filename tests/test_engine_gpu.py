@@ -818,6 +818,42 @@ def test_verify_keys_h_comparison_boundaries_and_unreduced_fp(eng):
         assert np.array_equal(got["rem_fp"], base["rem_fp"])                 # unreduced fp = reduced fp
 
 
+@pytest.mark.parametrize("N,q,path,kernel", [(17, 32, 0, "k_verify_keys<1>"), (65, 2048, 0, "k_verify_keys_t<1,2>"),
+                                             (193, 2048, 1, "k_verify_keys<3>"), (193, 2048, 2, "k_verify_keys_t<3,6>")])
+def test_verify_keys_h_boundaries_valu_kernels(eng, N, q, path, kernel):
+    """The construction of test_verify_keys_h_comparison_boundaries_and_unreduced_fp through the vector-ALU kernels, which share
+    one set of flag helpers: N = 17 packs seven items into a wave (per-item lane mask, partial last group), N = 65 has one pair
+    per lane, N = 193 three (a cut can fall inside a lane).  Cuts sit at 0, 1, 2, around a lane's 2K outputs, around N / 2 and
+    the lane boundaries next to it, and at the top.  Every array byte for byte against the oracle."""
+    rng = np.random.default_rng(1000 * N + path)
+    p, K = 3, int(kernel.split("<")[1].split(",")[0].rstrip(">"))
+    lane = N // 2 // (2 * K) * (2 * K)
+    cuts = sorted({0, 1, 2, 2 * K - 1, 2 * K, 2 * K + 1, N // 2, lane, lane + 2 * K, N - 2, N - 1, N} & set(range(N + 1)))
+    B = 4 * len(cuts) + 2
+    d = N // 3
+    f = ternary_rows(rng, B, N, d, max(d - 1, 0), two=-1); g = ternary_rows(rng, B, N, d, d, two=-1)
+    fq = rng.integers(0, q, (B, N)); fp = rng.integers(0, 256, (B, N))
+    h = orc.verify_keys_batch(N, q, p, f, g, fq, fp % 3, np.zeros((B, N), np.int64))["rem_h"].astype(np.int64)
+    for i, c in enumerate(cuts):
+        h[4 * i, c:] = 0                                   # truncated at c: equal below its own length -> valid
+        h[4 * i + 1, c:] = 0
+        if c > 0: h[4 * i + 1, rng.integers(0, c)] ^= 1     # ... with one coefficient below the cut changed
+        h[4 * i + 2, min(c, N - 1)] = (h[4 * i + 2, min(c, N - 1)] + 1) % q     # one coefficient changed, everything else equal
+        h[4 * i + 3, c:] = 0
+        if c < N: h[4 * i + 3, rng.integers(c, N)] = 1      # a lone non-zero coefficient above a matching prefix
+    h[B - 1] = 0                                          # the zero polynomial: length 1, compares index 0
+    want = orc.verify_keys_batch(N, q, p, f, g, fq, fp, h)
+    eng.set_kernel_path(path)
+    try:
+        got = eng.verify_keys_batch(N, q, p, f, g, fq, fp, h)
+        assert eng.last_kernel() == kernel
+    finally:
+        eng.set_kernel_path(0)
+    for k in want:
+        assert np.array_equal(got[k], want[k]), (k, np.nonzero(got[k] != want[k]))
+    assert (want["flags"][0::4][1:len(cuts)] & 4 == 0).all()            # the truncated copies are valid h
+
+
 def test_verify_keys_device_pointers_at_any_alignment(eng):
     """ntru_verify_keys_batch_dev with every array at an odd byte offset (uint16 arrays stay 2-aligned): the matrix-core
     kernel reads rows through aligned chunks + shifts and must neither read garbage nor write outside its rows."""
