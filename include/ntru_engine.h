@@ -541,6 +541,30 @@ int ntru_check_inverse_batch(ntru_engine_t *eng, int N, int M, int n, const uint
 int ntru_check_inverse_batch_dev(ntru_engine_t *eng, int N, int M, int n, const uint16_t *d_f, const uint16_t *d_fq,
                                  const uint16_t *d_quotI, const uint16_t *d_remI, int64_t B, uint8_t *d_flags);
 
+/* ---- re-randomising and shuffling ciphertexts under the shared public key h: encryptBits (index.js:87-110) with an existing
+ *      ciphertext in the place of m -- addPolynomials(e, multiplyPolynomials(r, h, q), q), then dividePolynomials(., I, q)
+ *      (index.js:90-92).  VerifyEncrypt puts no range constraint on m (circuits/ntru.circom:188-208), so
+ *      {r, m: the old row, h, quotientE, remainderE} is a valid witness and ntru_check_encrypt_batch accepts it.
+ *      For output row i, s = src ? src[i] : i:
+ *        e_out[i] = remainder and quotE[i] = quotient mod q of (r[i] * h + e_in[s]) mod q split by 1 - x^N,
+ *      exactly what ntru_encrypt_batch writes for (h, r[i], m) with m the 16-bit row e_in[s]:
+ *        e_out[i] = (Enc(0; r[i]) + e_in[s]) mod q, and quotE[i] is that of Enc(0; r[i]).
+ *      e_in [B_in][N]: any uint16_t value, reduced mod q.  src [B] (DEVICE memory in the _dev form) is a general gather: repeats are
+ *      allowed and B may differ from B_in; src == NULL needs B <= B_in.  quotE may be NULL.  (N, q), h and r as for
+ *      ntru_encrypt_batch, with the same choice of kernels (ntru_engine_set_kernel_path): where the matrix-core encrypt applies this
+ *      is ONE kernel (k_reencrypt_md / k_reencrypt_m: r in, the old row in, e and the quotient out, 7 N bytes per row); elsewhere the
+ *      vector-ALU encrypt of a zero message followed by one add kernel, with the same bytes.
+ *      NTRU_ERR_ARG before anything is launched: a NULL buffer, a negative size, src == NULL with B > B_in, e_in and e_out ranges
+ *      that overlap while src is given (with src == NULL, e_out == e_in -- in place -- is allowed), and in the host form an index
+ *      outside [0, B_in).  In the _dev form an index outside [0, B_in) is not an error: the kernels never read outside
+ *      e_in[0 .. B_in) -- to the dword: a row that is read is read in whole dwords, so up to 2 bytes next to an e_in that is not
+ *      4-byte aligned share an access with it -- and such a row is not read at all: it takes an all-zero addend, so its result is
+ *      Enc(0; r[i]). */
+int ntru_reencrypt_batch_dev(ntru_engine_t *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint16_t *d_e_in,
+                             int64_t B_in, const int64_t *d_src, int64_t B, uint16_t *d_e_out, uint16_t *d_quotE);
+int ntru_reencrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint16_t *e_in, int64_t B_in,
+                         const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE);
+
 #ifdef __cplusplus
 }
 #endif

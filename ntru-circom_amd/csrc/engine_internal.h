@@ -16,6 +16,9 @@
 //                            entry points and ntru_pipeline_bytes_batch)
 //   packed_ciphertexts.hip   ciphertexts as packOutput(q - 1, N, e) rows: sums straight from the packed rows, unpack to dense rows, tally
 //                            and decrypt on them (kernels, *_dev and host-pointer entry points)
+//   matrix_reencrypt.hip     re-randomising and shuffling ciphertexts: the shared-key encrypt body (matrix_encrypt_body.h) with a gathered
+//                            16-bit row as the addend (k_reencrypt_m, k_reencrypt_md), the add kernel behind the vector-ALU route, the *_dev
+//                            and host-pointer entry points
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

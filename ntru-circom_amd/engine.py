@@ -93,6 +93,8 @@ _SIGS = {
     **_both("ntru_sum_groups_packed", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_packed_batch", "p iii ppppp ll ppppp"),
     **_both("ntru_decrypt_packed_batch", "p iii ppp l pppp"),
+    # re-randomising and shuffling under the shared public key: the functions are in mix.py
+    **_both("ntru_reencrypt_batch", "p ii ppp l p l pp"),
     "ntru_keygen_workspace_bytes": _sig("i l Z"),
     **_both("ntru_keygen_batch", "p iiiii p u i l pppppppp"),
 }

@@ -508,6 +508,32 @@ export default class NTRU {
     return { e, quotientE: quot };
   }
 
+  // ---- one mix step (additive): re-randomises ciphertexts under h and optionally reorders them -- encryptBits (index.js:87-110) with
+  // the old ciphertext in the place of m.  e: Uint16Array[Bin*N] (any value, reduced mod q), r: Uint8Array[B*N] in {0,1,2}, src: B row
+  // indices into e (Array or BigInt64Array; repeats allowed; null: row i, B <= Bin) -> { e, quotientE, m } as Uint16Array[B*N]: output
+  // row i is (Enc(0; r[i]) + e[src[i]]) mod q, quotientE that of Enc(0; r[i]), m the gathered rows: {r, m, h, quotientE, remainderE: e}
+  // satisfies VerifyEncrypt (circuits/ntru.circom:188-208).  Composed here from encryptBatch on a zero message and addBatch, with the
+  // gather on the typed arrays; the bytes are those of the engine's fused ntru_reencrypt_batch, which has no native Node path yet.
+  reencryptBatch(e, r, B, src = null, wantWitness = true, out = {}) {
+    const { N, q } = this;
+    const Bin = e.length / N;
+    if (!Number.isInteger(Bin)) throw new RangeError('reencryptBatch: e is not a whole number of rows');
+    if (r.length !== B * N) throw new RangeError('reencryptBatch: r must hold B rows');
+    if (src == null && B > Bin) throw new RangeError('reencryptBatch: without src, B must not exceed the rows of e');
+    if (src != null && src.length !== B) throw new RangeError('reencryptBatch: src must hold B indices');
+    const m = new Uint16Array(B * N);
+    for (let i = 0; i < B; i++) {
+      const s = src == null ? i : Number(src[i]);
+      if (!Number.isInteger(s) || s < 0 || s >= Bin) throw new RangeError(`reencryptBatch: src[${i}] = ${s} is outside the rows of e`);
+      const row = e.subarray(s * N, (s + 1) * N);
+      for (let k = 0; k < N; k++) m[i * N + k] = row[k] & (q - 1);
+    }
+    const zero = this.encryptBatch(r, new Uint8Array(B * N), B, wantWitness, { quotientE: out.quotientE });
+    const sum = out.e || new Uint16Array(B * N);
+    if (B > 0) engine().addBatch(N, q, zero.e, m, B, sum);
+    return { e: sum, quotientE: zero.quotientE, m };
+  }
+
   // r for B encryptions drawn on the GPU: generateCustomArray(N, dr, dr) with -1 -> p-1 (index.js:89) on the ChaCha20
   // stream of `key` (Uint32Array[8]) for item indices firstItem .. firstItem+B-1; replayable on any host.
   // NTRU.samplerRounds(rounds): 20 (ChaCha20 as in RFC 8439, the default), 12 or 8 rounds of the block function behind sampleR and the

@@ -19,6 +19,7 @@ import secrets
 import numpy as np
 
 from . import lift as lift_calls
+from . import mix as mix_calls
 from . import packed as packed_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
@@ -493,6 +494,27 @@ class NTRU:
             value, q1, r1, q2 = packed_calls.decrypt_packed_batch(self.engine, N, q, p, expandArray(self.f, N), expandArray(self.fp, N),
                                                                   packed, want_witness=wantWitness)
         return {"value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    # -- one mix step: encryptBits (index.js:87-110) with an old ciphertext in the place of m ------------------------------------------
+    def reencryptBatch(self, e, r=None, src=None, wantWitness=True):
+        """Re-randomises the ciphertexts `e` [B_in][N] under h: output row i is (Enc(0; r[i]) + e[src[i]]) mod q (src None: row i;
+        any gather, repeats allowed).  r: [B][N] signed ternary or already mapped to {0, 1, p - 1} (index.js:89); None draws every row
+        as encryptBits does.  Returns {"value", "r", "m", "quotientE"} as [B][N] arrays: m is the gathered rows, and
+        {r, m, h, quotientE, remainderE: value} satisfies VerifyEncrypt (quotientE is None without wantWitness)."""
+        N, q, p = self.N, self.q, self.p
+        e = np.asarray(e).reshape(-1, N)
+        if src is not None:
+            src = np.asarray(src, dtype=np.int64).reshape(-1)
+            if np.any((src < 0) | (src >= e.shape[0])):
+                raise ValueError("reencryptBatch: src index outside the rows of e")
+        B = e.shape[0] if src is None else src.shape[0]
+        if r is None:
+            r = [generateCustomArray(N, self.dr, self.dr) for _ in range(B)]
+        r = np.asarray(r).reshape(-1, N)
+        r = np.where(r == -1, p - 1, r).astype(np.uint8)
+        m = np.ascontiguousarray((e if src is None else e[src]) % q).astype(np.uint16)
+        value, quot = mix_calls.reencrypt_batch(self.engine, N, q, expandArray(self.h, N), r, e % q, src=src, want_quot=wantWitness)
+        return {"value": value, "r": r, "m": m, "quotientE": quot}
 
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
