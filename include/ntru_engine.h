@@ -265,7 +265,7 @@ int ntru_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t
  * kernel argument.  Honoured by everything that runs decryptBits: ntru_decrypt_batch[_dev], ntru_decrypt_batch_pitched_dev,
  * ntru_decrypt_pack_batch_dev, ntru_decrypt_peritem_batch[_dev], ntru_decrypt_bytes_batch[_dev], ntru_tally_decrypt_batch[_dev],
  * ntru_tally_decrypt_packed_batch[_dev], ntru_decrypt_packed_batch[_dev], the decrypt stage of ntru_pipeline_batch and
- * ntru_pipeline_bytes_batch, ntru_multi_decrypt_batch (ntru_multi_set_lift).  ntru_check_decrypt_batch checks the circuit and
+ * ntru_pipeline_bytes_batch, ntru_scan_bytes_batch[_dev], ntru_scan_bytes_packed_batch[_dev], ntru_multi_decrypt_batch (ntru_multi_set_lift). ntru_check_decrypt_batch checks the circuit and
  * ntru_verify_keys_batch has no lift: neither changes.
  * The mode is read when a call enqueues and reaches the kernel by value: a _dev call enqueued before a later ntru_engine_set_lift
  * keeps the mode it was enqueued with.  As with ntru_engine_set_stream and ntru_engine_set_kernel_path, do not change it while a
@@ -318,6 +318,47 @@ int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nb
 int ntru_pipeline_bytes_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const int8_t *f, const uint8_t *fp,
                               const uint32_t *key, uint64_t first_item, int n1, int n2, const uint8_t *r, int nbytes,
                               const uint8_t *msg, int64_t B, uint8_t *r_out, uint16_t *e, uint8_t *msg_out, uint8_t *flags);
+
+/* ---- scanning: which rows of a batch does a key decrypt to a well-formed message that carries the expected padding?  The read side of
+ *      the README's "pad the message with data that can be confirmed during decryption": decryptStr (index.js:84-86) on decryptBits
+ *      (index.js:111-140) for every row under each of K private keys, tested and compacted on the device, so that the hits alone cross
+ *      the bus.
+ *      Row b is a HIT for key k when, for value = decryptBits(e[b]).value under (f[k], fp[k]):
+ *        - ntru_rows_to_bytes(value) gives flag byte 0: the first 8 nbytes coefficients are 0 or 1 and every later one is 0;
+ *        - the bytes [tag_off, tag_off + tag_len) of the message it gives equal tag[0 .. tag_len).
+ *      tag is a HOST pointer in every form, read when the call is made and handed to the kernels by value; 0 <= tag_len <=
+ *      NTRU_SCAN_MAX_TAG, tag_off >= 0, tag_off + tag_len <= nbytes; tag_len == 0 tests the flags only (tag may then be NULL).
+ *      f [K][N] int8_t, fp [K][N] uint8_t, K >= 1; e [B][N] uint16_t, or packed [B][output_size][4] uint64_t, the wire format of
+ *      "packed ciphertexts" above (ignored fields and bits as there).
+ *      count [K] int64_t: count[k] is SET to the number of hits of key k among the B rows; it may exceed max_hits.
+ *      hit_row [K][max_hits] int64_t, hit_bytes [K][max_hits][nbytes]: the first min(count[k], max_hits) hits of key k in ascending
+ *      row order -- the row index, and the nbytes message bytes as ntru_rows_to_bytes writes them.  Nothing behind that prefix is
+ *      written.  max_hits == 0 only counts (the hit buffers may be NULL).  hit_row needs 8-byte alignment, hit_bytes none.
+ *      The result is the same bytes whatever the launch shape, the pass size, the chunking of the host form and the kernel path:
+ *      positions come from prefix sums, never from the arrival order of an atomic.
+ *      Domain: that of ntru_decrypt_bytes_batch; the packed forms as ntru_decrypt_packed_batch.  A NULL buffer, K < 1, a tag outside
+ *      the message, max_hits < 0 are NTRU_ERR_ARG before anything is launched; B == 0 sets the counts to 0.  The lift is the
+ *      engine's mode (ntru_engine_set_lift), read at enqueue.
+ *   _dev forms: enqueue on the engine's stream, do not synchronise and allocate nothing per call beyond the engine-owned scratch
+ *      buffer: rows go in passes of at most 65536; per pass (packed: k_unpack_rows first) and key, ntru_decrypt_batch_dev and
+ *      ntru_rows_to_bytes_dev run as they are into scratch, then k_scan_mark (one hit count per 256 rows), k_scan_offsets (one
+ *      workgroup: exclusive offsets + the key's running count d_count[k]) and k_scan_emit (scan_hits.hip).
+ *   host forms: the rows stream through the chunked pipeline with the keys as shared inputs; counts and hits stay on the device until
+ *      the last chunk, then the K counts and the stored prefixes come down.  count is a host array. */
+#define NTRU_SCAN_MAX_TAG 32
+int ntru_scan_bytes_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, int K, const int8_t *f, const uint8_t *fp,
+                          const uint16_t *e, int64_t B, int tag_off, int tag_len, const uint8_t *tag, int64_t max_hits,
+                          int64_t *hit_row, uint8_t *hit_bytes, int64_t *count);
+int ntru_scan_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, int K, const int8_t *d_f, const uint8_t *d_fp,
+                              const uint16_t *d_e, int64_t B, int tag_off, int tag_len, const uint8_t *tag, int64_t max_hits,
+                              int64_t *d_hit_row, uint8_t *d_hit_bytes, int64_t *d_count);
+int ntru_scan_bytes_packed_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, int K, const int8_t *f, const uint8_t *fp,
+                                 const uint64_t *packed, int64_t B, int tag_off, int tag_len, const uint8_t *tag, int64_t max_hits,
+                                 int64_t *hit_row, uint8_t *hit_bytes, int64_t *count);
+int ntru_scan_bytes_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, int K, const int8_t *d_f,
+                                     const uint8_t *d_fp, const uint64_t *d_packed, int64_t B, int tag_off, int tag_len,
+                                     const uint8_t *tag, int64_t max_hits, int64_t *d_hit_row, uint8_t *d_hit_bytes,
+                                     int64_t *d_count);
 
 /* ---- encryptBits and decryptBits with a SEPARATE key pair for every item (one ciphertext per recipient, one decryption per key
  *      holder): h, f and fp are [B][N] batch arrays with the types and layout of ntru_keygen_batch's outputs, so its device arrays

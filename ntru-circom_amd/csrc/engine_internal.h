@@ -19,6 +19,9 @@
 //   matrix_reencrypt.hip     re-randomising and shuffling ciphertexts: the shared-key encrypt body (matrix_encrypt_body.h) with a gathered
 //                            16-bit row as the addend (k_reencrypt_m, k_reencrypt_md), the add kernel behind the vector-ALU route, the *_dev
 //                            and host-pointer entry points
+//   scan_hits.hip            scanning a batch for the rows a key decrypts to a well-formed, tagged message: decrypt and rows_to_bytes as
+//                            they are, then mark / offsets / emit kernels that compact the hits on the device (kernels, *_dev and
+//                            host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -206,6 +209,10 @@ NTRU_HIDDEN int ntru_launch_sum_finish(ntru_engine *eng, int N, int mod, const S
 NTRU_HIDDEN int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, const void *rows, size_t row_bytes,
                                      const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G, uint16_t *out,
                                      ntru_sum_launcher launch);
+
+// ---- packed rows (packed_ciphertexts.hip) -----------------------------------------------------------------------------------------------
+// Enqueues k_unpack_rows: B rows of packOutput(q - 1, N, e) -> dense uint16_t [B][N] (scan_hits.hip unpacks a pass with it).
+NTRU_HIDDEN int ntru_launch_unpack_rows(ntru_engine *eng, int N, int q, const uint64_t *d_packed, int64_t B, uint16_t *d_rows);
 
 // ---- host-pointer entry points (ntru_host.hip; keygen_batch, ciphertext_sum, message_bytes) --------------------------------------------------------------
 // True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).

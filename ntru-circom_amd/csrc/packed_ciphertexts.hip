@@ -259,6 +259,12 @@ int launch_unpack_rows(ntru_engine *eng, int N, const PackShape &ps, const uint6
 
 }  // namespace
 
+int ntru_launch_unpack_rows(ntru_engine *eng, int N, int q, const uint64_t *d_packed, int64_t B, uint16_t *d_rows) {
+  PackShape ps;
+  if (int rc = pack_shape(q, N, &ps)) return rc;
+  return launch_unpack_rows(eng, N, ps, d_packed, B, d_rows);
+}
+
 extern "C" int ntru_sum_groups_packed_dev(ntru_engine_t *eng, int N, int mod, const uint64_t *d_packed, const uint16_t *d_weights,
                                           const int64_t *d_offsets, int64_t K, int64_t G, uint16_t *d_out) {
   if (int rc = ntru_check_sum_args(eng, N, mod, !d_offsets, K, G, "ntru_sum_groups_packed")) return rc;

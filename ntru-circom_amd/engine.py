@@ -95,6 +95,9 @@ _SIGS = {
     **_both("ntru_decrypt_packed_batch", "p iii ppp l pppp"),
     # re-randomising and shuffling under the shared public key: the functions are in mix.py
     **_both("ntru_reencrypt_batch", "p ii ppp l p l pp"),
+    # scanning a batch for the rows a key decrypts to a tagged message: the functions are in scan.py
+    **_both("ntru_scan_bytes_batch", "p iiiii ppp l ii p l ppp"),
+    **_both("ntru_scan_bytes_packed_batch", "p iiiii ppp l ii p l ppp"),
     "ntru_keygen_workspace_bytes": _sig("i l Z"),
     **_both("ntru_keygen_batch", "p iiiii p u i l pppppppp"),
 }

@@ -863,6 +863,42 @@ export default class NTRU {
     if (blocks === 0) return Promise.resolve(this._rowsToBytes(new Uint8Array(0), 0, length));
     return this.decryptBatchAsync(e, blocks, false).then(o => this._rowsToBytes(o.value, blocks, length));
   }
+
+  // ---- scanning (additive; INTEGRATION.md "Scanning: scanBytes"): which blocks does a key decrypt to a well-formed message that carries
+  // the tag?  Same definition, order and truncation as the engine's ntru_scan_bytes_batch and the Python NTRU.scanBytes: block b is a hit
+  // for a key when decryptBytes gives it flag 0 and bytes [tagOffset, tagOffset + tag.length) of its message equal `tag` (at most 32
+  // bytes).  The addon's export list is fixed, so this is composed from decryptBytes per key plus a filter in JavaScript: correct, not
+  // fast -- every block's bytes cross the bus.  With lift: 'centred' it throws what decryptBytes throws.
+  // e: Uint16Array[blocks*N]; keys: [{f, fp}] or [[f, fp]] (default: this instance's key); maxHits null keeps every hit, 0 only counts.
+  // -> per key { count, rows: Array of block indices, bytes: Uint8Array[stored * bytesPerBlock] }, stored = min(count, maxHits)
+  scanBytes(e, blocks, { keys = null, tag = new Uint8Array(0), tagOffset = 0, maxHits = null } = {}) {
+    const { N, p, q, df, dg, dr, lift } = this, W = this.bytesPerBlock;
+    if (typeof tag === 'string') tag = Uint8Array.from(tag, c => c.charCodeAt(0));
+    if (tag.length > 32) throw new Error(`scanBytes: a tag has at most 32 bytes, got ${tag.length}`);
+    if (!(Number.isInteger(tagOffset) && tagOffset >= 0 && tagOffset + tag.length <= W))
+      throw new Error(`scanBytes: the tag [${tagOffset}, ${tagOffset + tag.length}) does not lie inside the ${W} message bytes`);
+    if (maxHits !== null && !(Number.isInteger(maxHits) && maxHits >= 0)) throw new Error('scanBytes: negative maxHits');
+    if (keys === null) keys = [{ f: this.f, fp: this.fp }];
+    if (keys.length < 1) throw new Error('scanBytes: need at least one key');
+    const limit = maxHits === null ? blocks : maxHits;
+    return keys.map(key => {
+      const [f, fp] = Array.isArray(key) ? key : [key.f, key.fp];
+      const one = new NTRU({ N, p, q, df, dg, dr, f: Array.from(f), fp: Array.from(fp), lift });
+      const { data, flags } = one.decryptBytes(e, blocks, blocks * W);
+      const rows = [], kept = [];
+      let count = 0;
+      for (let b = 0; b < blocks; b++) {
+        if (flags[b] !== 0) continue;
+        let same = true;
+        for (let j = 0; j < tag.length && same; j++) same = data[b * W + tagOffset + j] === tag[j];
+        if (!same) continue;
+        if (count++ < limit) { rows.push(b); kept.push(data.subarray(b * W, (b + 1) * W)); }
+      }
+      const bytes = new Uint8Array(kept.length * W);
+      kept.forEach((row, i) => bytes.set(row, i * W));
+      return { count, rows, bytes };
+    });
+  }
 }
 
 // ---- witness checks: does a witness satisfy VerifyEncrypt / VerifyDecrypt / VerifyInverse (circuits/ntru.circom)? ----------------

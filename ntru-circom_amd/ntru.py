@@ -21,6 +21,7 @@ import numpy as np
 from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
+from . import scan as scan_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
 
@@ -274,8 +275,8 @@ class NTRU:
     """index.js:7-207, hot-path methods.  Every return value is made of plain Python lists / ints.
 
     lift="reference" (the default) decrypts with index.js:117 verbatim and never touches the engine's mode; lift="centred" runs every
-    decrypt-family method (decryptBits, decryptStr, decryptBytes, tallyBatch, tallyPacked, decryptPackedBatch, decryptBatchPerKey, the
-    decrypt stage of pipeline) with the engine in the centred mode and puts the engine back into the mode it had (lift.py), so
+    decrypt-family method (decryptBits, decryptStr, decryptBytes, tallyBatch, tallyPacked, decryptPackedBatch, decryptBatchPerKey, scanBytes,
+    scanPacked, the decrypt stage of pipeline) with the engine in the centred mode and puts the engine back into the mode it had (lift.py), so
     an engine shared by two instances is never left in the other's mode.  The centred mode returns the plaintext where the reference's
     `+ 1` does not (q = 4096 with p = 3, p = 5 or 7 at almost every q).  The `params` of a witness do not depend on the mode;
     VerifyDecrypt (checkWitnesses) accepts a centred witness only when the addend (p - q % p) % p is 1."""
@@ -629,6 +630,31 @@ class NTRU:
         if not 0 <= length <= len(data):
             raise ValueError("decryptBytes: length %d is outside the %d bytes of %d blocks" % (length, len(data), e.shape[0]))
         return data[:length], flags
+
+    # -- scanning: which blocks does a key decrypt to a well-formed message that carries the expected tag? ----------------------------
+    def _scan(self, call, rows, keys, tag, tagOffset, maxHits):
+        N, W = self.N, self.bytesPerBlock
+        if keys is None:
+            if self.f is None:
+                raise TypeError("Cannot read property 'map' of null")
+            keys = [(self.f, self.fp)]
+        f = [expandArray(list(k[0]), N) for k in keys]
+        fp = [expandArray(list(k[1]), N) for k in keys]
+        with self._lifted():
+            count, rows_, data = call(self.engine, N, self.q, self.p, W, f, fp, rows, tag=tag, tag_off=tagOffset, max_hits=maxHits)
+        return {"count": count, "rows": rows_, "bytes": data}
+
+    def scanBytes(self, e, keys=None, tag=b"", tagOffset=0, maxHits=None):
+        """Tries every key of `keys` -- (f, fp) pairs, f signed ternary; None: this instance's own key -- on every block of e
+        [blocks][N] and keeps the hits: the blocks decryptBytes gives flag 0 for and whose bytes [tagOffset, tagOffset + len(tag)) equal
+        `tag` (at most 32 bytes).  Decrypt, test and compaction run on the device; only the hits come back.  Returns {"count": [K] int64
+        (every hit, may exceed maxHits), "rows", "bytes"}: per key the first min(count, maxHits) hits in ascending block order, block
+        indices and [.][bytesPerBlock] uint8 messages.  maxHits None keeps every hit, 0 only counts."""
+        return self._scan(scan_calls.scan_bytes_batch, np.asarray(e, dtype=np.uint16).reshape(-1, self.N), keys, tag, tagOffset, maxHits)
+
+    def scanPacked(self, packed, keys=None, tag=b"", tagOffset=0, maxHits=None):
+        """scanBytes on blocks in the wire format: rows of packOutput(q - 1, N, e), uint64 [blocks][outputSize][4]."""
+        return self._scan(scan_calls.scan_bytes_packed_batch, packed, keys, tag, tagOffset, maxHits)
 
     def encryptStr(self, inputPlain):
         return self.encryptBits(stringToBits(inputPlain))["value"]
