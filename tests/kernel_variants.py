@@ -1,7 +1,8 @@
 """Every kernel instantiation the library compiles, with a call that launches it.
 
-Plain data, imported by tests/test_build_quality.py (every compiled instantiation has a row and every row names one) and by
-tests/test_kernel_variants_gpu.py (each row's calls against the oracle, and the dispatch sweep).  Not a test module.
+Plain data, imported by tests/test_build_quality.py (every compiled instantiation has a row and every row names one), by
+tests/test_kernel_variants_gpu.py (each row's calls against the oracle, through the runners of tests/variant_runners.py, and the
+dispatch sweep) and by tests/valu_geometry.py (the K ranges; the rows pin its restatement of the launchers).  Not a test module.
 
 A row:
   kernel  the demangled instantiation as `c++filt` prints it, return type and argument list dropped ("k_decrypt_s<11, 11, true>")

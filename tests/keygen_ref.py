@@ -1,5 +1,5 @@
 """CPU replay of ntru_keygen_batch's documented stream positions (include/ntru_engine.h) on oracle.ntru_oracle's sampler and
-oracle.ntru_keygen's inverses.  Not a test module: imported by tests/test_keygen_gpu.py and tests/test_kernel_variants_gpu.py."""
+oracle.ntru_keygen's inverses.  Not a test module: imported by tests/test_keygen_gpu.py and tests/variant_runners.py."""
 import numpy as np
 
 from oracle import ntru_keygen as kg

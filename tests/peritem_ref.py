@@ -1,6 +1,6 @@
 """The per-item scheme's CPU reference, built from oracle.ntru_oracle.polymul_split_batch (one key pair per row), and the edge operands
 the GPU tests of matrix_peritem_scheme.hip feed it.  Not a test module: imported by tests/test_peritem_scheme_gpu.py and
-tests/test_kernel_variants_gpu.py."""
+tests/variant_runners.py (the runners of tests/test_kernel_variants_gpu.py)."""
 import numpy as np
 
 from oracle import ntru_oracle as orc
