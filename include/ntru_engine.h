@@ -606,6 +606,52 @@ int ntru_reencrypt_batch_dev(ntru_engine_t *eng, int N, int q, const uint16_t *d
 int ntru_reencrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint16_t *e_in, int64_t B_in,
                          const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE);
 
+/* ---- drawing the mix order: the permutation of a mix step from the same kind of ChaCha20 stream as r and the keys, made by a
+ *      stable sort on the device, and a whole mix step from a key (permutation.hip).
+ *      The permutation of B items under `key` (8 words, a HOST pointer in every form, as for ntru_sample_ternary) and perm_id:
+ *        k_i    = w[2 j] | (uint64_t)w[2 j + 1] << 32 with j = i mod 8, where w[0..15] is the output of the RFC 8439 ChaCha20 block
+ *                 function under `key` with block counter floor(i / 8) and nonce (perm_id_lo, perm_id_hi, NTRU_PERM_NONCE2).
+ *                 NTRU_PERM_NONCE2 ("PERM") differs from the sampler's 0x4e545255 ("NTRU"), so a permutation never shares a block
+ *                 with a draw of r or of a key under the same key.  Always 20 rounds: ntru_engine_set_sampler_rounds does not apply
+ *                 (as for ntru_keygen_batch).
+ *        src    = the stable ascending argsort of k: src[j] is the index whose key has rank j; equal keys keep index order.
+ *        dst    = its inverse: dst[src[j]] = j.
+ *      Any host replays it with a ChaCha20 implementation and a stable sort.  The order is uniform up to ties: two of the B keys
+ *      collide with probability below B^2 / 2^65 (about 2^-25 at B = 2^20), and a tie resolves by index.
+ *      0 <= B <= NTRU_PERM_MAX_B; B == 0 is NTRU_OK with nothing launched.
+ *      ntru_argsort_keys_dev is the sort by itself: d_order [B] = the stable ascending argsort of ANY device keys d_keys [B], which
+ *      are not modified; the two ranges must not overlap.  Eight passes of one byte, per pass a per-tile digit histogram
+ *      (k_perm_hist), exclusive offsets over digit x tile (k_perm_offsets) and a scatter that ranks every key inside its tile in
+ *      key order (k_perm_scatter); positions come from prefix sums only -- no global atomic -- and every dependency between
+ *      workgroups is a kernel boundary.  The temporaries (24 B per key + 1 KiB per 1024 keys) come from the engine's scratch buffer.
+ *      ntru_draw_permutation[_dev]: d_dst may be NULL; d_src may be NULL only if d_dst is not.  The host form brings only src / dst
+ *      down.
+ *      ntru_mix_batch_dev is one mix step from a key, enqueued on the engine's stream as
+ *        ntru_sample_ternary_dev(N, n1, n2, p - 1, key, first_item, B) into d_r,
+ *        the permutation (key, perm_id) into d_src,
+ *        ntru_reencrypt_batch_dev(N, q, d_h, d_r, d_e_in, B, d_src, B, d_e_out, d_quotE).
+ *      d_r [B][N] uint8_t and d_src [B] int64_t are outputs the caller owns and must supply (the prover needs both for the witness:
+ *      {r, m: e_in[src[i]], h, quotientE, remainderE}); d_quotE may be NULL; d_e_out must not overlap d_e_in.  The sampler honours
+ *      ntru_engine_set_sampler_rounds and the re-encrypt the kernel path, as everywhere.
+ *      ntru_mix_batch is the host-pointer form: the permutation is drawn on the device and brought down, the rows e_in[src[o ..]]
+ *      are gathered while the staging buffer of a chunk is filled (as ntru_reencrypt_batch does), r is sampled on the device per
+ *      chunk from positions first_item + o .. -- it never goes up, and comes down only when r_out is given.  r_out, src_out and
+ *      quotE may be NULL.
+ *      NTRU_ERR_ARG with a message of its own, before the engine is looked at and before anything is launched: B < 0,
+ *      B > NTRU_PERM_MAX_B, a NULL key, a NULL required buffer with B > 0, overlapping ranges where they are forbidden (keys / order,
+ *      src / dst, e_in / e_out, and any two outputs of a mix call), and for the mix calls what ntru_sample_ternary refuses; then a
+ *      NULL engine and what ntru_reencrypt_batch refuses. */
+#define NTRU_PERM_NONCE2 0x5045524du
+#define NTRU_PERM_MAX_B (1 << 24)
+int ntru_argsort_keys_dev(ntru_engine_t *eng, const uint64_t *d_keys, int64_t B, int64_t *d_order);
+int ntru_draw_permutation_dev(ntru_engine_t *eng, const uint32_t *key, uint64_t perm_id, int64_t B, int64_t *d_src, int64_t *d_dst);
+int ntru_draw_permutation(ntru_engine_t *eng, const uint32_t *key, uint64_t perm_id, int64_t B, int64_t *src, int64_t *dst);
+int ntru_mix_batch_dev(ntru_engine_t *eng, int N, int q, int p, const uint16_t *d_h, const uint32_t *key, uint64_t first_item, int n1,
+                       int n2, uint64_t perm_id, const uint16_t *d_e_in, int64_t B, uint8_t *d_r, int64_t *d_src, uint16_t *d_e_out,
+                       uint16_t *d_quotE);
+int ntru_mix_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const uint32_t *key, uint64_t first_item, int n1, int n2,
+                   uint64_t perm_id, const uint16_t *e_in, int64_t B, uint8_t *r_out, int64_t *src_out, uint16_t *e_out, uint16_t *quotE);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ Layout
   engine.py              ctypes binding of the C ABI (numpy host buffers or raw device pointers)
   lift.py                the lift of decryptBits as a mode of an engine: set_lift, get_lift, using (functions on an Engine / MultiEngine)
   packed.py              sums, tallies and decrypts of ciphertexts that arrive as packOutput rows (functions on an Engine)
-  mix.py                 re-randomising and shuffling ciphertexts under the shared public key (functions on an Engine)
+  csrc/permutation.hip   the order of a mix step drawn on the device (ChaCha20 sort keys + a stable radix argsort), one call per mix step
+  mix.py                 re-randomising and shuffling ciphertexts under the shared public key, the order drawn on the device, a whole
+                         mix step from a key (functions on an Engine)
   scan.py                scanning a batch for the rows a key decrypts to a tagged message; only the hits come back (functions on an Engine)
   ntru.py                `NTRU` class + pure functions with the reference's names and semantics (index.js)
   js/                    N-API addon + ES-module shim exposing the same surface to Node.js
@@ -22,6 +24,7 @@ from .engine import (FLAG_NOT_BITS, FLAG_PAD_NONZERO, Engine, EngineError, Multi
                      load_library)
 from . import lift, mix, packed, scan, sharding  # noqa: F401
 from .mix import reencrypt_batch, reencrypt_batch_dev  # noqa: F401
+from .mix import (argsort_keys_dev, draw_permutation, draw_permutation_dev, mix_batch, mix_batch_dev)  # noqa: F401
 from .scan import (scan_bytes_batch, scan_bytes_batch_dev, scan_bytes_packed_batch,  # noqa: F401
                    scan_bytes_packed_batch_dev)
 from .packed import (decrypt_packed_batch, decrypt_packed_batch_dev, pack_rows, sum_groups_packed,  # noqa: F401

@@ -22,6 +22,9 @@
 //   scan_hits.hip            scanning a batch for the rows a key decrypts to a well-formed, tagged message: decrypt and rows_to_bytes as
 //                            they are, then mark / offsets / emit kernels that compact the hits on the device (kernels, *_dev and
 //                            host-pointer entry points)
+//   permutation.hip          the order of a mix step drawn on the device: ChaCha20 sort keys (k_perm_keys), a stable radix argsort without
+//                            global atomics (k_perm_hist / k_perm_offsets / k_perm_scatter per byte, k_perm_finish), and a whole mix step
+//                            from a key: sample r, draw the order, re-encrypt (kernels, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H
@@ -213,6 +216,19 @@ NTRU_HIDDEN int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, i
 // ---- packed rows (packed_ciphertexts.hip) -----------------------------------------------------------------------------------------------
 // Enqueues k_unpack_rows: B rows of packOutput(q - 1, N, e) -> dense uint16_t [B][N] (scan_hits.hip unpacks a pass with it).
 NTRU_HIDDEN int ntru_launch_unpack_rows(ntru_engine *eng, int N, int q, const uint64_t *d_packed, int64_t B, uint16_t *d_rows);
+
+// ---- re-randomising from host pointers (matrix_reencrypt.hip) -------------------------------------------------------------------------------
+// Where the rows of r come from when the caller does not supply them: row i is row 0 of ntru_sample_ternary_dev(N, n1, n2, other, key,
+// first_item + i, 1), drawn on the device; r_out (host, [B][N], may be NULL) receives them.
+struct ReencryptDraw {
+  const uint32_t *key;
+  uint64_t first_item;
+  int n1, n2, other;
+  uint8_t *r_out;
+};
+// The body of ntru_reencrypt_batch; with r == NULL the rows of r come from `draw` (ntru_mix_batch, permutation.hip).
+NTRU_HIDDEN int ntru_reencrypt_host(ntru_engine *eng, int N, int q, const uint16_t *h, const uint8_t *r, const ReencryptDraw *draw,
+                                    const uint16_t *e_in, int64_t B_in, const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE);
 
 // ---- host-pointer entry points (ntru_host.hip; keygen_batch, ciphertext_sum, message_bytes) --------------------------------------------------------------
 // True when `p` points into memory HIP knows as pinned host memory (hipHostMalloc / hipHostRegister).

@@ -114,10 +114,12 @@ extern "C" int ntru_reencrypt_batch_dev(ntru_engine_t *eng, int N, int q, const 
 }
 
 // The host form gathers the rows while it fills the staging buffers (one chunk's rows at a time), so the device sees src == NULL.
-extern "C" int ntru_reencrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint16_t *e_in,
-                                    int64_t B_in, const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE) {
+// r == NULL (ntru_mix_batch, permutation.hip): row i of r is drawn on the device, chunk by chunk, as row 0 of
+// ntru_sample_ternary_dev(N, n1, n2, other, key, first_item + i, 1); it never goes up and comes down only when draw->r_out is given.
+int ntru_reencrypt_host(ntru_engine *eng, int N, int q, const uint16_t *h, const uint8_t *r, const ReencryptDraw *draw, const uint16_t *e_in,
+                        int64_t B_in, const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE) {
   bool done;
-  if (int rc = check_reencrypt(eng, N, q, h, r, e_in, B_in, src, B, e_out, &done)) return rc;
+  if (int rc = check_reencrypt(eng, N, q, h, r ? (const void *)r : (const void *)draw, e_in, B_in, src, B, e_out, &done)) return rc;
   if (done) return NTRU_OK;
   if (src)
     for (int64_t i = 0; i < B; i++)
@@ -132,13 +134,24 @@ extern "C" int ntru_reencrypt_batch(ntru_engine_t *eng, int N, int q, const uint
     if (src)
       for (int64_t i = 0; i < n; i++) memcpy(gathered.data() + (size_t)i * N, e_in + (size_t)src[o + i] * N, row);
     Pipeline P(eng);
-    const int ih = P.in(h, row, true), ir = P.in(r + o * N, N), ie = P.in(src ? gathered.data() : e_in, row);
+    const int ih = P.in(h, row, true);
+    const int ir = r ? P.in(r + o * N, N) : (draw->r_out ? P.out(draw->r_out + o * N, N) : P.tmp(N));
+    const int ie = P.in(src ? gathered.data() : e_in, row);
     const int io = P.out(e_out + o * N, row), iq = P.out(quotE ? quotE + o * N : nullptr, row);
-    const int rc = P.run(n, C, [&](int64_t, int64_t cnt, void **d) {
+    const int rc = P.run(n, C, [&](int64_t first, int64_t cnt, void **d) {
+      if (!r)
+        if (int rs = ntru_sample_ternary_dev(eng, N, draw->n1, draw->n2, draw->other, draw->key, draw->first_item + (uint64_t)(o + first), cnt,
+                                             (uint8_t *)d[ir]))
+          return rs;
       return ntru_reencrypt_batch_dev(eng, N, q, (const uint16_t *)d[ih], (const uint8_t *)d[ir], (const uint16_t *)d[ie], cnt, nullptr, cnt,
                                       (uint16_t *)d[io], (uint16_t *)d[iq]);
     });
     if (rc) return rc;
   }
   return NTRU_OK;
+}
+
+extern "C" int ntru_reencrypt_batch(ntru_engine_t *eng, int N, int q, const uint16_t *h, const uint8_t *r, const uint16_t *e_in,
+                                    int64_t B_in, const int64_t *src, int64_t B, uint16_t *e_out, uint16_t *quotE) {
+  return ntru_reencrypt_host(eng, N, q, h, r, nullptr, e_in, B_in, src, B, e_out, quotE);
 }

@@ -95,6 +95,10 @@ _SIGS = {
     **_both("ntru_decrypt_packed_batch", "p iii ppp l pppp"),
     # re-randomising and shuffling under the shared public key: the functions are in mix.py
     **_both("ntru_reencrypt_batch", "p ii ppp l p l pp"),
+    # the order of a mix step drawn on the device, and a whole mix step from a key: also in mix.py
+    "ntru_argsort_keys_dev": _sig("p p l p"),
+    **_both("ntru_draw_permutation", "p p u l pp"),
+    **_both("ntru_mix_batch", "p iii pp u ii u p l pppp"),
     # scanning a batch for the rows a key decrypts to a tagged message: the functions are in scan.py
     **_both("ntru_scan_bytes_batch", "p iiiii ppp l ii p l ppp"),
     **_both("ntru_scan_bytes_packed_batch", "p iiiii ppp l ii p l ppp"),

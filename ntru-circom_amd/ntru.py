@@ -517,6 +517,17 @@ class NTRU:
         value, quot = mix_calls.reencrypt_batch(self.engine, N, q, expandArray(self.h, N), r, e % q, src=src, want_quot=wantWitness)
         return {"value": value, "r": r, "m": m, "quotientE": quot}
 
+    def mixBatch(self, e, key, firstItem=0, permId=0, wantWitness=True):
+        """One mix step of the ciphertexts `e` [B][N] from a ChaCha20 key (8 words): r[i] is row firstItem + i of the on-device sampler
+        (dr ones, dr entries p - 1), src the permutation drawn on the device under (key, permId), output row i is
+        (Enc(0; r[i]) + e[src[i]]) mod q.  Returns {"value", "r", "m", "src", "quotientE"}: m is the gathered rows, and
+        {r, m, h, quotientE, remainderE: value} satisfies VerifyEncrypt (quotientE is None without wantWitness)."""
+        N, q, p = self.N, self.q, self.p
+        e = np.ascontiguousarray(np.asarray(e).reshape(-1, N) % q).astype(np.uint16)
+        value, quot, r, src = mix_calls.mix_batch(self.engine, N, q, p, expandArray(self.h, N), key, firstItem, self.dr, self.dr, permId, e,
+                                                  want_quot=wantWitness)
+        return {"value": value, "r": r, "m": e[src], "src": src, "quotientE": quot}
+
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
         """h = trim((p*fq mod q) * g mod (x^N - 1, q)) on the device."""
