@@ -16,9 +16,9 @@
 // [A | alpha A] x [lo ; beta hi], alpha beta = 128.  LDS images: operand stages [32 rows][pitchA] (ds_read_b128, pitch an
 // odd multiple of 16 bytes), key arrays reversed and cyclic, rev[y] = digit(sc[(32 NT - 1 - y) mod N]), in 4 byte-shifted
 // copies so that a lane's 16-byte Toeplitz fragment (which starts at an arbitrary byte) is 4 aligned dwords; each of the
-// 4 waves owns strips of <= 4 column tiles, its fragment window slides by one tile per contraction step (one new
-// fragment per step).  tools/mfma_model.py is the executable specification; profiles/archive/r01_microbench_mfma_lds.txt holds
-// the measurements behind the layout choices.
+// 4 waves owns strips of <= 4 column tiles, its fragment window advances by one tile per contraction step (one new
+// fragment per step, into the slot that fell out: no register moves, see toeplitz_strip).  tools/mfma_model.py is the
+// executable specification; profiles/archive/r01_microbench_mfma_lds.txt holds the measurements behind the layout choices.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned int v2u __attribute__((__vector_size__(2 * sizeof(unsigned int))));
@@ -148,75 +148,49 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, w0, zero, 0, 0, 0);
     if (TWO) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, w1, acc, 0, 0, 0);
   };
-  // Fragment window: at a step boundary slot t holds the fragment of tile t ("canonical").  A block of NT_S steps
-  // rotates through the slots with compile-time indices (no register moves) and ends canonical again: at sub-step u tile t
-  // uses slot (t - u) mod NT_S, and the fragment needed next replaces the one tile NT_S-1 just used.  Left-over steps
-  // slide the window physically.  The next operand fragment is requested before the current step's products.
-#pragma unroll
-  for (int t = 0; t < NT_S; t++) load_w(kb0 + t, W0[t], W1[t]);
+  // Fragment window: NT_S slots, rotated through with compile-time indices (no register moves).  Sub-step u of a block:
+  // tile t uses slot (t - u) mod NT_S, and the fragment needed next replaces the one tile NT_S-1 just used.  The window is
+  // "canonical" (slot t holds the fragment of tile t) where u = 0, so a block of NT_S steps starts and ends canonical.  The
+  // steps that do not fill a block never slide the window physically either: the ones above the diagonal come FIRST, as the
+  // last sub-steps NT_S - s .. NT_S - 1 of a block whose window is loaded already rotated (so they end canonical), and the
+  // ones below the diagonal come last, as the first sub-steps of a block after which the window is dead.  The next operand
+  // fragment is requested before the current step's products.
   u32 mhigh[4];
 #pragma unroll
   for (int c = 0; c < 4; c++) mhigh[c] = ~mlow[c];
   v4i a0, a1;
   load_a(0, a0, a1);
   unpack_a(a0, a1);
-  // kind: 0 = all tiles low, 1 = all high, 2 = the strip's own (diagonal) steps
-  auto block = [&](int ib, auto kind) {
-#pragma unroll
-    for (int u = 0; u < NT_S; u++) {
-      v4i n0, n1;
-      load_a(ib + u + 1, n0, n1);
-      // Tile 0 works on the fragment that was requested at the end of the sub-step before (slot (NT_S - u) % NT_S): it goes LAST, so
-      // that the read has the other tiles' matrix instructions to land behind (as the first it exposed an LDS round trip per sub-step).
-#pragma unroll
-      for (int tt = 1; tt <= NT_S; tt++) {
-        const int t = tt % NT_S;
-        constexpr int K = decltype(kind)::value;
-        const int sl = (t - u + NT_S) % NT_S;
-        if (K == 0 || (K == 2 && t > u)) mm(accL[t], a0, a1, W0[sl], W1[sl]);
-        else if (K == 1 || (K == 2 && t < u)) mm(accH[t], a0, a1, W0[sl], W1[sl]);
-        else {
-          mm(accL[t], a0, a1, and4(W0[sl], mlow), and4(W1[sl], mlow));
-          mm_first(accH[t], a0, a1, and4(W0[sl], mhigh), and4(W1[sl], mhigh));   // t == u: the first term of `high`
-        }
-      }
-      load_w(kb0 - (ib + u + 1), W0[(NT_S - 1 - u) % NT_S], W1[(NT_S - 1 - u) % NT_S]);
-      if (decltype(kind)::value == 2) diag(u);
-      a0 = n0; a1 = n1;
-      unpack_a(a0, a1);
-    }
-  };
-  auto single = [&](int ib, v16i (&acc)[NT_S]) {
+  // One contraction step ib as sub-step u (a constant once unrolled).  kind: 0 = all tiles low, 1 = all high, 2 = the
+  // strip's own (diagonal) steps; first: the first touch of every `low`.
+  auto step = [&](int ib, int u, auto kind, auto first) __attribute__((always_inline)) {
+    constexpr int K = decltype(kind)::value;
     v4i n0, n1;
     load_a(ib + 1, n0, n1);
+    // Tile 0 works on the fragment that was requested at the end of the sub-step before (slot (NT_S - u) % NT_S): it goes LAST, so
+    // that the read has the other tiles' matrix instructions to land behind (as the first it exposed an LDS round trip per sub-step).
 #pragma unroll
-    for (int t = 0; t < NT_S; t++) mm(acc[t], a0, a1, W0[t], W1[t]);
-#pragma unroll
-    for (int t = NT_S - 1; t > 0; t--) { W0[t] = W0[t - 1]; W1[t] = W1[t - 1]; }
-    load_w(kb0 - (ib + 1), W0[0], W1[0]);
+    for (int tt = 1; tt <= NT_S; tt++) {
+      const int t = tt % NT_S;
+      const int sl = (t - u + NT_S) % NT_S;
+      if (K == 0 && decltype(first)::value) mm_first(accL[t], a0, a1, W0[sl], W1[sl]);
+      else if (K == 0 || (K == 2 && t > u)) mm(accL[t], a0, a1, W0[sl], W1[sl]);
+      else if (K == 1 || (K == 2 && t < u)) mm(accH[t], a0, a1, W0[sl], W1[sl]);
+      else {
+        mm(accL[t], a0, a1, and4(W0[sl], mlow), and4(W1[sl], mlow));
+        mm_first(accH[t], a0, a1, and4(W0[sl], mhigh), and4(W1[sl], mhigh));   // t == u: the first term of `high`
+      }
+    }
+    load_w(kb0 - (ib + 1), W0[(NT_S - 1 - u) % NT_S], W1[(NT_S - 1 - u) % NT_S]);
+    if (K == 2) diag(u);
     a0 = n0; a1 = n1;
     unpack_a(a0, a1);
   };
-  int ib = 0;
+  auto block = [&](int ib, auto kind) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < NT_S; u++) step(ib + u, u, kind, std::false_type{});
+  };
   bool paused = false;
-  if (kb0 > 0 && g.NT > 0) {                              // contraction step 0: the first term of every `low`
-    if (!std::is_same<Pause, NoPause>::value && pause_ib <= 0) { pause(); paused = true; load_a(0, a0, a1); unpack_a(a0, a1); }
-    v4i n0, n1;
-    load_a(1, n0, n1);
-#pragma unroll
-    for (int t = 0; t < NT_S; t++) mm_first(accL[t], a0, a1, W0[t], W1[t]);
-#pragma unroll
-    for (int t = NT_S - 1; t > 0; t--) { W0[t] = W0[t - 1]; W1[t] = W1[t - 1]; }
-    load_w(kb0 - 1, W0[0], W1[0]);
-    a0 = n0; a1 = n1;
-    unpack_a(a0, a1);
-    ib = 1;
-  } else {                                               // the diagonal block comes first (or a timing-only build)
-#pragma unroll
-    for (int t = 0; t < NT_S; t++)
-#pragma unroll
-      for (int i = 0; i < 16; i++) accL[t][i] = 0;
-  }
   auto maybe_pause = [&](int first, int last) {          // the steps first .. last are what the next block touches
     if (!std::is_same<Pause, NoPause>::value && !paused && last >= pause_ib) {
       __builtin_amdgcn_s_setprio(0);
@@ -227,13 +201,43 @@ static __device__ __forceinline__ void toeplitz_strip(const unsigned char *__res
       unpack_a(a0, a1);
     }
   };
-  __builtin_amdgcn_s_setprio(3);       // the partner wave on this SIMD is usually in a VALU phase: decrypt -3 %
-  for (; ib + NT_S <= kb0; ib += NT_S) { maybe_pause(ib, ib + NT_S - 1); block(ib, std::integral_constant<int, 0>{}); }   // above the diagonal: low
-  for (; ib < kb0; ib++) { maybe_pause(ib, ib); single(ib, accL); }
+  // Above the diagonal there are kb0 steps.  The first s = kb0 mod NT_S of them (a whole block when s = 0) enter the block at
+  // sub-step u0 = (NT_S - s) mod NT_S: the window is loaded rotated by u0, and contraction step 0 is the first term of every `low`.
+  const bool lead = kb0 > 0 && g.NT > 0;                 // otherwise the diagonal block comes first (or a timing-only build)
+  const int u0 = lead ? (NT_S - kb0 % NT_S) % NT_S : 0;
+  if (lead) maybe_pause(0, NT_S - 1 - u0);
+#pragma unroll
+  for (int k = 0; k < NT_S; k++)
+    if (u0 == k) {
+#pragma unroll
+      for (int j = 0; j < NT_S; j++) load_w(kb0 + (j + k) % NT_S, W0[j], W1[j]);
+      if (k > 0 || lead) step(0, k, std::integral_constant<int, 0>{}, std::true_type{});
+    }
+  int ib = 0;
+  if (lead) {
+#pragma unroll
+    for (int u = 1; u < NT_S; u++)
+      if (u > u0) step(u - u0, u, std::integral_constant<int, 0>{}, std::false_type{});
+    ib = NT_S - u0;
+  } else {
+#pragma unroll
+    for (int t = 0; t < NT_S; t++)
+#pragma unroll
+      for (int i = 0; i < 16; i++) accL[t][i] = 0;
+  }
+  // The partner wave on this SIMD is usually in a VALU phase: decrypt -3 %.  Raised only behind the leading steps: with the window
+  // loads and those steps at priority 3 too, k_encrypt_md measured 2 % slower (profiles/r08_strip_leftovers.txt).
+  __builtin_amdgcn_s_setprio(3);
+  for (; ib < kb0; ib += NT_S) { maybe_pause(ib, ib + NT_S - 1); block(ib, std::integral_constant<int, 0>{}); }   // above the diagonal: low
   maybe_pause(kb0, kb0 + NT_S - 1);
   block(kb0, std::integral_constant<int, 2>{});                                        // ib = kb0 .. kb0 + NT_S - 1
   for (ib = kb0 + NT_S; ib + NT_S <= g.NT; ib += NT_S) { maybe_pause(ib, ib + NT_S - 1); block(ib, std::integral_constant<int, 1>{}); }   // below: high
-  for (; ib < g.NT; ib++) { maybe_pause(ib, ib); single(ib, accH); }
+  if (ib < g.NT) {                                       // what is left below: the first sub-steps of a block
+    maybe_pause(ib, g.NT - 1);
+#pragma unroll
+    for (int u = 0; u + 1 < NT_S; u++)
+      if (ib + u < g.NT) step(ib + u, u, std::integral_constant<int, 1>{}, std::false_type{});
+  }
   __builtin_amdgcn_s_setprio(0);
   if (!std::is_same<Pause, NoPause>::value && !paused) pause();
   STAMP(stamp_base);
