@@ -265,11 +265,12 @@ static __device__ __forceinline__ void pi_for_split(const v16i *L, const v16i *H
 
 // index.js:159: a remainder is invalid iff it has a non-zero coefficient above the constant one AND its constant one is not 1
 // (length !== 1 && [0] !== 1).  Register i of lane kl = pi_index_of(lane) holds index ko_i + kl: it exists iff ko_i < N - kl (one compare
-// against a per-lane limit, ko_i a constant); coefficient 0 is register 0 of lane 0.
+// against a per-lane limit, ko_i a constant); coefficient 0 is register 0 of lane 0.  Register 0 is no exception to the limit: below
+// N = 160 the lanes kl = 128 .. 159 hold indices at and beyond N there (tiles >= NT: junk that must not count).
 struct PiNotOne {
   u32 any_hi = 0, c0 = 0;
   __device__ __forceinline__ void see(int i, int ko, int kl, int N, u32 rv) {
-    if (i == 0) { c0 = rv; any_hi |= kl == 0 ? 0u : rv; }
+    if (i == 0) { c0 = rv; any_hi |= kl == 0 || kl >= N ? 0u : rv; }
     else any_hi |= ko < N - kl ? rv : 0u;
   }
   __device__ __forceinline__ bool invalid(int kl) const {                   // wave-wide
