@@ -35,8 +35,6 @@
 #include "kernels_common.h"
 #include "sum_groups_common.h"
 
-typedef unsigned long long u64;
-
 namespace {
 
 constexpr int SG_THREADS = 256;          // four independent waves
@@ -45,7 +43,6 @@ constexpr int SG_WAVES_PER_CU = 8;
 constexpr int FIN_COLS = 32, FIN_SLICES = 32;   // k_sum_groups_finish: 1024 threads = 32 columns x 32 slices of the partial list
 constexpr int FIN_Y = 32;
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef u32 u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
@@ -253,24 +250,14 @@ namespace {
 
 // Enqueues the sums of the groups `w` of the dense rows at d_rows (row w.wlo first) into d_out (group 0 of w first).
 int launch_sum(ntru_engine *eng, int N, int mod, const void *d_rows, const uint16_t *d_weights, const SumWindow &w, uint16_t *d_out) {
-  HIP_TRY(hipSetDevice(eng->device));
-  const int NT = (N + SG_TILE - 1) / SG_TILE;
-  const long Pb = sum_row_blocks(eng, NT, SG_WAVES_PER_CU, w);
-  ScratchHold hold(eng, (size_t)Pb * 8 + (size_t)Pb * 2 * N * 4);
-  if (hold.rc) return hold.rc;
-  long *meta = (long *)hold.p;
-  u32 *part = (u32 *)(hold.p + (size_t)Pb * 8);
-  const Groups gr = groups_of(w);
   const bool pow2 = is_pow2(mod);
-  const dim3 grid((unsigned)((Pb * NT + SG_THREADS / 64 - 1) / (SG_THREADS / 64)));
-#define SG_LAUNCH(P2, WT)                                                                                                              \
-  hipLaunchKernelGGL((k_sum_groups<P2, WT>), grid, dim3(SG_THREADS), 0, eng->stream, N, (u32)mod, gr, (const u16 *)d_rows, d_weights, NT, \
-                     Pb, part, meta, d_out)
-  if (pow2) { if (d_weights) SG_LAUNCH(true, true); else SG_LAUNCH(true, false); }
-  else { if (d_weights) SG_LAUNCH(false, true); else SG_LAUNCH(false, false); }
-#undef SG_LAUNCH
-  HIP_TRY(hipGetLastError());
-  if (int rc = ntru_launch_sum_finish(eng, N, mod, w, Pb, part, meta, d_out)) return rc;
+  auto enqueue = [&](dim3 grid, const Groups &gr, int NT, long Pb, u32 *part, long *meta) {
+    sum_variant(pow2, d_weights != nullptr, [&](auto p2, auto wt) {
+      hipLaunchKernelGGL((k_sum_groups<decltype(p2)::value, decltype(wt)::value>), grid, dim3(SG_THREADS), 0, eng->stream, N, (u32)mod, gr,
+                         (const u16 *)d_rows, d_weights, NT, Pb, part, meta, d_out);
+    });
+  };
+  if (int rc = launch_sum_rows(eng, N, mod, w, (N + SG_TILE - 1) / SG_TILE, SG_WAVES_PER_CU, SG_THREADS, d_out, enqueue)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sum_groups<%d,%d>", (int)pow2, d_weights ? 1 : 0);
   return NTRU_OK;
 }
@@ -306,12 +293,10 @@ extern "C" int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, in
                                             const uint16_t *d_rows, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K,
                                             int64_t G, uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
                                             uint8_t *d_quot2) {
-  if (int rc = ntru_check_sum_args(eng, N, q, !d_offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
-  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (G == 0) return NTRU_OK;
-  if (!d_f || !d_fp || !d_rows || !d_sum || !d_value) return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_batch: NULL buffer (d_sum is needed as the intermediate)");
-  if (int rc = ntru_sum_groups_dev(eng, N, q, d_rows, d_weights, d_offsets, K, G, d_sum)) return rc;
-  return ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_sum, G, d_value, d_quot1, d_rem1, d_quot2);
+  return tally_decrypt(
+      eng, "ntru_tally_decrypt_batch", N, q, p, !d_offsets, K, G, d_f && d_fp && d_rows && d_sum && d_value, "d_sum",
+      [&] { return ntru_sum_groups_dev(eng, N, q, d_rows, d_weights, d_offsets, K, G, d_sum); },
+      [&] { return ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_sum, G, d_value, d_quot1, d_rem1, d_quot2); });
 }
 
 // ---- host-pointer forms -------------------------------------------------------------------------------------------------------------
@@ -387,10 +372,8 @@ extern "C" int ntru_sum_groups(ntru_engine_t *eng, int N, int mod, const uint16_
 extern "C" int ntru_tally_decrypt_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
                                         const uint16_t *rows, const uint16_t *weights, const int64_t *offsets, int64_t K, int64_t G,
                                         uint16_t *sum, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
-  if (int rc = ntru_check_sum_args(eng, N, q, !offsets, K, G, "ntru_tally_decrypt_batch")) return rc;
-  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (G == 0) return NTRU_OK;
-  if (!f || !fp || !sum || !value) return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_batch: NULL buffer (sum is needed as the intermediate)");
-  if (int rc = ntru_sum_groups(eng, N, q, rows, weights, offsets, K, G, sum)) return rc;
-  return ntru_decrypt_batch(eng, N, q, p, f, fp, sum, G, value, quot1, rem1, quot2);
+  return tally_decrypt(                                  // (rows is tested by ntru_sum_groups_host, once it knows that there are rows)
+      eng, "ntru_tally_decrypt_batch", N, q, p, !offsets, K, G, f && fp && sum && value, "sum",
+      [&] { return ntru_sum_groups(eng, N, q, rows, weights, offsets, K, G, sum); },
+      [&] { return ntru_decrypt_batch(eng, N, q, p, f, fp, sum, G, value, quot1, rem1, quot2); });
 }

@@ -204,7 +204,8 @@ typedef int (*ntru_sum_launcher)(ntru_engine *eng, int N, int mod, const void *d
                                  uint16_t *d_out);
 // the domain and argument checks of ntru_sum_groups under the name `who`
 NTRU_HIDDEN int ntru_check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t K, int64_t G, const char *who);
-// k_sum_groups_finish on the partial rows a row kernel left for Pb row blocks (sum_groups_common.h); nothing to do for Pb == 1
+// k_sum_groups_finish on the partial rows a row kernel left for Pb row blocks, in the scratch that launch_sum_rows sized and carved
+// (sum_groups_common.h: the one launcher of both row kernels; the body of the four tally calls is there too); nothing to do for Pb == 1
 NTRU_HIDDEN int ntru_launch_sum_finish(ntru_engine *eng, int N, int mod, const SumWindow &w, long Pb, const uint32_t *d_part,
                                        const long *d_meta, uint16_t *d_out);
 // The host-pointer form of a sum: validates offsets and weights, streams the rows (row_bytes each) through the chunked pipeline, one

@@ -43,7 +43,6 @@ constexpr int SP_WAVES_PER_CU = 8;
 constexpr int SP_BATCH = 4;              // row steps in flight
 constexpr int PK_PASS = 65536;           // rows per pass of the calls that unpack into scratch
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_a8 __attribute__((aligned(8)));
 
 // How a lane sees an element of BITS-wide fields.
@@ -214,36 +213,27 @@ int pack_shape(int mod, int N, PackShape *ps) {
 int launch_sum_packed(ntru_engine *eng, int N, int mod, const void *d_packed, const uint16_t *d_weights, const SumWindow &w, uint16_t *d_out) {
   PackShape ps;
   if (int rc = pack_shape(mod, N, &ps)) return rc;
-  HIP_TRY(hipSetDevice(eng->device));
-  const int U = ps.os * slices_of(ps.bits), NT = U <= 64 ? 1 : (U + 63) / 64;
-  const long Pb = sum_row_blocks(eng, NT, SP_WAVES_PER_CU, w);
-  ScratchHold hold(eng, (size_t)Pb * 8 + (size_t)Pb * 2 * N * 4);
-  if (hold.rc) return hold.rc;
-  long *meta = (long *)hold.p;
-  u32 *part = (u32 *)(hold.p + (size_t)Pb * 8);
-  const Groups gr = groups_of(w);
-  const bool pow2 = is_pow2(mod);
-  const dim3 grid((unsigned)((Pb * NT + SP_THREADS / 64 - 1) / (SP_THREADS / 64)));
-#define SP_LAUNCH(BITS, P2, WT)                                                                                                   \
-  hipLaunchKernelGGL((k_sum_groups_packed<BITS, P2, WT>), grid, dim3(SP_THREADS), 0, eng->stream, N, (u32)mod, gr, (const u32 *)d_packed, \
-                     d_weights, ps.os, NT, Pb, part, meta, d_out)
-#define SP_CASE(BITS)                                                                       \
-  case BITS:                                                                                \
-    if (pow2) { if (d_weights) SP_LAUNCH(BITS, true, true); else SP_LAUNCH(BITS, true, false); } \
-    else { if (d_weights) SP_LAUNCH(BITS, false, true); else SP_LAUNCH(BITS, false, false); }    \
-    break;
-  switch (ps.bits) {
-    case 1:                                             // mod = 2: a power of two
-      if (d_weights) SP_LAUNCH(1, true, true); else SP_LAUNCH(1, true, false);
-      break;
-    SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6) SP_CASE(7) SP_CASE(8) SP_CASE(9) SP_CASE(10) SP_CASE(11) SP_CASE(12) SP_CASE(13)
-    SP_CASE(14) SP_CASE(15) SP_CASE(16)
-    default: return fail(NTRU_ERR_ARG, "ntru_sum_groups_packed: no kernel for fields of " + std::to_string(ps.bits) + " bits");
-  }
+  if (ps.bits < 1 || ps.bits > 16) return fail(NTRU_ERR_ARG, "ntru_sum_groups_packed: no kernel for fields of " + std::to_string(ps.bits) + " bits");
+  const int U = ps.os * slices_of(ps.bits);
+  const bool pow2 = is_pow2(mod), weighted = d_weights != nullptr;
+  auto enqueue = [&](dim3 grid, const Groups &gr, int NT, long Pb, u32 *part, long *meta) {
+    auto go = [&](auto bits, auto p2, auto wt) {
+      hipLaunchKernelGGL((k_sum_groups_packed<decltype(bits)::value, decltype(p2)::value, decltype(wt)::value>), grid, dim3(SP_THREADS), 0,
+                         eng->stream, N, (u32)mod, gr, (const u32 *)d_packed, d_weights, ps.os, NT, Pb, part, meta, d_out);
+    };
+#define SP_CASE(BITS) \
+  case BITS: sum_variant(pow2, weighted, [&](auto p2, auto wt) { go(std::integral_constant<int, BITS>{}, p2, wt); }); break;
+    switch (ps.bits) {
+      case 1:                                           // mod = 2: a power of two
+        weighted ? go(std::integral_constant<int, 1>{}, std::true_type{}, std::true_type{})
+                 : go(std::integral_constant<int, 1>{}, std::true_type{}, std::false_type{});
+        break;
+      SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6) SP_CASE(7) SP_CASE(8) SP_CASE(9) SP_CASE(10) SP_CASE(11) SP_CASE(12) SP_CASE(13)
+      SP_CASE(14) SP_CASE(15) SP_CASE(16)
+    }
 #undef SP_CASE
-#undef SP_LAUNCH
-  HIP_TRY(hipGetLastError());
-  if (int rc = ntru_launch_sum_finish(eng, N, mod, w, Pb, part, meta, d_out)) return rc;
+  };
+  if (int rc = launch_sum_rows(eng, N, mod, w, U <= 64 ? 1 : (U + 63) / 64, SP_WAVES_PER_CU, SP_THREADS, d_out, enqueue)) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sum_groups_packed<%d,%d,%d>", ps.bits, (int)pow2, d_weights ? 1 : 0);
   return NTRU_OK;
 }
@@ -286,25 +276,19 @@ extern "C" int ntru_tally_decrypt_packed_batch_dev(ntru_engine_t *eng, int N, in
                                                    const uint64_t *d_packed, const uint16_t *d_weights, const int64_t *d_offsets,
                                                    int64_t K, int64_t G, uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1,
                                                    uint16_t *d_rem1, uint8_t *d_quot2) {
-  if (int rc = ntru_check_sum_args(eng, N, q, !d_offsets, K, G, "ntru_tally_decrypt_packed_batch")) return rc;
-  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (G == 0) return NTRU_OK;
-  if (!d_f || !d_fp || !d_packed || !d_sum || !d_value)
-    return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_packed_batch: NULL buffer (d_sum is needed as the intermediate)");
-  if (int rc = ntru_sum_groups_packed_dev(eng, N, q, d_packed, d_weights, d_offsets, K, G, d_sum)) return rc;
-  return ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_sum, G, d_value, d_quot1, d_rem1, d_quot2);
+  return tally_decrypt(
+      eng, "ntru_tally_decrypt_packed_batch", N, q, p, !d_offsets, K, G, d_f && d_fp && d_packed && d_sum && d_value, "d_sum",
+      [&] { return ntru_sum_groups_packed_dev(eng, N, q, d_packed, d_weights, d_offsets, K, G, d_sum); },
+      [&] { return ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_sum, G, d_value, d_quot1, d_rem1, d_quot2); });
 }
 
 extern "C" int ntru_tally_decrypt_packed_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp,
                                                const uint64_t *packed, const uint16_t *weights, const int64_t *offsets, int64_t K,
                                                int64_t G, uint16_t *sum, uint8_t *value, uint16_t *quot1, uint16_t *rem1, uint8_t *quot2) {
-  if (int rc = ntru_check_sum_args(eng, N, q, !offsets, K, G, "ntru_tally_decrypt_packed_batch")) return rc;
-  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
-  if (G == 0) return NTRU_OK;
-  if (!f || !fp || !sum || !value)
-    return fail(NTRU_ERR_ARG, "ntru_tally_decrypt_packed_batch: NULL buffer (sum is needed as the intermediate)");
-  if (int rc = ntru_sum_groups_packed(eng, N, q, packed, weights, offsets, K, G, sum)) return rc;
-  return ntru_decrypt_batch(eng, N, q, p, f, fp, sum, G, value, quot1, rem1, quot2);
+  return tally_decrypt(                                  // (packed is tested by ntru_sum_groups_host, once it knows that there are rows)
+      eng, "ntru_tally_decrypt_packed_batch", N, q, p, !offsets, K, G, f && fp && sum && value, "sum",
+      [&] { return ntru_sum_groups_packed(eng, N, q, packed, weights, offsets, K, G, sum); },
+      [&] { return ntru_decrypt_batch(eng, N, q, p, f, fp, sum, G, value, quot1, rem1, quot2); });
 }
 
 // Rows are unpacked into the engine-owned scratch buffer, in passes of at most PK_PASS rows (its size is bounded in B), and are still on

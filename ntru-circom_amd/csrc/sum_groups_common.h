@@ -1,6 +1,6 @@
 // sum_groups_common.h -- what the kernels that sum rows in groups share (ciphertext_sum.hip: dense rows; packed_ciphertexts.hip: rows of
-// packed field elements): the groups of one launch, their cut into row blocks, and the layout of the partial rows that
-// k_sum_groups_finish completes.
+// packed field elements): the groups of one launch, their cut into row blocks, the layout of the partial rows that
+// k_sum_groups_finish completes, the launcher that sizes and carves the scratch for them, and the body of the tally calls.
 //
 // A launch covers the rows [first offset, last offset), cut into Pb equal ROW BLOCKS.  A group that crosses a block boundary leaves one
 // partial row per block it meets in `part` (u32 [Pb][2][N]): slot 0 of a block for the group that entered through the block's start,
@@ -16,6 +16,7 @@
 #include "kernels_common.h"
 
 typedef unsigned long long u64;
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -59,17 +60,48 @@ inline Groups groups_of(const SumWindow &w) {
   return gr;
 }
 
-// Row blocks of a launch whose row needs `tiles` wavefronts: from the grid (waves_per_cu x CUs), and for uniform groups, whose row
-// count the host knows, no more than there are rows.
-inline long sum_row_blocks(const ntru_engine *eng, int tiles, int waves_per_cu, const SumWindow &w) {
-  long pb = (long)eng->cus * waves_per_cu / tiles;
-  pb = pb < 1 ? 1 : (pb > 32768 ? 32768 : pb);
+// Enqueues the sums of the groups `w` into d_out: a row kernel whose row needs `tiles` wavefronts of workgroups of `threads`, through
+// enqueue(grid, Groups, tiles, Pb, part, meta), then k_sum_groups_finish.  The scratch is [Pb] long meta | [Pb][2][N] u32 part.
+template <class Enqueue>
+int launch_sum_rows(ntru_engine *eng, int N, int mod, const SumWindow &w, int tiles, int waves_per_cu, int threads, uint16_t *d_out,
+                    Enqueue enqueue) {
+  HIP_TRY(hipSetDevice(eng->device));
+  // row blocks: from the grid (waves_per_cu x CUs), and for uniform groups, whose row count the host knows, no more than there are rows
+  long Pb = (long)eng->cus * waves_per_cu / tiles;
+  Pb = Pb < 1 ? 1 : (Pb > 32768 ? 32768 : Pb);
   if (!w.off) {
     long T = std::min<long>(w.whi, (w.g0 + w.G) * w.K) - std::max<long>(w.wlo, w.g0 * w.K);
     if (T < 1) T = 1;
-    if (pb > T) pb = T;
+    if (Pb > T) Pb = T;
   }
-  return pb;
+  ScratchHold hold(eng, (size_t)Pb * 8 + (size_t)Pb * 2 * N * 4);
+  if (hold.rc) return hold.rc;
+  long *meta = (long *)hold.p;
+  u32 *part = (u32 *)(hold.p + (size_t)Pb * 8);
+  const dim3 grid((unsigned)((Pb * tiles + threads / 64 - 1) / (threads / 64)));
+  enqueue(grid, groups_of(w), tiles, Pb, part, meta);
+  HIP_TRY(hipGetLastError());
+  return ntru_launch_sum_finish(eng, N, mod, w, Pb, part, meta, d_out);
+}
+
+// f(power of two?, weighted?) with the two as std::integral_constant<bool>: the instantiations of a row kernel
+template <class F>
+void sum_variant(bool pow2, bool weighted, F f) {
+  if (pow2) weighted ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  else weighted ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+
+// The tally calls: the checks of the sum and of the decrypt, then sum() into the intermediate `inter` and decrypt() of it.  `buffers` is
+// false when a buffer that the two need is NULL.
+template <class Sum, class Decrypt>
+int tally_decrypt(ntru_engine *eng, const char *who, int N, int q, int p, bool uniform, int64_t K, int64_t G, bool buffers,
+                  const char *inter, Sum sum, Decrypt decrypt) {
+  if (int rc = ntru_check_sum_args(eng, N, q, uniform, K, G, who)) return rc;
+  if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr)) return rc;
+  if (G == 0) return NTRU_OK;
+  if (!buffers) return fail(NTRU_ERR_ARG, std::string(who) + ": NULL buffer (" + inter + " is needed as the intermediate)");
+  if (int rc = sum()) return rc;
+  return decrypt();
 }
 
 }  // namespace
