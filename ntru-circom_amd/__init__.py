@@ -2,7 +2,7 @@
 
 Layout
   csrc/abi.hip           engine life cycle + the *_dev entry points of the C ABI declared in include/ntru_engine.h
-  csrc/valu_families.hip, matrix_encrypt.hip, matrix_decrypt.hip, matrix_peritem.hip, keygen_sampler_pack.hip
+  csrc/valu_families.hip, matrix_encrypt.hip, matrix_decrypt.hip, matrix_peritem.hip, key_inversion.hip, ternary_sampler.hip, elementwise.hip
                          the HIP kernels (gfx950), one translation unit per kernel family (csrc/engine_internal.h lists them)
   csrc/ntru_host.hip     host-pointer entry points: pinned staging, three stage streams, chunked H2D / kernel / D2H pipeline
   csrc/ntru_generic.hip  reference-faithful generic family (arbitrary divisors, moduli up to 2^26, EEA, polyInv)

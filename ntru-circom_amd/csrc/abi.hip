@@ -1,6 +1,6 @@
 // abi.hip -- engine life cycle and the *_dev entry points of include/ntru_engine.h that choose between kernel families.  The kernels
 // and their launchers live in valu_families.hip, matrix_encrypt.hip, matrix_decrypt.hip, matrix_peritem.hip; the entry points of key
-// inversion, sampler, packing and the elementwise kernels are in keygen_sampler_pack.hip, the host-pointer forms in ntru_host.hip.
+// inversion, sampler, packing and the elementwise kernels are in key_inversion.hip, ternary_sampler.hip and elementwise.hip, the host-pointer forms in ntru_host.hip.
 //
 // No CPU fallback exists in this library: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>

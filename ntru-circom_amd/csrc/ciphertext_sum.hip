@@ -322,7 +322,7 @@ int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, cons
   const size_t out_row = (size_t)N * 2, out_bytes = (size_t)G * out_row;
   if (B == 0) { memset(out, 0, out_bytes); return NTRU_OK; }
   HIP_TRY(hipSetDevice(eng->device));
-  const size_t off_at = Pipeline::up(out_bytes), tmp_at = off_at + Pipeline::up(offsets ? (size_t)(G + 1) * 8 : 0);
+  const size_t off_at = ntru_up256(out_bytes), tmp_at = off_at + ntru_up256(offsets ? (size_t)(G + 1) * 8 : 0);
   if (int rc = ntru_grow_dev(&eng->shared_dev, tmp_at + out_row)) return rc;
   char *dev = (char *)eng->shared_dev.p;
   uint16_t *d_out = (uint16_t *)dev, *d_tmp = (uint16_t *)(dev + tmp_at);

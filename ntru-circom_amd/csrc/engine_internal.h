@@ -5,7 +5,10 @@
 //   matrix_encrypt.hip       family 4, encryptBits with a shared key on the int8 matrix cores (k_encrypt_m, k_encrypt_md)
 //   matrix_decrypt.hip       family 4, decryptBits with a shared key (k_decrypt_m, k_decrypt_m8)
 //   matrix_peritem.hip       family 4 with per-item operands (k_verify_keys_m, k_polymul_m, k_product_tern_m)
-//   keygen_sampler_pack.hip  key inversion, ternary sampler, field packing, elementwise kernels + their *_dev entry points
+//   key_inversion.hip        key inversion: k_invert_key, the Newton rounds around the per-item product kernels, ntru_invert_key_batch_dev
+//   ternary_sampler.hip      the on-device ternary sampler: k_sample_ternary for consecutive or listed stream positions, its launchers,
+//                            ntru_sample_ternary_dev
+//   elementwise.hip          split by I, add, field packing and unpacking (kernels and *_dev entry points), ntru_pack_params
 //   ntru_host.hip            host-pointer entry points: every regular one (its _dev form through the chunked H2D / kernel / D2H pipeline below,
 //                            from one description per call) with its ntru_multi_ form, ntru_pipeline_batch, device buffers; no kernels
 //   ntru_generic.hip         reference-faithful generic family (arbitrary divisors, moduli up to 2^26, signed coefficients)
@@ -131,6 +134,8 @@ struct ScratchHold {
 
 static inline int fail(int code, const std::string &msg) { return ntru_fail(code, msg); }
 static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+// Bytes rounded up to the 256-byte granule at which scratch, workspace and staging arrays are carved.
+static inline size_t ntru_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 // Workgroups of 256 for an elementwise kernel.  Kernels that move 16 bytes per lane and access (streaming = true) get TWO per CU: more
 // resident waves lower the HBM rate (the add of two ciphertext batches: 5.0 TB/s with 8 per CU, 5.9 with 2, 4.8 with 1:
 // profiles/archive/r03_ab_elementwise_grid.txt); element-per-lane kernels keep 8.
@@ -192,6 +197,11 @@ NTRU_HIDDEN int ntru_launch_verify_keys_valu(ntru_engine *eng, int N, int q, int
                                              uint16_t *d_quot_fq, uint16_t *d_rem_fq, uint8_t *d_quot_fp, uint8_t *d_rem_fp,
                                              uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags);
 
+// k_sample_ternary (ternary_sampler.hip) for the items d_idx[0 .. n) of a device list: compact row k is the row of stream position
+// pos_base + d_idx[k] under `key` (eight words).  Always ChaCha20; N + 1 < 2048.
+NTRU_HIDDEN int ntru_launch_sample_listed(ntru_engine *eng, int N, int n1, int n2, int other, const uint32_t *key, uint64_t pos_base,
+                                          const uint32_t *d_idx, int n, uint8_t *d_out);
+
 // ---- sums of rows in groups (ciphertext_sum.hip; packed_ciphertexts.hip sums packed rows through the same finish kernel and host form)
 // The groups of one launch as the host hands them on: off != NULL (DEVICE, G + 1 row indices): group g is rows [off[g], off[g + 1]);
 // else rows [(g0 + g) K, (g0 + g + 1) K); both clamped to the window [wlo, whi), whose first row is the first row of the array passed.
@@ -243,7 +253,6 @@ NTRU_HIDDEN int64_t ntru_chunk_items(int64_t B);
 // calls launch(first item, items, device pointers in declaration order) once per chunk on eng->stream.
 struct Pipeline {
   static constexpr int MAX_ARR = 16;
-  static constexpr size_t ALIGN = 256;
   struct HArr {
     const void *src = nullptr;   // host source (inputs)
     void *dst = nullptr;         // host destination (outputs); an output with dst == nullptr is not wanted
@@ -254,7 +263,6 @@ struct Pipeline {
     size_t dev_off = 0, pin_off = 0;
   };
   struct Pending { void *dst; const void *pin; size_t bytes; };
-  static size_t up(size_t v) { return (v + ALIGN - 1) & ~(ALIGN - 1); }
 
   ntru_engine *eng;
   HArr arr[MAX_ARR];
@@ -301,8 +309,8 @@ struct Pipeline {
       HArr &a = arr[i];
       const size_t bytes = a.shared ? a.row : a.row * (size_t)C;
       if (!a.src && !a.dst && !a.temp) continue;
-      a.dev_off = dev_bytes; dev_bytes += up(bytes);
-      if (!a.direct && !a.temp) { a.pin_off = pin_bytes; pin_bytes += up(bytes); }
+      a.dev_off = dev_bytes; dev_bytes += ntru_up256(bytes);
+      if (!a.direct && !a.temp) { a.pin_off = pin_bytes; pin_bytes += ntru_up256(bytes); }
     }
     for (hipStream_t *st : {&eng->st_up, &eng->st_comp, &eng->st_down})
       if (!*st) HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));

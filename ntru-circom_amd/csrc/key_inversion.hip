@@ -1,133 +1,7 @@
-// keygen_sampler_pack.hip -- MI355X (gfx950): the rows SURVEY.md 8(f) widens into, each with its *_dev entry point:
-//   key inversion (loadPrivateKeyF / polyInv, index.js:30-49, :491-514): k_invert_key + Newton rounds on the per-item product kernels
-//   on-device ternary sampler (generateCustomArray, index.js:461-488) on a ChaCha20 stream: k_sample_ternary
-//   BN254 field packing (packOutput / unpackInput, index.js:572-620): k_pack, k_unpack
-//   elementwise: stand-alone dividePolynomials(., I, mod) and addPolynomials on ciphertexts (index.js:358-401, :235-244)
+// key_inversion.hip -- MI355X (gfx950): key inversion, polyInv / loadPrivateKeyF (index.js:30-49, 491-514):
+// k_invert_key for one key per LANE, the Newton rounds on the per-item product kernels, ntru_invert_key_batch_dev.
 #include "kernels_common.h"
-#include "sampler_common.h"
 
-// dividePolynomials(a, I, mod) for reduced dividends, elementwise (HBM-bound): a is [B][2N].
-__global__ void k_split_by_I(int N, u32 mod, const u16 *__restrict__ a, long B, u16 *__restrict__ quot,
-                             u16 *__restrict__ rem) {
-  const long total = B * N;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const long row = idx / N; const int k = (int)(idx - row * N);
-    const u32 lo = a[row * 2 * N + k], hi = a[row * 2 * N + N + k];
-    quot[idx] = (u16)((mod - hi % mod) % mod);
-    rem[idx] = (u16)((lo + hi) % mod);
-  }
-}
-
-// addPolynomials(a, b, mod) on [B][N] rows, elementwise (HBM-bound).  The rows are contiguous, so the batch is one flat
-// array: 16 bytes (8 coefficients) per lane per access when the three base pointers are 16-byte aligned.
-typedef u16 u16x8 __attribute__((ext_vector_type(8)));
-template <bool POW2>
-__global__ void k_add_mod_vec(u32 mod, const u16x8 *__restrict__ a, const u16x8 *__restrict__ b, long nvec,
-                              u16x8 *__restrict__ out) {
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < nvec; idx += (long)gridDim.x * blockDim.x) {
-    const u16x8 x = a[idx], y = b[idx];
-    u16x8 r;
-    if (POW2) {
-      r = (x + y) & (u16)(mod - 1);                     // q | 2^16: wrapped 16-bit sums are exact mod q
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; k++) r[k] = (u16)(((u32)x[k] + (u32)y[k]) % mod);
-    }
-    out[idx] = r;
-  }
-}
-__global__ void k_add_mod(u32 mod, const u16 *__restrict__ a, const u16 *__restrict__ b, long first, long total,
-                          u16 *__restrict__ out) {
-  for (long idx = first + (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x)
-    out[idx] = (u16)(((u32)a[idx] + (u32)b[idx]) % mod);
-}
-
-
-// ---- on-device ternary sampler: generateCustomArray (index.js:461-488) for one item per LANE ---------------------
-// Same procedure as the reference: [1]*n1 ++ [other]*n2 ++ [0]*..., then for i = N-1 .. 1: j = u32 % (i+1), swap.
-// The u32 of step t of item b is word t of the ChaCha20 keystream (RFC 8439 block function) under the caller's key with
-// nonce (b_lo, b_hi, "NTRU"), so any host can replay it with a stock ChaCha20.  The Fisher-Yates chain is inherently
-// sequential per item, so items are spread over lanes.  A lane's row lives in LDS as 2-bit symbols (0, 1, 2 = `other`),
-// 16 per dword, laid out [word][lane]: whatever word a lane touches, it is in the lane's own bank.  13 KB per wave at
-// N = 821 -> 12 waves per CU, and the launcher asks for as much LDS as makes the resident count a MULTIPLE OF FOUR: the
-// kernel is bound by vector issue, every workgroup is one wave, and 9 waves on 4 SIMDs (what the round-2 layout with its
-// per-wave reciprocal table got) left three SIMDs idle a third of the time (profiles/archive/r03_ablation_sampler.txt).
-// A workgroup is WAVES = 4 independent waves (no barrier, private LDS regions) wherever four rows regions fit the LDS: as TWELVE
-// single-wave workgroups per CU the same kernel took 3.4 ms per 2^20 items at N = 821, as three four-wave workgroups 2.2 ms
-// (profiles/archive/r03_ab_sampler.txt; the inversion kernel, eight single-wave workgroups per CU, does not care: more than eight workgroups
-// per CU do not seem to be resident together, whatever the occupancy query says).
-// The block function, reciprocal table, start row and shuffle walk are in sampler_common.h (shared with keygen_batch.hip).
-
-// DR: double rounds of the block function: 10 = ChaCha20 (RFC 8439, the default), 6 = ChaCha12, 4 = ChaCha8 (ntru_engine_set_sampler_rounds:
-// the kernel is bound by the vector issue of these rounds; generateCustomArray's contract is the shuffle and its `u32 % (i + 1)` draws,
-// not the generator behind them, and a host replays whichever variant it asked for).
-template <bool BIGN, int WAVES, int DR>     // BIGN: N + 1 >= 2048, reciprocals from an LDS table behind the rows
-__global__ __launch_bounds__(WAVES * 64) void k_sample_ternary(int N, int n1, int n2, u32 other, ChaChaKey key,
-                                                       unsigned long long first_item, long B,
-                                                       uint8_t *__restrict__ out, int NW) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const size_t per_wave = (size_t)NW * 64 + (BIGN ? (size_t)((N + 2) & ~1) : 0);     // dwords
-  u32 *rows = (u32 *)lds + wave * per_wave;              // [NW][64] dwords of 16 symbols
-  u32 *recip_l = rows + (size_t)NW * 64;                 // BIGN: [N + 1]
-  if (BIGN) {
-    for (int d = lane; d <= N; d += 64) recip_l[d] = d >= 2 ? (u32)(0x100000000ULL / (unsigned)d) : 0u;
-    wave_lds_fence();
-  }
-  u32 *col = rows + lane;                                // word w of this lane's row: col[64 w]
-  const bool out_aligned = (((unsigned long long)out) & 15) == 0 && N >= 16;
-  for (long base = ((long)blockIdx.x * WAVES + wave) * 64; base < B; base += (long)gridDim.x * WAVES * 64) {
-    for (int w = 0; w < NW; w++) col[64 * w] = sampler_start_word(w, n1, n2);
-    const unsigned long long item = first_item + (unsigned long long)(base + lane);
-    sampler_shuffle_row<BIGN, DR>(col, N, key, (u32)item, (u32)(item >> 32), SAMPLER_NONCE2, recip_l);
-    wave_lds_fence();
-    if (out_aligned && base + 64 <= B) {
-      // rows -> row-major byte output.  The 64 rows of the block are ONE contiguous run of 64 N bytes that starts on a 64-byte
-      // boundary: lane L writes the 16-byte pieces of bytes [S L, S L + S), S = 16 NW >= N, i.e. the end of row ~L and the start of
-      // row ~L + 1 (distinct rows per lane: distinct LDS banks), every store aligned; 64 N is a multiple of 16, so a piece is
-      // inside the run or outside it.
-      const u32 S = 16u * (u32)NW, a0 = S * (u32)lane, run = 64u * (u32)N;
-      u32 r = a0 / (u32)N, c = a0 - r * (u32)N;
-      uint4 *dst = (uint4 *)(out + (size_t)base * N) + (size_t)NW * lane;
-      for (int it = 0; it < NW; it++) {
-        if (a0 + 16u * (u32)it < run) {
-          const u32 *rp = rows + r;
-          const int w = (int)(c >> 4), w1i = w + 1 < NW ? w + 1 : w;
-          u32 bits = __builtin_amdgcn_alignbit(rp[64 * w1i], rp[64 * w], 2 * (c & 15));
-          const int nf = N - (int)c;                     // symbols of row r from c on (>= 1)
-          if (nf < 16) bits = (bits & ((1u << (2 * nf)) - 1u)) | (rows[r + 1] << (2 * nf));   // the piece continues in row r + 1
-          u32 o[4];
-#pragma unroll
-          for (int q = 0; q < 4; q++) {
-            u32 t = (bits >> (8 * q)) & 0xFFu;
-            t = (t | (t << 12)) & 0x000F000Fu;
-            t = (t | (t << 6)) & 0x03030303u;
-            if (other != 2u) t += ((t >> 1) & 0x01010101u) * (other - 2u);
-            o[q] = t;
-          }
-          dst[it] = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-        c += 16;
-        if (c >= (u32)N) { c -= (u32)N; r++; }
-      }
-    } else {
-      // any alignment, partial last block: the wave walks one row at a time, one byte per lane
-      for (int rr = 0; rr < 64; rr++) {
-        if (base + rr >= B) break;
-        uint8_t *dst = out + (size_t)(base + rr) * N;
-        const u32 *src = rows + rr;
-        for (int k = lane; k < N; k += 64) {
-          const u32 sym = (src[64 * (k >> 4)] >> (2 * (k & 15))) & 3u;
-          dst[k] = (uint8_t)(sym == 2u ? other : sym);
-        }
-      }
-    }
-    wave_lds_fence();
-  }
-}
-
-
-// ---- key inversion: polyInv / loadPrivateKeyF (index.js:30-49, 491-514) for one key per LANE --------
 // f^-1 in Z_P[x]/(x^N - 1), P = 2 or 3, by 2N - 1 Bernstein-Yang division steps on the reversed polynomials: the control
 // flow is the same for every key (a conditional swap and two multiply-accumulates by per-lane scalars per step), which is
 // what 64 keys in lock-step need; the reference's Euclidean algorithm returns the same polynomial because the inverse is
@@ -196,8 +70,8 @@ __global__ __launch_bounds__(64) void k_invert_key(int N, const int8_t *__restri
             r0 = v & ~(v >> 1) & 0x01010101u;
             r1 = (v >> 1) & ~v & 0x01010101u;
           }
-          x0 |= (((r0 * 0x00204081u) >> 21) & 15u) << (4 * c);          // bit 0 of byte j -> bit j
-          x1 |= (((r1 * 0x00204081u) >> 21) & 15u) << (4 * c);
+          x0 |= bytes_to_nibble(r0) << (4 * c);
+          x1 |= bytes_to_nibble(r1) << (4 * c);
         }
         const u32 kk = __umulhi(e, inv), i = e - kk * uN, nf = uN - i, na = nf < 16u ? nf : 16u;
         put(tin + kk, nf - na, na, x0);
@@ -397,7 +271,6 @@ __global__ __launch_bounds__(64) void k_invert_key(int N, const int8_t *__restri
         }
         return __builtin_bitreverse32(x) >> 16;
       };
-      auto spread4 = [](u32 nib) { return (nib * 0x00204081u) & 0x01010101u; };       // bit j of a nibble -> byte j
       for (u32 e = 16u * (u32)lane; e < total; e += 1024u) {
         const u32 kk = __umulhi(e, inv), i = e - kk * uN, nf = uN - i;
         u32 f0 = seg(tr + kk, nf), f1 = P == 3 ? seg(tr + (size_t)NW * 64 + kk, nf) : 0u;
@@ -410,7 +283,7 @@ __global__ __launch_bounds__(64) void k_invert_key(int N, const int8_t *__restri
         if (out8) {
           u32 o[4];
 #pragma unroll
-          for (int c = 0; c < 4; c++) o[c] = spread4((f0 >> (4 * c)) & 15u) + 2u * spread4((f1 >> (4 * c)) & 15u);
+          for (int c = 0; c < 4; c++) o[c] = nibble_to_bytes((f0 >> (4 * c)) & 15u) + 2u * nibble_to_bytes((f1 >> (4 * c)) & 15u);
           *(uint4 *)(out8 + at0) = make_uint4(o[0], o[1], o[2], o[3]);
         }
         if (out16) {
@@ -468,122 +341,6 @@ __global__ void k_newton_combine_vec(u16x8 *__restrict__ v, const u16x8 *__restr
     v[i] = ((u16)2 * v[i] - u[i]) & (u16)(q - 1);                        // q | 2^16: wrapped 16-bit arithmetic is exact mod q
 }
 
-// ---- BN254 field-element packing (index.js:572-620): elementwise, HBM-bound ---------------------------------------
-// One thread per 64-bit limb of the output: out[b][o] = sum_j data[b][o*per + j] << (j*bits), four LE limbs per element.
-// T: u16 values (ciphertexts, witness arrays) or bytes (decrypted values, ternary arrays).
-template <class T>
-__global__ void k_pack(int bits, int per, int data_len, int out_size, const T *__restrict__ data, long B,
-                       unsigned long long *__restrict__ out) {
-  const long total = B * out_size * 4;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int l = (int)(idx & 3);
-    const long eo = idx >> 2;
-    const long b = eo / out_size;
-    const int o = (int)(eo - b * out_size);
-    const int lo_bit = 64 * l;
-    int j0 = lo_bit / bits, j1 = (lo_bit + 63) / bits;
-    if (j1 >= per) j1 = per - 1;
-    unsigned long long limb = 0;
-    for (int j = j0; j <= j1; j++) {
-      const int i = o * per + j;
-      const unsigned long long v = i < data_len ? data[b * data_len + i] : 0ull;
-      const int sh = j * bits - lo_bit;
-      limb |= sh >= 0 ? v << sh : v >> (-sh);
-    }
-    out[idx] = limb;
-  }
-}
-
-// packOutput of BYTES with 2-bit fields (values of decryptBits, ternary rows: max_val 2 or 3; 126 values per element): one thread per
-// output DWORD = 16 consecutive values = 16 consecutive bytes of the row (the eighth dword of an element holds 14), read as four
-// dwords at whatever alignment they have.  (The generic kernel above reads 32 single bytes per 64-bit limb: 1.2 ms per 2^20 rows of
-// N = 821 against 0.3 ms.)
-__global__ void k_pack_bytes2(int data_len, int out_size, const uint8_t *__restrict__ data, long B, u32 *__restrict__ out) {
-  const long total = B * out_size * 8;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const long b = idx / (out_size * 8);
-    const int dw = (int)(idx - b * out_size * 8), o = dw >> 3, k = dw & 7, i0 = 126 * o + 16 * k;
-    const uint8_t *src = data + b * data_len + i0;
-    u32 res = 0;
-    if (i0 + 16 <= data_len) {
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        u32 d;
-        __builtin_memcpy(&d, src + 4 * c, 4);
-        u32 t = d & 0x03030303u;
-        t |= t >> 6;
-        t = (t | (t >> 12)) & 0xFFu;
-        res |= t << (8 * c);
-      }
-    } else {
-      for (int j = 0; j < 16; j++) if (i0 + j < data_len) res |= ((u32)src[j] & 3u) << (2 * j);
-    }
-    out[idx] = k == 7 ? res & 0x0FFFFFFFu : res;
-  }
-}
-
-// unpackInput before trimming: out[b][i*per + j] = (in[b][i] >> (j*bits)) & mask.
-__global__ void k_unpack(int bits, int per, int packed_size, const unsigned long long *__restrict__ in, long B,
-                         u16 *__restrict__ out) {
-  const long total = B * packed_size * per;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const long e = idx / per;
-    const int j = (int)(idx - e * per);
-    const unsigned long long *l = in + e * 4;
-    const int pos = j * bits, w = pos >> 6, sft = pos & 63;
-    unsigned long long v = l[w] >> sft;
-    if (sft + bits > 64 && w + 1 < 4) v |= l[w + 1] << (64 - sft);
-    out[idx] = (u16)(v & ((1u << bits) - 1u));
-  }
-}
-
-// ---- host side: *_dev entry points ------------------------------------------------------------------------------------------
-
-static int check_elementwise(const ntru_engine *eng, int N, int mod, long B) {
-  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B < 0) return fail(NTRU_ERR_ARG, "negative batch size");
-  if (N < 1 || mod < 2 || mod > 65536) return fail(NTRU_ERR_UNSUPPORTED, "need N >= 1 and 2 <= mod <= 65536");
-  return NTRU_OK;
-}
-
-extern "C" int ntru_split_by_I_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_a, int64_t B,
-                                   uint16_t *d_quot, uint16_t *d_rem) {
-  if (int rc = check_elementwise(eng, N, mod, B)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!d_a || !d_quot || !d_rem) return fail(NTRU_ERR_ARG, "ntru_split_by_I: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  hipLaunchKernelGGL(k_split_by_I, elementwise_grid(eng, B * N), dim3(256), 0, eng->stream, N, (u32)mod, d_a, (long)B,
-                     d_quot, d_rem);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
-}
-
-extern "C" int ntru_add_batch_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_a, const uint16_t *d_b,
-                                  int64_t B, uint16_t *d_out) {
-  if (int rc = check_elementwise(eng, N, mod, B)) return rc;
-  if (B == 0) return NTRU_OK;
-  if (!d_a || !d_b || !d_out) return fail(NTRU_ERR_ARG, "ntru_add_batch: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  const long total = (long)B * N;
-  const bool aligned = (((uintptr_t)d_a | (uintptr_t)d_b | (uintptr_t)d_out) & 15) == 0;
-  const long nvec = aligned ? total / 8 : 0;
-  if (nvec) {
-    if (is_pow2(mod))
-      hipLaunchKernelGGL(k_add_mod_vec<true>, elementwise_grid(eng, nvec, true), dim3(256), 0, eng->stream, (u32)mod,
-                         (const u16x8 *)d_a, (const u16x8 *)d_b, nvec, (u16x8 *)d_out);
-    else
-      hipLaunchKernelGGL(k_add_mod_vec<false>, elementwise_grid(eng, nvec, true), dim3(256), 0, eng->stream, (u32)mod,
-                         (const u16x8 *)d_a, (const u16x8 *)d_b, nvec, (u16x8 *)d_out);
-  }
-  if (nvec * 8 < total)
-    hipLaunchKernelGGL(k_add_mod, elementwise_grid(eng, total - nvec * 8), dim3(256), 0, eng->stream, (u32)mod, d_a, d_b,
-                       nvec * 8, total, d_out);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
-}
-
-// ---- key inversion, sampler, field packing: *_dev entry points (the host-pointer forms are in ntru_host.hip) --------
-
 static const int64_t INVERT_CHUNK = 1 << 16;   // keys per set of Newton temporaries
 
 template <int P, int NWC>
@@ -635,8 +392,8 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
   bits_of[rounds] = k;
   for (int r = rounds; r > 0; r--) bits_of[r - 1] = (bits_of[r] + 1) / 2;
   const int64_t C = B < INVERT_CHUNK ? B : INVERT_CHUNK;     // Newton temporaries for C keys at a time
-  const size_t row = (size_t)N * 2, part = rounds > 0 ? ((size_t)C * row + 255) & ~(size_t)255 : 0;
-  const size_t fl_bytes = d_fp ? ((size_t)B + 255) & ~(size_t)255 : 0;
+  const size_t row = (size_t)N * 2, part = rounds > 0 ? ntru_up256((size_t)C * row) : 0;
+  const size_t fl_bytes = d_fp ? ntru_up256((size_t)B) : 0;
   ScratchHold hold(eng, 4 * part + fl_bytes + 256);          // engine-owned, grown on demand, never per call; released (event
   if (hold.rc) return hold.rc;                               // recorded) on every way out of this function
   char *const sc = hold.p;
@@ -710,109 +467,5 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
   }
   if (int rc = join()) return rc;
   snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_invert_key");
-  return NTRU_OK;
-}
-
-template <bool BIGN, int WAVES, int DR>
-static int launch_sampler(ntru_engine *eng, int N, int n1, int n2, int other, const ChaChaKey &ck, uint64_t first_item, int64_t B,
-                          uint8_t *d_out) {
-  const int NW = (N + 15) / 16;                          // dwords of 16 symbols per row
-  const size_t lds = WAVES * ((size_t)64 * NW * 4 + (BIGN ? (size_t)((N + 2) & ~1) * 4 : 0));
-  if (lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "N too large for the sampler's LDS rows");
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sample_ternary");
-  return launch_resident(eng, k_sample_ternary<BIGN, WAVES, DR>, (B + WAVES * 64 - 1) / (WAVES * 64), WAVES * 64, lds, N, n1, n2, (u32)other,
-                         ck, (unsigned long long)first_item, (long)B, d_out, NW);
-}
-
-extern "C" int ntru_sample_ternary_dev(ntru_engine_t *eng, int N, int n1, int n2, int other, const uint32_t *key,
-                                       uint64_t first_item, int64_t B, uint8_t *d_out) {
-  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B < 0 || N < 1 || n1 < 0 || n2 < 0) return fail(NTRU_ERR_ARG, "negative size");
-  if (n1 + n2 > N) return fail(NTRU_ERR_ARG, "The total of 1s and -1s cannot exceed the array length.");   // index.js:463
-  if (other < 0 || other > 255) return fail(NTRU_ERR_ARG, "`other` must fit a byte");
-  if (!key) return fail(NTRU_ERR_ARG, "ntru_sample_ternary: key is NULL");
-  if (B == 0) return NTRU_OK;
-  if (!d_out) return fail(NTRU_ERR_ARG, "ntru_sample_ternary: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  ChaChaKey ck;
-  memcpy(ck.k, key, 32);
-  auto go = [&](auto dr) -> int {
-    constexpr int DR = decltype(dr)::value;
-    return N + 1 < 2048 ? launch_sampler<false, 4, DR>(eng, N, n1, n2, other, ck, first_item, B, d_out)     // <= 32 KB of rows per wave
-                        : launch_sampler<true, 1, DR>(eng, N, n1, n2, other, ck, first_item, B, d_out);
-  };
-  switch (eng->sampler_rounds) {
-    case 8: return go(std::integral_constant<int, 4>{});
-    case 12: return go(std::integral_constant<int, 6>{});
-    default: return go(std::integral_constant<int, 10>{});
-  }
-}
-
-extern "C" int ntru_pack_params(int max_val, int data_len, int *bits, int *per_output, int *arr_len, int *output_size) {
-  if (max_val < 1 || max_val > 65535 || data_len < 0 || !bits || !per_output || !arr_len || !output_size)
-    return fail(NTRU_ERR_ARG, "ntru_pack_params: need 1 <= max_val <= 65535, data_len >= 0 and non-NULL outputs");
-  int b = 0;
-  while ((max_val >> b) != 0) b++;                    // floor(log2(maxVal) + 1), index.js:573
-  const int n = 252 / b;                              // index.js:574
-  int al = ((data_len + n - 1) / n) * n;              // index.js:575-578
-  if (al < 3 * n) al = 3 * n;
-  int os = (al + n - 1) / n;                          // index.js:580
-  if (os < 3) os = 3;
-  *bits = b; *per_output = n; *arr_len = al; *output_size = os;
-  return NTRU_OK;
-}
-
-extern "C" int ntru_pack_batch_dev(ntru_engine_t *eng, int max_val, int data_len, const uint16_t *d_data, int64_t B,
-                                   uint64_t *d_out) {
-  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B < 0) return fail(NTRU_ERR_ARG, "negative batch size");
-  int bits, per, al, os;
-  if (int rc = ntru_pack_params(max_val, data_len, &bits, &per, &al, &os)) return rc;
-  if (B == 0) return NTRU_OK;
-  if ((!d_data && data_len) || !d_out) return fail(NTRU_ERR_ARG, "ntru_pack_batch: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  hipLaunchKernelGGL(k_pack<u16>, elementwise_grid(eng, B * os * 4), dim3(256), 0, eng->stream, bits, per, data_len, os, d_data,
-                     (long)B, (unsigned long long *)d_out);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
-}
-
-// The same for an array of BYTES (decryptBits' value, quotient2, r, m: values <= 255): packOutput without widening it first.
-extern "C" int ntru_pack_bytes_batch_dev(ntru_engine_t *eng, int max_val, int data_len, const uint8_t *d_data, int64_t B,
-                                         uint64_t *d_out) {
-  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B < 0) return fail(NTRU_ERR_ARG, "negative batch size");
-  if (max_val > 255) return fail(NTRU_ERR_ARG, "ntru_pack_bytes_batch: max_val must fit a byte");
-  int bits, per, al, os;
-  if (int rc = ntru_pack_params(max_val, data_len, &bits, &per, &al, &os)) return rc;
-  if (B == 0) return NTRU_OK;
-  if ((!d_data && data_len) || !d_out) return fail(NTRU_ERR_ARG, "ntru_pack_bytes_batch: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  if (bits == 2) {                                         // ternary rows / decrypted values: 16 values per output dword
-    hipLaunchKernelGGL(k_pack_bytes2, elementwise_grid(eng, B * os * 8), dim3(256), 0, eng->stream, data_len, os, d_data, (long)B, (u32 *)d_out);
-    HIP_TRY(hipGetLastError());
-    return NTRU_OK;
-  }
-  hipLaunchKernelGGL(k_pack<uint8_t>, elementwise_grid(eng, B * os * 4), dim3(256), 0, eng->stream, bits, per, data_len, os, d_data,
-                     (long)B, (unsigned long long *)d_out);
-  HIP_TRY(hipGetLastError());
-  return NTRU_OK;
-}
-
-extern "C" int ntru_unpack_batch_dev(ntru_engine_t *eng, int max_val, int packed_bits, const uint64_t *d_in,
-                                     int packed_size, int64_t B, uint16_t *d_out) {
-  if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
-  if (B < 0 || packed_size < 0) return fail(NTRU_ERR_ARG, "negative size");
-  if (max_val < 1 || max_val > 65535) return fail(NTRU_ERR_ARG, "need 1 <= max_val <= 65535");
-  int bits = 0;
-  while ((max_val >> bits) != 0) bits++;
-  const int per = packed_bits / bits;
-  if (per < 1 || per * bits > 256) return fail(NTRU_ERR_ARG, "packed_bits does not hold a whole number of values within 256 bits");
-  if (B == 0 || packed_size == 0) return NTRU_OK;
-  if (!d_in || !d_out) return fail(NTRU_ERR_ARG, "ntru_unpack_batch: NULL buffer");
-  HIP_TRY(hipSetDevice(eng->device));
-  hipLaunchKernelGGL(k_unpack, elementwise_grid(eng, B * packed_size * per), dim3(256), 0, eng->stream, bits, per,
-                     packed_size, (const unsigned long long *)d_in, (long)B, d_out);
-  HIP_TRY(hipGetLastError());
   return NTRU_OK;
 }

@@ -4,50 +4,22 @@
 // The chain: g and the first f of every item from k_sample_ternary (ntru_sample_ternary_dev), fq / fp from ntru_invert_key_batch_dev,
 // then the redraw passes, then h from ntru_public_key_batch_dev over the whole batch.  A redraw pass:
 //   k_keygen_compact          flags -> list of the items still waiting for attempt t (wave ballot + prefix, one atomic per wave) + count
-//   k_sample_ternary_listed   attempt t of every listed item into compact rows (position (t << 44) + item: its own, whatever else failed)
+//   k_sample_ternary (listed) attempt t of every listed item into compact rows (position (t << 44) + item: its own, whatever else failed),
+//                             through ntru_launch_sample_listed (ternary_sampler.hip)
 //   ntru_invert_key_batch_dev the compact rows
 //   k_keygen_scatter          compact rows back to their items: f, tries and flags always, fq / fp where the new f is a unit
 // An item that still waits carries a parity mark (bit 0 of its flags byte: t & 1 after a failed attempt t), so that a pass of at most
 // KG_PASS_ROWS rows can leave the rest of attempt t's items for the next pass without confusing them with the items that just failed
 // attempt t.  k_keygen_finalize clears the marks and zeroes fq / fp of the items that never drew a unit.
-#include "sampler_common.h"
+#include "kernels_common.h"
 
 namespace {
 
 constexpr int KG_PASS_ROWS = 4096;            // compact rows per redraw pass: the workspace does not grow with B
-constexpr int KG_WAVES = 4;
 constexpr u32 KG_NOT_UNIT = NTRU_FLAG_NOT_UNIT_MOD2 | NTRU_FLAG_NOT_UNIT_MODP;
 constexpr u32 KG_MARK = 1;                    // parity mark of a waiting item (never set in a returned flags byte)
 constexpr int KG_ATTEMPT_SHIFT = 44;          // stream position of attempt t of item i: (t << 44) + i
 constexpr uint64_t KG_G_BASE = 1ull << 40;    // stream position of g of item i: 2^40 + i; every item index is below 2^40
-
-// k_sample_ternary for the items idx[0 .. n) (stream positions pos_base + idx[k]) into compact rows k: the same start row, block
-// function, reciprocals and shuffle (sampler_common.h), always ChaCha20.  N + 1 < 2048 (N <= NTRU_MAX_N): reciprocals from the constant
-// table.  Lanes past n draw a copy of the last item and store nothing (the shuffle loop is uniform).
-__global__ __launch_bounds__(KG_WAVES * 64) void k_sample_ternary_listed(int N, int n1, int n2, u32 other, ChaChaKey key,
-                                                                       unsigned long long pos_base, const u32 *__restrict__ idx, int n,
-                                                                       uint8_t *__restrict__ out, int NW) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  u32 *rows = (u32 *)lds + (size_t)wave * NW * 64;       // [NW][64] dwords of 16 symbols
-  u32 *col = rows + lane;
-  for (int base = ((int)blockIdx.x * KG_WAVES + wave) * 64; base < n; base += (int)gridDim.x * KG_WAVES * 64) {
-    for (int w = 0; w < NW; w++) col[64 * w] = sampler_start_word(w, n1, n2);
-    const int k = base + lane < n ? base + lane : n - 1;
-    const unsigned long long item = pos_base + idx[k];
-    sampler_shuffle_row<false, 10>(col, N, key, (u32)item, (u32)(item >> 32), SAMPLER_NONCE2, nullptr);
-    wave_lds_fence();
-    for (int rr = 0; rr < 64 && base + rr < n; rr++) {   // one row at a time, one byte per lane
-      uint8_t *dst = out + (size_t)(base + rr) * N;
-      const u32 *src = rows + rr;
-      for (int c = lane; c < N; c += 64) {
-        const u32 sym = (src[64 * (c >> 4)] >> (2 * (c & 15))) & 3u;
-        dst[c] = (uint8_t)(sym == 2u ? other : sym);
-      }
-    }
-    wave_lds_fence();
-  }
-}
 
 // The items b < B whose flags say "not a unit" and whose mark equals `mark` -> list[0 .. min(count, cap)), count = how many there are
 // (all of them, also past cap).  List order is whatever the atomics make it: every row's draw depends on its own index only.
@@ -64,7 +36,7 @@ __global__ void k_keygen_compact(const uint8_t *__restrict__ flags, long B, u32 
     const bool waiting = (fl & KG_NOT_UNIT) && (fl & KG_MARK) == mark;
     const unsigned long long ballot = __ballot(waiting);
     if (!ballot) continue;
-    const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((u32)ballot, 0u));
+    const u32 below = lanes_below(ballot);
     u32 first = 0;
     if (lane == 0) first = atomicAdd(count, (u32)__popcll(ballot));
     first = __shfl(first, 0);
@@ -119,19 +91,17 @@ struct Layout {
   size_t list, count, f, fq, fp, fl, total;
 };
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 Layout layout_of(int N, int64_t B) {
   Layout L;
   L.rows = std::max<int64_t>(1, std::min<int64_t>(B, KG_PASS_ROWS));
   const size_t r = (size_t)L.rows;
   L.list = 0;
-  L.count = L.list + up256(4 * r);
+  L.count = L.list + ntru_up256(4 * r);
   L.f = L.count + 256;
-  L.fq = L.f + up256(r * N);
-  L.fp = L.fq + up256(2 * r * N);
-  L.fl = L.fp + up256(r * N);
-  L.total = L.fl + up256(r);
+  L.fq = L.f + ntru_up256(r * N);
+  L.fp = L.fq + ntru_up256(2 * r * N);
+  L.fl = L.fp + ntru_up256(r * N);
+  L.total = L.fl + ntru_up256(r);
   return L;
 }
 
@@ -186,9 +156,6 @@ extern "C" int ntru_keygen_batch_dev(ntru_engine_t *eng, int N, int q, int p, in
   int8_t *const wf = (int8_t *)(w + L.f);
   uint16_t *const wfq = (uint16_t *)(w + L.fq);
   uint8_t *const wfp = (uint8_t *)(w + L.fp), *const wfl = (uint8_t *)(w + L.fl);
-  const int NW = (N + 15) / 16;
-  ChaChaKey ck;
-  memcpy(ck.k, key, 32);
 
   if (int rc = ntru_sample_ternary_dev(eng, N, dg, dg, 255, key, KG_G_BASE + first_item, B, (uint8_t *)d_g)) return rc;
   if (int rc = ntru_sample_ternary_dev(eng, N, df, df - 1, 255, key, first_item, B, (uint8_t *)d_f)) return rc;
@@ -213,10 +180,8 @@ extern "C" int ntru_keygen_batch_dev(ntru_engine_t *eng, int N, int q, int p, in
     const u32 mark_in = (u32)(t - 1) & KG_MARK, mark_out = (u32)t & KG_MARK;
     for (;;) {                                                 // passes of at most L.rows items of attempt t
       const int n = (int)std::min<int64_t>(waiting, L.rows);
-      const size_t lds = (size_t)KG_WAVES * 64 * NW * 4;
-      if (int rc = launch_resident(eng, k_sample_ternary_listed, (n + KG_WAVES * 64 - 1) / (KG_WAVES * 64), KG_WAVES * 64, lds, N, df, df - 1,
-                                   255u, ck, (unsigned long long)(((uint64_t)t << KG_ATTEMPT_SHIFT) + first_item), (const u32 *)list, n,
-                                   (uint8_t *)wf, NW))
+      if (int rc = ntru_launch_sample_listed(eng, N, df, df - 1, 255, key, ((uint64_t)t << KG_ATTEMPT_SHIFT) + first_item, list, n,
+                                             (uint8_t *)wf))
         return rc;
       if (int rc = ntru_invert_key_batch_dev(eng, N, q, p, wf, n, wfq, wfp, wfl)) return rc;
       hipLaunchKernelGGL(k_keygen_scatter, dim3((unsigned)std::min(n, eng->cus * 8)), dim3(256), 0, eng->stream, N, n, (const u32 *)list,

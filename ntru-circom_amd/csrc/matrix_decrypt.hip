@@ -68,17 +68,10 @@ static __device__ __forceinline__ void decrypt_m_body(MGeom g, u32 q, u32 p, u32
     for (int x = (int)threadIdx.x; x < rows_left * per_row; x += BLOCK_THREADS) {
       const int R = x / per_row, dw = x - R * per_row, o = dw >> 3, k = dw & 7;
       const unsigned char *src = pimg + (2 * (R >> 3) + ((R >> 2) & 1)) * pcols + 126 * o + 16 * k;
-      const int sh = 2 * (R & 3);
-      u32 out = 0;
+      u32 d[4];                                              // sixteen columns; the address is only 2-byte aligned
 #pragma unroll
-      for (int c = 0; c < 4; c++) {
-        u32 d;                                               // four columns; the address is only 2-byte aligned
-        __builtin_memcpy(&d, src + 4 * c, 4);
-        u32 t = (d >> sh) & 0x03030303u;
-        t |= t >> 6;
-        t = (t | (t >> 12)) & 0xFFu;
-        out |= t << (8 * c);
-      }
+      for (int c = 0; c < 4; c++) __builtin_memcpy(&d[c], src + 4 * c, 4);
+      const u32 out = pack2x16(d, 2 * (R & 3));              // row R's values are bits 2 (R & 3) .. of its row group's bytes
       dst[x] = k == 7 ? out & 0x0FFFFFFFu : out;             // 126 = 7 x 16 + 14: the eighth dword of an element holds 14 values
     }
   };

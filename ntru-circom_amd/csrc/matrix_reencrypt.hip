@@ -68,7 +68,7 @@ int launch_reencrypt_matrix(ntru_engine *eng, int N, int q, const uint16_t *d_h,
 int launch_reencrypt_valu(ntru_engine *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint16_t *d_e_in, int64_t B_in,
                           const int64_t *d_src, int64_t B, uint16_t *d_e_out, uint16_t *d_quotE) {
   const int64_t pass = std::min<int64_t>(B, RE_PASS);
-  const size_t zbytes = ((size_t)pass * N + 255) & ~(size_t)255;
+  const size_t zbytes = ntru_up256((size_t)pass * N);
   ScratchHold hold(eng, zbytes + (size_t)pass * N * 2);
   if (hold.rc) return hold.rc;
   uint8_t *d_zero = (uint8_t *)hold.p;

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(MB_THREADS) k_bytes_to_rows(int N, int nbytes,
       const u32 bits = flat_bits16(bytes, N, nbytes, row, col, 16);
       u32x4 o;
 #pragma unroll
-      for (int c = 0; c < 4; c++) o[c] = (((bits >> (4 * c)) & 15u) * 0x00204081u) & 0x01010101u;   // bit t of the nibble -> byte t
+      for (int c = 0; c < 4; c++) o[c] = nibble_to_bytes((bits >> (4 * c)) & 15u);
       *(u32x4 *)(m + head + 16 * i) = o;
       row += step_rows;
       col += step_cols;

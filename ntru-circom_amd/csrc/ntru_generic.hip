@@ -298,10 +298,9 @@ int run_generic(ntru_engine *eng, int op, int la, int lb, int64_t mod, const int
   long blocks = (long)eng->cus * 2;
   if (blocks > B) blocks = B;
   const size_t in_a = (size_t)B * la * 8, in_b = (size_t)B * lb * 8, rows = (size_t)B * cap * 8, lens = (size_t)B * 4;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_a = 0, o_b = o_a + up(in_a), o_w = o_b + up(in_b), o_0 = o_w + up((size_t)blocks * NBUF * cap * 8),
-               o_1 = o_0 + up(rows), o_l0 = o_1 + up(rows), o_l1 = o_l0 + up(lens), o_st = o_l1 + up(lens),
-               total = o_st + up((size_t)B);
+  const size_t o_a = 0, o_b = o_a + ntru_up256(in_a), o_w = o_b + ntru_up256(in_b),
+               o_0 = o_w + ntru_up256((size_t)blocks * NBUF * cap * 8), o_1 = o_0 + ntru_up256(rows), o_l0 = o_1 + ntru_up256(rows),
+               o_l1 = o_l0 + ntru_up256(lens), o_st = o_l1 + ntru_up256(lens), total = o_st + ntru_up256((size_t)B);
   // the engine's shared scratch buffer, ordered against its last user on another stream (key inversion on stream A, then this
   // call after ntru_engine_set_stream(B): B waits for A's event before the first copy below lands in the buffer)
   ScratchHold hold(eng, total);

@@ -47,17 +47,8 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_keys(ChaChaKey key, u32 id_
   const long wave_first = ((long)blockIdx.x * PT_THREADS + w * 64) * 8;      // the first key of this wave
   if (wave_first >= n) return;                      // uniform per wave; no workgroup barrier below
   const u32 ctr = (u32)(wave_first / 8) + lane;
-  u32 x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
-  u32 x4 = key.k[0], x5 = key.k[1], x6 = key.k[2], x7 = key.k[3], x8 = key.k[4], x9 = key.k[5], x10 = key.k[6], x11 = key.k[7],
-      x12 = ctr, x13 = id_lo, x14 = id_hi, x15 = NTRU_PERM_NONCE2;
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
-    CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
-  }
-  const u32 ks[16] = {x0 + 0x61707865u, x1 + 0x3320646eu, x2 + 0x79622d32u, x3 + 0x6b206574u,
-                      x4 + key.k[0], x5 + key.k[1], x6 + key.k[2], x7 + key.k[3], x8 + key.k[4], x9 + key.k[5],
-                      x10 + key.k[6], x11 + key.k[7], x12 + ctr, x13 + id_lo, x14 + id_hi, x15 + NTRU_PERM_NONCE2};
+  u32 ks[16];
+  chacha_block<10>(key, ctr, id_lo, id_hi, NTRU_PERM_NONCE2, ks);
 #pragma unroll
   for (int j = 0; j < 8; j++) s_keys[w][9 * lane + j] = (u64)ks[2 * j] | ((u64)ks[2 * j + 1] << 32);
   wave_lds_fence();
@@ -97,12 +88,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_offsets(u32 *hist, int tile
     const u32 c = t < tiles ? hist[(long)t * PT_DIGITS + d] : 0u;
     s_sum[tid] = c;
     __syncthreads();
-    for (int s = 1; s < PT_THREADS; s <<= 1) {
-      const u32 v = tid >= s ? s_sum[tid - s] : 0u;
-      __syncthreads();
-      s_sum[tid] += v;
-      __syncthreads();
-    }
+    wg_inclusive_scan<PT_THREADS>(s_sum, tid);
     if (t < tiles) hist[(long)t * PT_DIGITS + d] = carry + s_sum[tid] - c;
     carry += s_sum[PT_THREADS - 1];
     __syncthreads();                                                         // every lane has read the round's total
@@ -121,12 +107,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_scatter(const u64 *__restri
   const u32 tot = total[tid];
   s_base[tid] = tot;
   __syncthreads();
-  for (int s = 1; s < PT_DIGITS; s <<= 1) {         // inclusive prefix of the totals
-    const u32 v = tid >= s ? s_base[tid - s] : 0u;
-    __syncthreads();
-    s_base[tid] += v;
-    __syncthreads();
-  }
+  wg_inclusive_scan<PT_DIGITS>(s_base, tid);        // inclusive prefix of the totals
   s_base[tid] += offs[(long)blockIdx.x * PT_DIGITS + tid] - tot;
 #pragma unroll
   for (int v = 0; v < PT_WAVES; v++) s_wave[v][tid] = 0;
@@ -144,7 +125,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_scatter(const u64 *__restri
       const u64 bal = __ballot(bit);
       same &= bit ? bal : ~bal;
     }
-    const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(same >> 32), __builtin_amdgcn_mbcnt_lo((u32)same, 0u));
+    const u32 below = lanes_below(same);
     if (valid && below == 0) s_wave[w][d] = (u32)__popcll(same);
     __syncthreads();
     u32 pos = s_base[d] + below;
@@ -178,8 +159,6 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_finish(const u32 *__restric
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool overlap(const void *a, size_t na, const void *b, size_t nb) {
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
   return a && b && a0 < b0 + nb && b0 < a0 + na;
@@ -190,8 +169,8 @@ bool overlap(const void *a, size_t na, const void *b, size_t nb) {
 int perm_flow(ntru_engine *eng, const uint64_t *d_keys, const ChaChaKey *ck, uint64_t perm_id, int64_t B, int64_t *d_src, int64_t *d_dst) {
   HIP_TRY(hipSetDevice(eng->device));
   const int tiles = (int)((B + PT_TILE - 1) / PT_TILE);
-  const size_t kbytes = up256((size_t)B * 8), ibytes = up256((size_t)B * 4), hbytes = up256((size_t)tiles * PT_DIGITS * 4);
-  ScratchHold hold(eng, 2 * kbytes + 2 * ibytes + hbytes + up256(PT_DIGITS * 4));
+  const size_t kbytes = ntru_up256((size_t)B * 8), ibytes = ntru_up256((size_t)B * 4), hbytes = ntru_up256((size_t)tiles * PT_DIGITS * 4);
+  ScratchHold hold(eng, 2 * kbytes + 2 * ibytes + hbytes + ntru_up256(PT_DIGITS * 4));
   if (hold.rc) return hold.rc;
   u64 *kbuf[2] = {(u64 *)hold.p, (u64 *)(hold.p + kbytes)};
   u32 *ibuf[2] = {(u32 *)(hold.p + 2 * kbytes), (u32 *)(hold.p + 2 * kbytes + ibytes)};
@@ -258,9 +237,9 @@ int check_mix(ntru_engine *eng, const std::string &name, int N, int q, int p, co
 int draw_to_host(ntru_engine *eng, const ChaChaKey &ck, uint64_t perm_id, int64_t B, int64_t *src, int64_t *dst) {
   HIP_TRY(hipSetDevice(eng->device));
   const size_t bytes = (size_t)B * 8;
-  if (int rc = ntru_grow_dev(&eng->shared_dev, 2 * up256(bytes))) return rc;
+  if (int rc = ntru_grow_dev(&eng->shared_dev, 2 * ntru_up256(bytes))) return rc;
   int64_t *d_src = src ? (int64_t *)eng->shared_dev.p : nullptr;
-  int64_t *d_dst = dst ? (int64_t *)((char *)eng->shared_dev.p + up256(bytes)) : nullptr;
+  int64_t *d_dst = dst ? (int64_t *)((char *)eng->shared_dev.p + ntru_up256(bytes)) : nullptr;
   if (int rc = perm_flow(eng, nullptr, &ck, perm_id, B, d_src, d_dst)) return rc;
   HIP_TRY(hipStreamSynchronize(eng->stream));
   if (src) HIP_TRY(hipMemcpy(src, d_src, bytes, hipMemcpyDeviceToHost));

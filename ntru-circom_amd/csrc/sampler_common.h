@@ -1,7 +1,7 @@
-// sampler_common.h -- the device side of the ternary sampler (generateCustomArray, index.js:461-488) that its kernels share:
-// k_sample_ternary (keygen_sampler_pack.hip: consecutive stream positions) and k_sample_ternary_listed (keygen_batch.hip: the positions
-// of a device list of items).  One item per LANE: the ChaCha block function, the reciprocal table of `u32 % (i + 1)`, the start row
-// and the Fisher-Yates walk over a row of 2-bit symbols in LDS.
+// sampler_common.h -- the device side of the ternary sampler (generateCustomArray, index.js:461-488) that k_sample_ternary
+// (ternary_sampler.hip) is made of, one item per LANE: the reciprocal table of `u32 % (i + 1)`, the start row and the Fisher-Yates
+// walk over a row of 2-bit symbols in LDS -- and the ChaCha block function, which k_perm_keys (permutation.hip) draws its sort keys
+// from as well.
 #ifndef NTRU_SAMPLER_COMMON_H
 #define NTRU_SAMPLER_COMMON_H
 
@@ -19,6 +19,25 @@ static __constant__ const RecipTable g_recip = RecipTable();
 #define CHACHA_QR(a, b, c, d)                                                          \
   a += b; d ^= a; d = __builtin_rotateleft32(d, 16); c += d; b ^= c; b = __builtin_rotateleft32(b, 12); \
   a += b; d ^= a; d = __builtin_rotateleft32(d, 8);  c += d; b ^= c; b = __builtin_rotateleft32(b, 7);
+
+// The ChaCha block function of RFC 8439 with DR double rounds (10 = ChaCha20): ks = the 16 keystream words of block `ctr` under `key`
+// and nonce (n0, n1, n2).
+template <int DR>
+static __device__ __forceinline__ void chacha_block(const ChaChaKey &key, u32 ctr, u32 n0, u32 n1, u32 n2, u32 (&ks)[16]) {
+  u32 x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
+  u32 x4 = key.k[0], x5 = key.k[1], x6 = key.k[2], x7 = key.k[3], x8 = key.k[4], x9 = key.k[5], x10 = key.k[6],
+      x11 = key.k[7], x12 = ctr, x13 = n0, x14 = n1, x15 = n2;
+#pragma unroll
+  for (int r = 0; r < DR; r++) {
+    CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
+    CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
+  }
+  ks[0] = x0 + 0x61707865u; ks[1] = x1 + 0x3320646eu; ks[2] = x2 + 0x79622d32u; ks[3] = x3 + 0x6b206574u;
+  ks[4] = x4 + key.k[0]; ks[5] = x5 + key.k[1]; ks[6] = x6 + key.k[2]; ks[7] = x7 + key.k[3];
+  ks[8] = x8 + key.k[4]; ks[9] = x9 + key.k[5]; ks[10] = x10 + key.k[6]; ks[11] = x11 + key.k[7];
+  ks[12] = x12 + ctr; ks[13] = x13 + n0; ks[14] = x14 + n1; ks[15] = x15 + n2;
+}
+#undef CHACHA_QR
 
 constexpr u32 SAMPLER_NONCE2 = 0x4e545255u;             // "NTRU": the third nonce word of every item
 
@@ -47,17 +66,8 @@ static __device__ __forceinline__ void sampler_shuffle_row(u32 *col, int N, cons
 #pragma unroll
       for (int w = 0; w < 16; w++) rc[w] = recip_of(i + 1 - w);
     }
-    u32 x0 = 0x61707865u, x1 = 0x3320646eu, x2 = 0x79622d32u, x3 = 0x6b206574u;
-    u32 x4 = key.k[0], x5 = key.k[1], x6 = key.k[2], x7 = key.k[3], x8 = key.k[4], x9 = key.k[5], x10 = key.k[6],
-        x11 = key.k[7], x12 = ctr, x13 = n0, x14 = nn1, x15 = nn2;
-#pragma unroll
-    for (int r = 0; r < DR; r++) {
-      CHACHA_QR(x0, x4, x8, x12) CHACHA_QR(x1, x5, x9, x13) CHACHA_QR(x2, x6, x10, x14) CHACHA_QR(x3, x7, x11, x15)
-      CHACHA_QR(x0, x5, x10, x15) CHACHA_QR(x1, x6, x11, x12) CHACHA_QR(x2, x7, x8, x13) CHACHA_QR(x3, x4, x9, x14)
-    }
-    const u32 ks[16] = {x0 + 0x61707865u, x1 + 0x3320646eu, x2 + 0x79622d32u, x3 + 0x6b206574u,
-                        x4 + key.k[0], x5 + key.k[1], x6 + key.k[2], x7 + key.k[3], x8 + key.k[4], x9 + key.k[5],
-                        x10 + key.k[6], x11 + key.k[7], x12 + ctr, x13 + n0, x14 + nn1, x15 + nn2};
+    u32 ks[16];
+    chacha_block<DR>(key, ctr, n0, nn1, nn2, ks);
 #pragma unroll
     for (int w = 0; w < 16; w++) {
       if (i >= 1) {

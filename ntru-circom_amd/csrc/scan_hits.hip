@@ -77,12 +77,7 @@ __global__ void __launch_bounds__(SC_ROWS) k_scan_offsets(const u32 *__restrict_
   const long long base = *count;
   s_sum[tid] = c;
   __syncthreads();
-  for (int d = 1; d < SC_ROWS; d <<= 1) {
-    const u32 v = tid >= d ? s_sum[tid - d] : 0u;
-    __syncthreads();
-    s_sum[tid] += v;
-    __syncthreads();                            // (the first round's barrier also orders every lane's read of *count before its update)
-  }
+  wg_inclusive_scan<SC_ROWS>(s_sum, tid);       // (its first barrier also orders every lane's read of *count before its update)
   if (tid < nblocks) offsets[tid] = base + (long long)(s_sum[tid] - c);
   if (tid == SC_ROWS - 1) *count = base + (long long)s_sum[tid];
 }
@@ -99,7 +94,7 @@ __global__ void __launch_bounds__(SC_ROWS) k_scan_emit(int nbytes, ScanTag tag, 
   if (base >= limit) return;                    // uniform: the whole block lies behind the stored prefix
   const bool hit = r < n && row_hits(bytes, flags, r, nbytes, tag);
   const unsigned long long ballot = __ballot(hit);
-  const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((u32)ballot, 0u));
+  const u32 below = lanes_below(ballot);
   if ((tid & 63) == 0) s_wave[tid >> 6] = (u32)__popcll(ballot);
   __syncthreads();
   u32 before = 0, total = 0;
@@ -123,8 +118,6 @@ __global__ void __launch_bounds__(SC_ROWS) k_scan_emit(int nbytes, ScanTag tag, 
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The checks that need no engine, then the decrypt call's own (engine, (N, q), p).  `packed`: the rows arrive as packOutput rows.
 int check_scan_args(const ntru_engine *eng, const char *who, bool packed, int N, int q, int p, int nbytes, int K, int64_t B, int tag_off,
@@ -173,9 +166,9 @@ int scan_flow(ntru_engine *eng, int N, int q, int p, int nbytes, int K, const in
   HIP_TRY(hipSetDevice(eng->device));
   const int64_t pass = std::min<int64_t>(B, SC_PASS);
   const int max_blocks = (int)((pass + SC_ROWS - 1) / SC_ROWS);
-  const size_t at_value = up256(os ? (size_t)pass * N * 2 : 0), at_bytes = at_value + up256((size_t)pass * N),
-               at_flags = at_bytes + up256((size_t)pass * nbytes), at_counts = at_flags + up256((size_t)pass),
-               at_offsets = at_counts + up256((size_t)max_blocks * 4), total = at_offsets + up256((size_t)max_blocks * 8);
+  const size_t at_value = ntru_up256(os ? (size_t)pass * N * 2 : 0), at_bytes = at_value + ntru_up256((size_t)pass * N),
+               at_flags = at_bytes + ntru_up256((size_t)pass * nbytes), at_counts = at_flags + ntru_up256((size_t)pass),
+               at_offsets = at_counts + ntru_up256((size_t)max_blocks * 4), total = at_offsets + ntru_up256((size_t)max_blocks * 8);
   ScratchHold hold(eng, total);
   if (hold.rc) return hold.rc;
   uint16_t *d_unpacked = (uint16_t *)hold.p;
@@ -237,8 +230,8 @@ int scan_host(ntru_engine *eng, const char *who, bool packed, int N, int q, int 
   if (!f || !fp || !rows) return fail(NTRU_ERR_ARG, std::string(who) + ": NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
   const int64_t cap = std::min<int64_t>(max_hits, B);
-  const size_t at_row = up256((size_t)K * 8), at_bytes = at_row + up256((size_t)K * cap * 8);
-  if (int rc = ntru_grow_dev(&eng->shared_dev, at_bytes + up256((size_t)K * cap * nbytes))) return rc;
+  const size_t at_row = ntru_up256((size_t)K * 8), at_bytes = at_row + ntru_up256((size_t)K * cap * 8);
+  if (int rc = ntru_grow_dev(&eng->shared_dev, at_bytes + ntru_up256((size_t)K * cap * nbytes))) return rc;
   char *dev = (char *)eng->shared_dev.p;
   int64_t *d_count = (int64_t *)dev, *d_hit_row = (int64_t *)(dev + at_row);
   uint8_t *d_hit_bytes = (uint8_t *)dev + at_bytes;

@@ -61,7 +61,7 @@ int ntru_launch_verify_keys_valu(ntru_engine *, int, int, int, const int8_t *, c
   return NTRU_ERR_UNSUPPORTED;
 }
 
-// ---- the entry points of keygen_sampler_pack.hip -------------------------------------------------------------------------------
+// ---- the entry points of key_inversion.hip, ternary_sampler.hip and elementwise.hip -------------------------------------------------------------------------------
 extern "C" int ntru_split_by_I_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_a, int64_t B, uint16_t *d_quot, uint16_t *d_rem) {
   if (B == 0) return NTRU_OK;
   fake_enqueue(eng->stream, [=] { for (int64_t i = 0; i < B * N; i++) { d_quot[i] = (uint16_t)((d_a[2 * i] + 1) % mod); d_rem[i] = (uint16_t)((d_a[2 * i + 1] + 2) % mod); } });

@@ -172,9 +172,9 @@ _row("k_or_bytes", "invert_key", [(17, 32, 3, 0, 3), (821, 4096, 3, 0, 3)], None
 
 # ---- sampler, elementwise, generic ----------------------------------------------------------------------------------------------
 for _DR, _R in ((10, 20), (6, 12), (4, 8)):
-    _row("k_sample_ternary<false, 4, %d>" % _DR, "sample_ternary", [(2, 0, _R, 0, 1), (1920, 0, _R, 0, 257)], None,
+    _row("k_sample_ternary<false, 4, %d, ConsecutiveItems>" % _DR, "sample_ternary", [(2, 0, _R, 0, 1), (1920, 0, _R, 0, 257)], None,
          "N + 1 < 2048, %d rounds" % _R)
-    _row("k_sample_ternary<true, 1, %d>" % _DR, "sample_ternary", [(2047, 0, _R, 0, 3), (2500, 0, _R, 0, 3)], None,
+    _row("k_sample_ternary<true, 1, %d, ConsecutiveItems>" % _DR, "sample_ternary", [(2047, 0, _R, 0, 3), (2500, 0, _R, 0, 3)], None,
          "N + 1 >= 2048, %d rounds" % _R)
 _row("k_add_mod_vec<true>", "add", [(8, 2048, 0, 0, 1), (821, 65536, 0, 0, 9)], None, "power-of-two mod, 16-byte aligned, B N >= 8")
 _row("k_add_mod_vec<false>", "add", [(8, 3, 0, 0, 1), (821, 5, 0, 0, 9)], None, "other mod, 16-byte aligned, B N >= 8")
@@ -221,8 +221,12 @@ for _t in ("encrypt", "decrypt", "inverse"):
 
 # ---- key generation (keygen_batch.hip): the redraw kernels run only when a first draw is a non-unit -----------------------------------
 _KEYGEN = [(7, 32, 3, 0, 16, dict(df=2, dg=2, first=125)), (17, 32, 3, 0, 8, dict(df=3, dg=2, first=311))]
-for _k in ("k_sample_ternary_listed", "k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
+for _k in ("k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
     _row(_NS + _k, "keygen", _KEYGEN, "k_keygen", "ntru_keygen_batch_dev with a non-unit among the first draws")
+# the sampler at listed positions (ternary_sampler.hip); at the third shape about half of the 256 first draws are non-units: full
+# blocks of 64 compact rows with N >= 16, which leave through the aligned output stage (first = 2: the runner's third call starts at 0)
+_row("k_sample_ternary<false, 4, 10, ListedItems>", "keygen", _KEYGEN + [(16, 32, 3, 0, 256, dict(df=3, dg=2, first=2))], "k_keygen",
+     "ntru_keygen_batch_dev with a non-unit among the first draws")
 
 # ---- packed ciphertexts (packed_ciphertexts.hip) ------------------------------------------------------------------------------------------
 SP_BATCH, SP_WAVES_PER_CU = 4, 8      # row steps in flight and waves per CU of k_sum_groups_packed, as the kernel file sets them

@@ -1,4 +1,4 @@
-"""The degree bounds k_invert_key skips words by (csrc/keygen_sampler_pack.hip), checked on a plain-Python run of the same division
+"""The degree bounds k_invert_key skips words by (csrc/key_inversion.hip), checked on a plain-Python run of the same division
 steps (CPU only).  Before step n of the 2N - 1 Bernstein-Yang steps on ff = 1 - x^N, gg = rev_{N-1}(f), vv = 0, ww = 1, delta = 1:
     2 deg f <= 2N - 1 - n + delta      2 deg g <= 2N - 1 - n - delta      2 deg v <= n - 1 + delta      2 deg w <= n + 1 - delta
 and the kernel's word tests derive from them with the wave maximum of |delta| taken every 16th step: f and g are zero above

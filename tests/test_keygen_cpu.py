@@ -70,18 +70,27 @@ def test_workspace_is_bounded_in_B(lib):
 
 
 def test_new_kernels_do_not_spill(tmp_path):
-    """`make asm` of keygen_batch.hip: every kernel reports ScratchSize 0, and the four kernels are there."""
+    """`make asm` of keygen_batch.hip: every kernel reports ScratchSize 0, and the three kernels are there; the fourth, the sampler at
+    listed positions, is an instantiation in ternary_sampler.hip, with ScratchSize 0 as well."""
     src = os.path.join(ge.PKG_DIR, "csrc")
-    target = os.path.join(str(tmp_path), "keygen_batch.s")
-    out = subprocess.run(["make", "-C", src, "ASMDIR=" + str(tmp_path), target], capture_output=True, text=True, timeout=900)
+    targets = [os.path.join(str(tmp_path), tu + ".s") for tu in ("keygen_batch", "ternary_sampler")]
+    out = subprocess.run(["make", "-C", src, "-j2", "ASMDIR=" + str(tmp_path)] + targets, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
-    text = open(os.path.join(str(tmp_path), "keygen_batch.usage")).read()
-    names = re.findall(r"Function Name: (\S+)", text)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)]
-    assert len(names) == len(scratch) == 4, names
-    for must in ("k_sample_ternary_listed", "k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
+
+    def usage(tu):
+        text = open(os.path.join(str(tmp_path), tu + ".usage")).read()
+        names = re.findall(r"Function Name: (\S+)", text)
+        scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)]
+        assert len(names) == len(scratch), names
+        return names, scratch
+
+    names, scratch = usage("keygen_batch")
+    assert len(names) == 3, names
+    for must in ("k_keygen_compact", "k_keygen_scatter", "k_keygen_finalize"):
         assert any(must in n for n in names), must
     assert not any(scratch), list(zip(names, scratch))
+    listed = [s for n, s in zip(*usage("ternary_sampler")) if "k_sample_ternary" in n and "ListedItems" in n]
+    assert listed == [0], listed
 
 
 def test_shims_expose_key_generation():

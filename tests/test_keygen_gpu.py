@@ -8,7 +8,7 @@ import pytest
 import __graft_entry__ as ge
 from oracle import ntru_keygen as kg
 from oracle import ntru_oracle as orc
-from keygen_ref import replay
+from keygen_ref import key_pairs, replay
 
 pytestmark = pytest.mark.gpu
 pkg = ge.load_package()
@@ -87,6 +87,19 @@ def test_more_non_units_than_one_pass(eng):
     assert (out["tries"] > 1).sum() > 4096
     want = replay(N, df, dg, KEY, 0, B, 40)
     check_against_replay(N, q, out, want)
+
+
+def test_listed_draw_fills_whole_blocks_of_compact_rows(eng):
+    """N = 16, B = 256: 135 items wait after the first attempt and 65 after the second, so the listed draw writes two full blocks of 64
+    compact rows plus seven, then one full block plus one: full blocks with N >= 16 leave through the sampler's aligned output stage,
+    the rest row by row.  Every field against the CPU replay."""
+    N, q, df, dg, B, tries = 16, 32, 3, 2, 256, 6
+    key = np.arange(1, 9, dtype=np.uint32)
+    want = key_pairs(N, q, df, dg, key, 0, B, tries)
+    assert int((want["tries"] >= 2).sum()) == 135 and int((want["tries"] >= 3).sum()) == 65    # the oracle still exercises the path
+    out = eng.keygen_batch(N, q, 3, df, dg, key, B, first_item=0, max_tries=tries)
+    for name in ("tries", "flags", "f", "g", "fq", "fp", "h"):
+        assert np.array_equal(out[name], want[name]), name
 
 
 @pytest.mark.parametrize("name", ["n821_q4096", "n701_q8192", "n509_q2048"])

@@ -9,7 +9,7 @@ from oracle import ntru_keygen as kg
 
 
 def schedule(k):
-    """bits of v before every round and after the last one: k halved backwards down to 1 (csrc/keygen_sampler_pack.hip: bits_of)."""
+    """bits of v before every round and after the last one: k halved backwards down to 1 (csrc/key_inversion.hip: bits_of)."""
     rounds = 0
     while (1 << rounds) < k:
         rounds += 1
