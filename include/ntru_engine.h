@@ -397,7 +397,8 @@ int ntru_decrypt_batch_pitched_dev(ntru_engine_t *eng, int N, int q, int p, int 
                                    uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2);
 
 /* loadPrivateKeyF / polyInv (index.js:30-49, 491-514) for B keys: fq[b] = f[b]^-1 in Z_q[x]/(x^N - 1) (q a power of two:
- * inverse modulo 2, then Newton rounds v <- 2v - f v^2), fp[b] = f[b]^-1 modulo p = 3; f in {-1,0,1}.  The inverse is
+ * inverse modulo 2, then Newton rounds v <- 2v - f v^2), fp[b] = f[b]^-1 modulo p = 3; f in {-1,0,1} (any other int8
+ * coefficient counts by its value, in the inversions and in every Newton round alike).  The inverse is
  * unique, so for units the result equals the reference's Euclidean algorithm bit for bit.  For f that is not a unit the
  * matching flag is set and the row is zero; the reference throws 'invalid_gcd' / 'invalid fq' for most such f but its
  * `&&` checks (index.js:41-45, :451) accept some and return meaningless polynomials -- that artefact is not reproduced, and neither

@@ -397,7 +397,9 @@ __global__ __launch_bounds__(64 * PI_WAVES) __attribute__((amdgpu_waves_per_eu(4
       pi_digits(xv, me, 1u, 16 * ch, N, b0, o1);
       pi_digits(xv, 256u, 1u, 16 * ch, N, F[0], o1);      // v < 2^kb <= 128: its own centred representative modulo 256
       STAMP(1);                                            // operands arrived, digits
-      pi_build_array_half(nat, T, g, lane, ch, pi_ternary(vf, col_mask16(16 * ch, N)));          // (its last fence: nat is free for v's image)
+      // f by its VALUE, as k_invert_key reduced it modulo 2 (not ValTernary's "any negative byte is -1": the round would start from
+      // the inverse of another polynomial); |f v| <= 1024 * 128 * 127 < 2^31 per coefficient
+      pi_build_array_half(nat, T, g, lane, ch, vf & col_mask16(16 * ch, N));                     // (its last fence: nat is free for v's image)
       pi_store_image(nat, g, ch, F[0]);
       wave_lds_fence();
     }
