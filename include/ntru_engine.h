@@ -177,6 +177,34 @@ int ntru_tally_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const 
                                  const uint16_t *d_rows, const uint16_t *d_weights, const int64_t *d_offsets, int64_t K, int64_t G,
                                  uint16_t *d_sum, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1, uint8_t *d_quot2);
 
+/* ---- combining ciphertexts by a weight matrix: G linear combinations of the SAME B rows in one pass over them (one ballot counted in
+ *      several totals, rows scored against several public weight vectors) -- addPolynomials (index.js:235-244) over rows scaled as
+ *      multiplyPolynomialsByScalar does, once per output.  rows: [B][N], entries below mod, as for ntru_sum_groups; weights: [B][G]
+ *      row-major, row b holds the G weights of ciphertext b, each below mod (the [B] weights of ntru_sum_groups widened to G columns);
+ *      out: [G][N],
+ *        out[g][k] = (sum over b of weights[b][g] * rows[b][k]) % mod,
+ *      and row g of out is byte for byte what ntru_sum_groups(rows, column g of weights, K = B, G = 1) returns.
+ *      Domain: 2 <= N <= NTRU_MAX_N; 2 <= mod <= 65536, a power of two or not; 1 <= G <= NTRU_COMBINE_MAX_G; 0 <= B <= 2^31 (B == 0
+ *      writes G zero rows); pointers of any 2-byte alignment.  NTRU_ERR_ARG, each with a message of its own, before the engine is looked
+ *      at and before anything is launched: anything outside the domain, a NULL buffer with B > 0 (out: always), an out range that
+ *      overlaps rows or weights; a NULL engine with valid arguments is then the usual "engine is NULL".
+ *      The product is one integer matrix product modulo mod, out = W^T . rows.  A power-of-two modulus on kernel paths 0, 4 and 5 runs
+ *      on the int8 matrix cores (k_combine_m: two balanced digit planes per operand, wrapping int32 accumulators, exact); any other
+ *      modulus, and every modulus on kernel paths 1-3, runs on the vector ALU (k_combine_v).  The rows are cut into row blocks that
+ *      leave int32 partial results in the engine-owned scratch (at most 256 MiB, bounded by N, G and the grid, not by B) and
+ *      k_combine_finish adds them in a fixed order.  Integer sums do not depend on the order of the summands: the bytes of out do not
+ *      depend on the grid, the number of row blocks, the chunking of the host form or the kernel path.
+ *   _dev: enqueues on the engine's stream, does not synchronise, allocates nothing per call; weights >= mod are the caller's error.
+ *   host form: refuses a weight >= mod (NTRU_ERR_ARG naming row and column); rows and weights run through the chunked pipeline side by
+ *      side, out is accumulated across chunks on the device and comes down once.
+ *   Whether a combination decrypts to the weighted sum of the plaintexts depends on its noise: a weight multiplies its row's noise
+ *   ("Combining ciphertexts"). */
+#define NTRU_COMBINE_MAX_G 4096
+int ntru_combine_batch(ntru_engine_t *eng, int N, int mod, const uint16_t *rows, const uint16_t *weights, int64_t B, int G,
+                       uint16_t *out);
+int ntru_combine_batch_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_rows, const uint16_t *d_weights, int64_t B, int G,
+                           uint16_t *d_out);
+
 /* ---- packed ciphertexts: the three calls above and decryptBits on ciphertexts that arrive in the circuits' wire format,
  *      packOutput(mod - 1, N, e) (index.js:572-596) -- what CombineArray makes public and what ntru_encrypt_pack_batch_dev,
  *      ntru_pipeline_batch(packed) and ntru_keygen_batch(packed_h) emit -- without unpacking them first.

@@ -13,6 +13,8 @@ Layout
   csrc/permutation.hip   the order of a mix step drawn on the device (ChaCha20 sort keys + a stable radix argsort), one call per mix step
   mix.py                 re-randomising and shuffling ciphertexts under the shared public key, the order drawn on the device, a whole
                          mix step from a key (functions on an Engine)
+  csrc/matrix_combine.hip  G linear combinations of the same rows by a weight matrix, on the matrix cores (k_combine_m) or the vector ALU
+  combine.py             combining ciphertexts by a weight matrix: out = weights^T . rows (functions on an Engine)
   scan.py                scanning a batch for the rows a key decrypts to a tagged message; only the hits come back (functions on an Engine)
   ntru.py                `NTRU` class + pure functions with the reference's names and semantics (index.js)
   js/                    N-API addon + ES-module shim exposing the same surface to Node.js
@@ -22,7 +24,8 @@ raises `EngineError` when it (or a GPU) is missing.
 """
 from .engine import (FLAG_NOT_BITS, FLAG_PAD_NONZERO, Engine, EngineError, MultiEngine, library_path,  # noqa: F401
                      load_library)
-from . import lift, mix, packed, scan, sharding  # noqa: F401
+from . import combine, lift, mix, packed, scan, sharding  # noqa: F401
+from .combine import combine_batch, combine_batch_dev  # noqa: F401
 from .mix import reencrypt_batch, reencrypt_batch_dev  # noqa: F401
 from .mix import (argsort_keys_dev, draw_permutation, draw_permutation_dev, mix_batch, mix_batch_dev)  # noqa: F401
 from .scan import (scan_bytes_batch, scan_bytes_batch_dev, scan_bytes_packed_batch,  # noqa: F401
@@ -32,4 +35,4 @@ from .packed import (decrypt_packed_batch, decrypt_packed_batch_dev, pack_rows, 
 from .ntru import (NTRU, addCiphertexts, addPolynomials, bigintToBits, bitsToBigInt, bitsToString, degree,  # noqa: F401
                    dividePolynomials, expandArray, extendedEuclideanAlgorithm, generateCustomArray, modInverse,
                    multiplyPolynomials, multiplyPolynomialsByScalar, packOutput, polyInv, stringToBits, checkWitnesses,
-                   subtractPolynomials, sumCiphertexts, trimPolynomial, unpackInput)
+                   combineCiphertexts, subtractPolynomials, sumCiphertexts, trimPolynomial, unpackInput)

@@ -28,6 +28,9 @@
 //   permutation.hip          the order of a mix step drawn on the device: ChaCha20 sort keys (k_perm_keys), a stable radix argsort without
 //                            global atomics (k_perm_hist / k_perm_offsets / k_perm_scatter per byte, k_perm_finish), and a whole mix step
 //                            from a key: sample r, draw the order, re-encrypt (kernels, *_dev and host-pointer entry points)
+//   matrix_combine.hip       G linear combinations of the same rows by a weight matrix, out = W^T rows: the contraction over the batch axis on
+//                            the int8 matrix cores (k_combine_m), the vector-ALU twin (k_combine_v), the finish over row blocks (kernels, *_dev
+//                            and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

@@ -89,6 +89,8 @@ _SIGS = {
     "ntru_multi_set_lift": _sig("p i"),
     **_both("ntru_sum_groups", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_batch", "p iii ppppp ll ppppp"),
+    # combining ciphertexts by a weight matrix: the functions are in combine.py
+    **_both("ntru_combine_batch", "p ii pp l i p"),
     # ciphertexts as packOutput(q - 1, N, e) rows: the methods are in packed.py
     **_both("ntru_sum_groups_packed", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_packed_batch", "p iii ppppp ll ppppp"),

@@ -263,6 +263,47 @@ export function sumCiphertexts(rows, q, offsets = null, weights = null) {
   return offsets == null ? sums[0] : sums;
 }
 
+// The weight matrix of a combination, row b = the G weights of ciphertext b: an Array of B arrays of G numbers, or a Uint16Array[B * G]
+// with G.  -> { w: Uint16Array[B * G] reduced below q, G }
+function combineWeights(weights, B, G, q) {
+  if (!(weights instanceof Uint16Array)) {
+    const rows = Array.from(weights, r => Array.from(r));
+    if (rows.length !== B) throw new TypeError(`combine: ${rows.length} rows of weights for ${B} rows`);
+    G = rows.length ? rows[0].length : G;
+    if (rows.some(r => r.length !== G)) throw new TypeError('combine: every row of weights must hold G weights');
+    weights = Uint16Array.from(rows.flat(), x => ((x % q) + q) % q);
+  }
+  if (!Number.isInteger(G) || G < 1 || G > 4096) throw new RangeError('combine: need 1 <= G <= 4096');
+  if (weights.length !== B * G) throw new TypeError(`combine: weights must hold B * G = ${B * G} values`);
+  return { w: weights, G };
+}
+
+// out[g] = (sum over b of w[b * G + g] * rows[b]) mod q for the dense rows flat: Uint16Array[B * N] -> Uint16Array[G * N].  Composed from
+// sumGroups, one weighted sum of ONE group per output column: the same bytes as the engine's ntru_combine_batch, which reads the rows
+// once, but not that call (INTEGRATION.md, "Combining ciphertexts"): from Node this is correct, not fast.
+function combineRows(N, q, flat, B, w, G) {
+  const out = new Uint16Array(G * N), col = new Uint16Array(B), one = new Uint16Array(N);
+  for (let g = 0; g < G && B > 0; g++) {
+    for (let b = 0; b < B; b++) col[b] = w[b * G + g];
+    engine().sumGroups(N, q, flat, col, null, B, 1, B, one);
+    out.set(one, g * N);
+  }
+  return out;
+}
+
+// G linear combinations of the same ciphertexts: weights[b] holds the G weights of rows[b] (or weights: Uint16Array[B * G] and G), and
+// combination g is addPolynomials folded over every row scaled by weights[b][g] as multiplyPolynomialsByScalar does.  Returns the G
+// trimmed sums; entry g is sumCiphertexts(rows, q, null, column g of weights).
+export function combineCiphertexts(rows, q, weights, G = null) {
+  const B = rows.length;
+  const N = Math.max(2, ...rows.map(r => r.length));
+  const flat = new Uint16Array(B * N);
+  rows.forEach((r, b) => flat.set(r, b * N));
+  const m = combineWeights(weights, B, G, q);
+  const out = combineRows(N, q, flat, B, m.w, m.G);
+  return Array.from({ length: m.G }, (_, g) => trimPolynomial(Array.from(out.subarray(g * N, (g + 1) * N))));
+}
+
 // Rows of packOutput(q - 1, N, e) field elements, BigUint64Array[B * outputSize * 4] -> the dense rows Uint16Array[B * N]: unpackInput of
 // every row with the pad dropped, whatever the pad and the bits above an element's fields hold.
 function unpackRows(N, q, packed, B) {
@@ -595,6 +636,16 @@ export default class NTRU {
     const second = this._centredSecondStage(r1, G);
     if (!wantWitness) return { sum, value: second.value, quotient1: null, remainder1: null, quotient2: null };
     return { sum, value: second.value, quotient1: q1, remainder1: r1, quotient2: second.quotient2 };
+  }
+
+  // ---- combinations (additive): combines the ciphertexts rows: Uint16Array[B*N] by the weight matrix weights (Uint16Array[B*G] below q
+  // with G, or an Array of B arrays of G numbers) and decrypts every combination, in this instance's lift.
+  // -> { sum, value, quotient1, remainder1, quotient2 }, [G*N] each: row g is what decryptBatch returns for sum row g.  Composed from
+  // sumGroups and decryptBatch (combineRows above).
+  combineBatch(rows, B, weights, G = null, wantWitness = true) {
+    const m = combineWeights(weights, B, G, this.q);
+    const sum = combineRows(this.N, this.q, rows, B, m.w, m.G);
+    return { sum, ...this.decryptBatch(sum, m.G, wantWitness) };
   }
 
   // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed

@@ -18,6 +18,7 @@ import secrets
 
 import numpy as np
 
+from . import combine as combine_calls
 from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
@@ -248,6 +249,18 @@ def sumCiphertexts(rows, q, offsets=None, weights=None, engine=None):
     return sums if offsets is not None else sums[0]
 
 
+def combineCiphertexts(rows, q, weights, engine=None):
+    """G linear combinations of the same ciphertexts in one device pass: weights[b] holds the G weights of rows[b] (lists of
+    coefficients in [0, q)), and combination g is addPolynomials (index.js:235-244) folded over every row scaled by weights[b][g] as
+    multiplyPolynomialsByScalar does.  Returns the G trimmed sums; sumCiphertexts(rows, q, weights=column g) is entry g."""
+    eng = engine or default_engine()
+    rows = [list(r) for r in rows]
+    N = max([len(r) for r in rows] + [2])
+    weights = np.asarray([[int(w) % q for w in row] for row in weights], dtype=np.uint16)
+    out = combine_calls.combine_batch(eng, N, q, np.array([expandArray(r, N) for r in rows], dtype=np.uint16).reshape(-1, N), weights)
+    return [trimPolynomial(row.tolist()) for row in out]
+
+
 def packOutput(maxVal, dataLen, data, engine=None):
     """index.js:572-596: same dict as the reference; `expected` is a list of Python ints (the reference's BigInts)."""
     eng = engine or default_engine()
@@ -469,6 +482,21 @@ class NTRU:
         with self._lifted():
             total, value, q1, r1, q2 = self.engine.tally_decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), rows,
                                                                        offsets=offsets, weights=weights, want_witness=wantWitness)
+        return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    def combineBatch(self, rows, weights, want_witness=True):
+        """Combines the ciphertexts `rows` [B][N] by the weight matrix `weights` [B][G] (row b: the weights of row b in the G outputs)
+        and decrypts every combination.  Returns {"sum", "value", "quotient1", "remainder1", "quotient2"} as [G][N] arrays (the witness
+        arrays are None without want_witness): row g equals the witness arrays of decryptBits(sum[g])."""
+        N, q, p = self.N, self.q, self.p
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")
+        rows = np.asarray(rows).reshape(-1, N)
+        weights = np.asarray(weights, dtype=np.int64) % q
+        total = combine_calls.combine_batch(self.engine, N, q, rows, weights)
+        with self._lifted():
+            value, q1, r1, q2 = self.engine.decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), total,
+                                                          want_witness=want_witness)
         return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
 
     # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
