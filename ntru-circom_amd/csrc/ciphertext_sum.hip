@@ -44,30 +44,26 @@ constexpr int FIN_COLS = 32, FIN_SLICES = 32;   // k_sum_groups_finish: 1024 thr
 constexpr int FIN_Y = 32;
 
 typedef u32 u32x3 __attribute__((ext_vector_type(3)));
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
 
-// The 8 coefficients at p (2-byte aligned), as u32, from the aligned 16 bytes at or just below p and the dword behind them.  The
-// caller has checked that p + 10 elements lie inside the array, so a batch of these loads has no branch between them.
-__device__ __forceinline__ void load8_raw(const u16 *p, u32 (&d)[5]) {
-  const u16 *ap = p - (((uintptr_t)p >> 1) & 1u);     // 4-byte aligned; at most 2 bytes below p, inside p's own dword
-  const u32x4 v = *(const u32x4_a4 *)ap;
-  d[4] = *(const u32 *)(ap + 8);
-  d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-}
-__device__ __forceinline__ void shift8(const u16 *p, const u32 (&d)[5], u32 (&x)[8]) {
-  const u32 sh = (u32)((uintptr_t)p >> 1) & 1u;
+// The 8 coefficients at p as u32, from load8_raw's five dwords (sum_groups_common.h): the pairs, split into halves.
+__device__ __forceinline__ void split8(const u32 (&w)[4], u32 (&x)[8]) {
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const u32 w = __builtin_amdgcn_alignbyte(d[k + 1], d[k], 2u * sh);
-    x[2 * k] = w & 0xffffu;
-    x[2 * k + 1] = w >> 16;
+    x[2 * k] = w[k] & 0xffffu;
+    x[2 * k + 1] = w[k] >> 16;
   }
+}
+__device__ __forceinline__ void shift8(const u16 *p, const u32 (&d)[5], u32 (&x)[8]) {
+  u32 w[4];
+  pairs8(half_dword(p), d, w);
+  split8(w, x);
 }
 // The same with every element checked against `lim`, the end of the array: the last rows only.
 __device__ __forceinline__ void load8_checked(const u16 *p, const u16 *lim, u32 (&x)[8]) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) x[k] = p + k < lim ? (u32)p[k] : 0u;
+  u32 w[4];
+  pairs8_checked(p, lim, w);
+  split8(w, x);
 }
 
 template <bool POW2, bool WEIGHTED, class Acc>
@@ -85,7 +81,7 @@ template <int R, bool POW2, bool WEIGHTED, class Acc>
 __device__ __forceinline__ void row_batch(Acc (&acc)[8], const u16 *p, int N, const u16 *w) {
   u32 d[R][5];
 #pragma unroll
-  for (int j = 0; j < R; j++) load8_raw(p + j * (long)N, d[j]);
+  for (int j = 0; j < R; j++) load8_raw(p + j * (long)N, half_dword(p + j * (long)N), d[j]);
 #pragma unroll
   for (int j = 0; j < R; j++) {
     u32 x[8];
@@ -236,9 +232,7 @@ __global__ void __launch_bounds__(FIN_COLS * FIN_SLICES) k_sum_groups_finish(int
 }  // namespace
 
 int ntru_check_sum_args(const ntru_engine *eng, int N, int mod, bool uniform, int64_t K, int64_t G, const char *who) {
-  if (N < 2 || N > NTRU_MAX_N)
-    return fail(NTRU_ERR_ARG, std::string(who) + ": need 2 <= N <= " + std::to_string(NTRU_MAX_N) + ", got N = " + std::to_string(N));
-  if (mod < 2 || mod > 65536) return fail(NTRU_ERR_ARG, std::string(who) + ": need 2 <= mod <= 65536, got " + std::to_string(mod));
+  if (int rc = ntru_check_ring_mod(std::string(who) + ": ", N, mod)) return rc;
   if (G < 0) return fail(NTRU_ERR_ARG, std::string(who) + ": negative group count");
   if (uniform && K < 1) return fail(NTRU_ERR_ARG, std::string(who) + ": uniform groups need K >= 1, got " + std::to_string(K));
   if (uniform && G > 0 && K > (int64_t)0x7fffffffffffLL / G) return fail(NTRU_ERR_ARG, std::string(who) + ": G * K is out of range");
@@ -258,7 +252,7 @@ int launch_sum(ntru_engine *eng, int N, int mod, const void *d_rows, const uint1
     });
   };
   if (int rc = launch_sum_rows(eng, N, mod, w, (N + SG_TILE - 1) / SG_TILE, SG_WAVES_PER_CU, SG_THREADS, d_out, enqueue)) return rc;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sum_groups<%d,%d>", (int)pow2, d_weights ? 1 : 0);
+  note_kernel(eng, "k_sum_groups", (int)pow2, d_weights ? 1 : 0);
   return NTRU_OK;
 }
 
@@ -322,10 +316,12 @@ int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, cons
   const size_t out_row = (size_t)N * 2, out_bytes = (size_t)G * out_row;
   if (B == 0) { memset(out, 0, out_bytes); return NTRU_OK; }
   HIP_TRY(hipSetDevice(eng->device));
-  const size_t off_at = ntru_up256(out_bytes), tmp_at = off_at + ntru_up256(offsets ? (size_t)(G + 1) * 8 : 0);
-  if (int rc = ntru_grow_dev(&eng->shared_dev, tmp_at + out_row)) return rc;
-  char *dev = (char *)eng->shared_dev.p;
-  uint16_t *d_out = (uint16_t *)dev, *d_tmp = (uint16_t *)(dev + tmp_at);
+  Carve c;
+  const size_t out_at = c.take(out_bytes), off_at = c.take(offsets ? (size_t)(G + 1) * 8 : 0), tmp_at = c.total;
+  ResidentHold hold(eng, who, tmp_at + out_row);                         // (the last array, one row, is not rounded up)
+  if (hold.rc) return hold.rc;
+  char *dev = hold.p;
+  uint16_t *d_out = (uint16_t *)(dev + out_at), *d_tmp = (uint16_t *)(dev + tmp_at);
   const int64_t *d_off = offsets ? (const int64_t *)(dev + off_at) : nullptr;
   HIP_TRY(hipMemset(d_out, 0, out_bytes));                               // empty groups; every other row is stored by some chunk
   if (offsets) HIP_TRY(hipMemcpy(dev + off_at, offsets, (size_t)(G + 1) * 8, hipMemcpyHostToDevice));
@@ -350,8 +346,9 @@ int ntru_sum_groups_host(ntru_engine *eng, const char *who, int N, int mod, cons
     if (start_of(g_first) < a) {                                         // reaches in from the chunk before: add to its part
       gr.g0 = g_first; gr.G = 1;
       if (gr.off) gr.off = d_off + g_first;
-      if (int rc2 = launch_sum(eng, N, mod, dr, dw, gr, d_tmp)) return rc2;
-      if (int rc2 = ntru_add_batch_dev(eng, N, mod, d_out + g_first * N, d_tmp, 1, d_out + g_first * N)) return rc2;
+      if (int rc2 = accumulate_chunk(eng, N, mod, false, 1, d_out + g_first * N, d_tmp,
+                                     [&](uint16_t *dst) { return launch_sum(eng, N, mod, dr, dw, gr, dst); }))
+        return rc2;
       g0 = g_first + 1;
     }
     if (g0 > g_last) return (int)NTRU_OK;

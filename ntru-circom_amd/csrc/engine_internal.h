@@ -41,6 +41,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -94,7 +95,9 @@ struct ntru_engine {
   hipStream_t st_up, st_comp, st_down;   // the three stage streams of the host path (created at first use)
   hipStream_t st_aux;       // forked from / joined back into the caller's stream inside ONE *_dev call (key inversion: the mod-p inversion,
   hipEvent_t ev_fork, ev_join;   // vector-ALU bound, runs beside the Newton chain on the matrix cores); created at first use
-  GrowBuf shared_dev;       // shared key rows of the host path (h, f, fp)
+  GrowBuf shared_dev;       // what ONE host form keeps on the device across the chunks of its Pipeline run (sums and offsets, combined
+                            // rows, scan counts and hits, a drawn order); taken through ResidentHold only
+  const char *shared_holder = nullptr;   // the host form that holds shared_dev now (ResidentHold), or NULL
   GrowBuf scratch_dev;      // temporaries of *_dev calls (Newton rounds, generic family) on the caller's stream
   GrowBuf keygen_work;      // workspace of the host-pointer ntru_keygen_batch (ntru_keygen_workspace_bytes of one chunk)
   hipStream_t scratch_stream;   // the stream whose work used scratch_dev last, and an event recorded behind that work: a call on
@@ -139,6 +142,76 @@ static inline int fail(int code, const std::string &msg) { return ntru_fail(code
 static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // Bytes rounded up to the 256-byte granule at which scratch, workspace and staging arrays are carved.
 static inline size_t ntru_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// Arrays carved out of one buffer, one after the other at that granule: take(bytes) is where the next array starts, `total` what
+// has been taken so far.
+struct NTRU_HIDDEN Carve {
+  size_t total = 0;
+  size_t take(size_t bytes) {
+    const size_t at = total;
+    total += ntru_up256(bytes);
+    return at;
+  }
+};
+
+// eng->shared_dev grown to `bytes` and held by the host form `what` until the guard leaves scope.  Growing frees the old buffer, so a
+// host form that holds it must not call another that takes it: the second hold fails (NTRU_ERR_ARG, both names) and grows nothing.
+struct NTRU_HIDDEN ResidentHold {
+  ntru_engine *eng;
+  char *p = nullptr;
+  int rc;
+  ResidentHold(ntru_engine *e, const char *what, size_t bytes) : eng(e) {
+    if (e->shared_holder) {
+      rc = ntru_fail(NTRU_ERR_ARG, std::string(what) + ": the engine's resident buffer is held by " + e->shared_holder);
+      return;
+    }
+    if ((rc = ntru_grow_dev(&e->shared_dev, bytes))) return;
+    e->shared_holder = what;
+    p = (char *)e->shared_dev.p;
+  }
+  ~ResidentHold() { if (rc == NTRU_OK) eng->shared_holder = nullptr; }
+  ResidentHold(const ResidentHold &) = delete;
+  ResidentHold &operator=(const ResidentHold &) = delete;
+};
+
+// f(first row, rows) for consecutive passes of at most `pass` rows over B rows; the first non-zero return ends the walk.
+template <class F>
+static inline int for_each_pass(int64_t B, int64_t pass, F f) {
+  for (int64_t o = 0; o < B; o += pass)
+    if (int rc = f(o, std::min<int64_t>(pass, B - o))) return rc;
+  return NTRU_OK;
+}
+// An optional array `elems` elements on.
+template <class T>
+static inline T *rows_at(T *p, int64_t elems) { return p ? p + elems : nullptr; }
+
+// Whether [a, a + na) and [b, b + nb) share a byte; nothing overlaps a NULL pointer or an empty range.
+static inline bool ntru_ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// One chunk's share of `rows` result rows that several chunks add up: launch(dst) enqueues it; the first chunk stores into d_out, every
+// later one stores beside it in d_tmp and adds.
+template <class Launch>
+static inline int accumulate_chunk(ntru_engine *eng, int N, int mod, bool first, int64_t rows, uint16_t *d_out, uint16_t *d_tmp,
+                                   Launch launch) {
+  if (int rc = launch(first ? d_out : d_tmp)) return rc;
+  return first ? (int)NTRU_OK : ntru_add_batch_dev(eng, N, mod, d_out, d_tmp, rows, d_out);
+}
+
+// (N, mod) of the sums and combinations of rows; `who` ends where the message begins ("name: ").
+static inline int ntru_check_ring_mod(const std::string &who, int N, int mod) {
+  if (N < 2 || N > NTRU_MAX_N) return fail(NTRU_ERR_ARG, who + "need 2 <= N <= " + std::to_string(NTRU_MAX_N) + ", got N = " + std::to_string(N));
+  if (mod < 2 || mod > 65536) return fail(NTRU_ERR_ARG, who + "need 2 <= mod <= 65536, got " + std::to_string(mod));
+  return NTRU_OK;
+}
+
+// What ntru_engine_last_kernel() reports: a plain name, or a templated family's name<K> / name<K,me> (me < 0: no second argument).
+static inline void note_kernel(ntru_engine *eng, const char *name) { snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s", name); }
+static inline void note_kernel(ntru_engine *eng, const char *family, int K, int me) {
+  if (me >= 0) snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s<%d,%d>", family, K, me);
+  else snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s<%d>", family, K);
+}
 // Workgroups of 256 for an elementwise kernel.  Kernels that move 16 bytes per lane and access (streaming = true) get TWO per CU: more
 // resident waves lower the HBM rate (the add of two ciphertext batches: 5.0 TB/s with 8 per CU, 5.9 with 2, 4.8 with 1:
 // profiles/archive/r03_ab_elementwise_grid.txt); element-per-lane kernels keep 8.

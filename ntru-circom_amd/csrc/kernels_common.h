@@ -102,9 +102,4 @@ static int launch_resident(ntru_engine *eng, Kern kern, long work_blocks, int th
   return NTRU_OK;
 }
 
-static inline void note_kernel(ntru_engine *eng, const char *family, int K, int me) {
-  if (me >= 0) snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s<%d,%d>", family, K, me);
-  else snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s<%d>", family, K);
-}
-
 #endif

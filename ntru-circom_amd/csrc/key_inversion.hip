@@ -374,7 +374,7 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
   HIP_TRY(hipMemsetAsync(d_flags, 0, (size_t)B, eng->stream));
   if (!d_fq) {                                     // only the inverse modulo p was asked for (polyInv(f, I, 3))
     if (int rc = launch_invert<3>(eng, N, d_f, (long)B, nullptr, d_fp, d_flags, NTRU_FLAG_NOT_UNIT_MODP)) return rc;
-    snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_invert_key");
+    note_kernel(eng, "k_invert_key");
     return NTRU_OK;
   }
   // The mod-p inversion (k_invert_key<3>: bit-sliced division steps, vector-ALU bound, no LDS at the usual sizes) depends on f only, and
@@ -392,12 +392,13 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
   bits_of[rounds] = k;
   for (int r = rounds; r > 0; r--) bits_of[r - 1] = (bits_of[r] + 1) / 2;
   const int64_t C = B < INVERT_CHUNK ? B : INVERT_CHUNK;     // Newton temporaries for C keys at a time
-  const size_t row = (size_t)N * 2, part = rounds > 0 ? ntru_up256((size_t)C * row) : 0;
-  const size_t fl_bytes = d_fp ? ntru_up256((size_t)B) : 0;
-  ScratchHold hold(eng, 4 * part + fl_bytes + 256);          // engine-owned, grown on demand, never per call; released (event
+  const size_t part = rounds > 0 ? (size_t)C * N * 2 : 0;    // one Newton temporary
+  Carve c;
+  const size_t at_f16 = c.take(part), at_t = c.take(part), at_u = c.take(part), at_qs = c.take(part), at_flags = c.take(d_fp ? (size_t)B : 0);
+  ScratchHold hold(eng, c.total + 256);                      // engine-owned, grown on demand, never per call; released (event
   if (hold.rc) return hold.rc;                               // recorded) on every way out of this function
   char *const sc = hold.p;
-  uint8_t *const flags_p = (uint8_t *)(sc + 4 * part);
+  uint8_t *const flags_p = (uint8_t *)(sc + at_flags);
   hipStream_t main_stream = eng->stream;
   bool forked = false;
   if (d_fp) {
@@ -432,7 +433,7 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
   // the reference runs log2(q) - 1 of them, the unique inverse mod q is reached once 2^rounds >= log2(q))
   if (int rc = launch_invert<2>(eng, N, d_f, (long)B, d_fq, nullptr, d_flags, NTRU_FLAG_NOT_UNIT_MOD2)) return rc;
   if (rounds > 0) {
-    struct { void *p; } f16{sc}, t{sc + part}, u{sc + 2 * part}, qs{sc + 3 * part};
+    struct { void *p; } f16{sc + at_f16}, t{sc + at_t}, u{sc + at_u}, qs{sc + at_qs};
     bool need_f16 = false;                                 // f as u16 residues: only the vector-ALU form of a round reads it
     for (int r = 0; r < rounds; r++) need_f16 |= !ntru_newton_round_matrix_applies(eng, N, bits_of[r], bits_of[r + 1]);
     for (int64_t o = 0; o < B; o += C) {
@@ -466,6 +467,6 @@ extern "C" int ntru_invert_key_batch_dev(ntru_engine_t *eng, int N, int q, int p
     }
   }
   if (int rc = join()) return rc;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_invert_key");
+  note_kernel(eng, "k_invert_key");
   return NTRU_OK;
 }

@@ -95,13 +95,14 @@ Layout layout_of(int N, int64_t B) {
   Layout L;
   L.rows = std::max<int64_t>(1, std::min<int64_t>(B, KG_PASS_ROWS));
   const size_t r = (size_t)L.rows;
-  L.list = 0;
-  L.count = L.list + ntru_up256(4 * r);
-  L.f = L.count + 256;
-  L.fq = L.f + ntru_up256(r * N);
-  L.fp = L.fq + ntru_up256(2 * r * N);
-  L.fl = L.fp + ntru_up256(r * N);
-  L.total = L.fl + ntru_up256(r);
+  Carve c;
+  L.list = c.take(4 * r);
+  L.count = c.take(256);
+  L.f = c.take(r * N);
+  L.fq = c.take(2 * r * N);
+  L.fp = c.take(r * N);
+  L.fl = c.take(r);
+  L.total = c.total;
   return L;
 }
 
@@ -200,7 +201,7 @@ extern "C" int ntru_keygen_batch_dev(ntru_engine_t *eng, int N, int q, int p, in
     HIP_TRY(hipGetLastError());
   }
   if (int rc = ntru_public_key_batch_dev(eng, N, q, p, d_fq, d_g, B, d_h)) return rc;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_keygen");
+  note_kernel(eng, "k_keygen");
   return NTRU_OK;
 }
 

@@ -18,7 +18,7 @@
 // well): the number of planes follows from the modulus's bit count, the bytes do not change.
 // A lane's fragment is 16 consecutive contraction indices (matrix_common.h), and the contraction index is the batch row, so both
 // operands pass through an LDS transpose: a thread loads 8 columns of two quads of consecutive rows (coalesced 16-byte loads from
-// 4-byte aligned addresses + v_alignbyte, ciphertext_sum.hip), takes the digits (v_perm_b32 gathers the bytes of four rows) and writes
+// 4-byte aligned addresses + v_alignbyte, sum_groups_common.h), takes the digits (v_perm_b32 gathers the bytes of four rows) and writes
 // one dword = 4 batch bytes per column, quad and plane.  The images are [slot][80 bytes] (64 batch bytes + 16: an odd multiple of 16,
 // so that a fragment is one conflict-free ds_read_b128); column 8 c + j of the 256 sits in slot 32 j + c, which makes the dword writes
 // of a half-wave (8 values of c x 4 row quads) hit 32 different banks; matrix tile j therefore holds the columns = j (mod 8), which
@@ -48,25 +48,16 @@ constexpr int CM_PITCH = CM_ROWS + 16;       // bytes per image slot: an odd mul
 constexpr int CV_WG_PER_CU = 8;
 constexpr int CV_OUTS = 4;                   // outputs per thread of k_combine_v
 constexpr long CB_MIN_ROWS = 64;             // rows per row block, at least; a block is a multiple of it
-constexpr long CB_MAX_BLOCKS = 32768;        // row blocks: k_combine_finish adds that many reduced partials in a u32
+constexpr long CB_MAX_BLOCKS = SUM_MAX_ROW_BLOCKS;   // row blocks: k_combine_finish adds that many reduced partials in a u32
 constexpr size_t CB_MAX_PART = (size_t)256 << 20;
 
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
-
-// The 8 coefficients at p (2-byte aligned) as 4 dwords of two, from the aligned 16 bytes at or just below p and the dword behind them.
-// The caller has checked that p + 10 elements lie inside the array.
+// The 8 coefficients at p (2-byte aligned) as 4 dwords of two: the row read of sum_groups_common.h, raw and then pairs.  The caller has
+// checked that p + 10 elements lie inside the array.
 __device__ __forceinline__ void load8_pairs(const u16 *p, u32 (&x)[4]) {
-  const u32 sh = (u32)((uintptr_t)p >> 1) & 1u;
-  const u16 *ap = p - sh;                              // 4-byte aligned; at most 2 bytes below p, inside p's own dword
-  const u32x4 v = *(const u32x4_a4 *)ap;
-  const u32 d[5] = {v[0], v[1], v[2], v[3], *(const u32 *)(ap + 8)};
-#pragma unroll
-  for (int k = 0; k < 4; k++) x[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], 2u * sh);
-}
-// The same element by element, every one checked against `lim`, the end of the array: the last row or two only.
-__device__ __forceinline__ void load8_pairs_checked(const u16 *p, const u16 *lim, u32 (&x)[4]) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) x[k] = (p + 2 * k < lim ? (u32)p[2 * k] : 0u) | (p + 2 * k + 1 < lim ? (u32)p[2 * k + 1] << 16 : 0u);
+  const u32 sh = half_dword(p);
+  u32 d[5];
+  load8_raw(p, sh, d);
+  pairs8(sh, d, x);
 }
 
 // Byte 0 (even) and byte 2 (odd) of four dwords, each as one dword with a's byte first: the low bytes of two packed columns of four rows.
@@ -137,7 +128,7 @@ __global__ void __launch_bounds__(CB_THREADS) k_combine_m(int N, u32 mod, const 
       if (row < u.r1 && c0 < N) {
         const long at = row * N + c0;
         if (at + 10 <= total) load8_pairs(rows + at, xw[i]);
-        else load8_pairs_checked(rows + at, lim, xw[i]);
+        else pairs8_checked(rows + at, lim, xw[i]);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; k++) xw[i][k] = 0;
@@ -274,17 +265,15 @@ __global__ void __launch_bounds__(CB_THREADS) k_combine_finish(long total, u32 m
 int check_combine(const ntru_engine *eng, int N, int mod, const uint16_t *rows, const uint16_t *weights, int64_t B, int G,
                   const uint16_t *out) {
   const std::string who = "ntru_combine_batch: ";
-  if (N < 2 || N > NTRU_MAX_N) return fail(NTRU_ERR_ARG, who + "need 2 <= N <= " + std::to_string(NTRU_MAX_N) + ", got N = " + std::to_string(N));
-  if (mod < 2 || mod > 65536) return fail(NTRU_ERR_ARG, who + "need 2 <= mod <= 65536, got " + std::to_string(mod));
+  if (int rc = ntru_check_ring_mod(who, N, mod)) return rc;
   if (G < 1 || G > NTRU_COMBINE_MAX_G)
     return fail(NTRU_ERR_ARG, who + "need 1 <= G <= " + std::to_string(NTRU_COMBINE_MAX_G) + ", got G = " + std::to_string(G));
   if (B < 0 || B > ((int64_t)1 << 31)) return fail(NTRU_ERR_ARG, who + "need 0 <= B <= 2^31, got B = " + std::to_string(B));
   if (!out) return fail(NTRU_ERR_ARG, who + "NULL buffer (out)");
   if (B > 0 && (!rows || !weights)) return fail(NTRU_ERR_ARG, who + std::string("NULL buffer (") + (rows ? "weights" : "rows") + ")");
-  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)G * N * 2;
-  auto meets = [&](const void *p, size_t bytes) { return bytes && (uintptr_t)p < o1 && o0 < (uintptr_t)p + bytes; };
-  if (meets(rows, (size_t)B * N * 2)) return fail(NTRU_ERR_ARG, who + "out overlaps rows");
-  if (meets(weights, (size_t)B * G * 2)) return fail(NTRU_ERR_ARG, who + "out overlaps weights");
+  const size_t out_bytes = (size_t)G * N * 2;
+  if (ntru_ranges_overlap(out, out_bytes, rows, (size_t)B * N * 2)) return fail(NTRU_ERR_ARG, who + "out overlaps rows");
+  if (ntru_ranges_overlap(out, out_bytes, weights, (size_t)B * G * 2)) return fail(NTRU_ERR_ARG, who + "out overlaps weights");
   if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
   return NTRU_OK;
 }
@@ -295,7 +284,7 @@ int launch_combine(ntru_engine *eng, int N, int mod, const uint16_t *d_rows, con
                    uint16_t *d_out) {
   HIP_TRY(hipSetDevice(eng->device));
   const bool pow2 = is_pow2(mod);
-  const bool matrix = pow2 && (eng->path == 0 || eng->path == 4 || eng->path == 5);
+  const bool matrix = pow2 && matrix_path_allowed(eng);
   const int planes = mod <= 256 ? 1 : 2, gt = G <= 32 ? 1 : 2;          // k_combine_m: digit planes, output tiles per workgroup
   typedef void (*Kern)(int, u32, const u16 *, const u16 *, long, int, long, int, int, u32 *, u16 *);
   const Kern kern = !matrix ? (pow2 ? k_combine_v<true> : k_combine_v<false>)
@@ -357,15 +346,17 @@ extern "C" int ntru_combine_batch(ntru_engine_t *eng, int N, int mod, const uint
   const size_t out_bytes = (size_t)G * N * 2;
   if (B == 0) { memset(out, 0, out_bytes); return NTRU_OK; }
   HIP_TRY(hipSetDevice(eng->device));
-  const size_t tmp_at = ntru_up256(out_bytes);
-  if (int rc = ntru_grow_dev(&eng->shared_dev, 2 * tmp_at)) return rc;
-  uint16_t *d_out = (uint16_t *)eng->shared_dev.p, *d_tmp = (uint16_t *)((char *)eng->shared_dev.p + tmp_at);
+  Carve c;
+  const size_t out_at = c.take(out_bytes), tmp_at = c.take(out_bytes);
+  ResidentHold hold(eng, "ntru_combine_batch", c.total);
+  if (hold.rc) return hold.rc;
+  uint16_t *d_out = (uint16_t *)(hold.p + out_at), *d_tmp = (uint16_t *)(hold.p + tmp_at);
   Pipeline P(eng);
   const int ir = P.in(rows, (size_t)N * 2), iw = P.in(weights, (size_t)G * 2);
   int rc = P.run(B, ntru_chunk_items(B), [&](int64_t o, int64_t n, void **d) {
-    uint16_t *dst = o == 0 ? d_out : d_tmp;
-    if (int rc2 = launch_combine(eng, N, mod, (const uint16_t *)d[ir], (const uint16_t *)d[iw], n, G, dst)) return rc2;
-    return o == 0 ? (int)NTRU_OK : ntru_add_batch_dev(eng, N, mod, d_out, d_tmp, G, d_out);
+    return accumulate_chunk(eng, N, mod, o == 0, G, d_out, d_tmp, [&](uint16_t *dst) {
+      return launch_combine(eng, N, mod, (const uint16_t *)d[ir], (const uint16_t *)d[iw], n, G, dst);
+    });
   });
   if (rc) return rc;
   HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));

@@ -371,7 +371,7 @@ int ntru_launch_decrypt_pack_matrix(ntru_engine *eng, int N, int q, int p, const
   // the 2-bit image of the values lives in the e_hi stage behind the mod-p tables
   const size_t m3_end = ((((size_t)4 * N + 4) & ~(size_t)3) + (size_t)4 * N + 1 + 15) & ~(size_t)15, img = ((size_t)8 * (126 * out_size + 16) + 15) & ~(size_t)15;
   if (lds > 160 * 1024 || m3_end + img > (size_t)32 * mg.pitchA || 126 * out_size + 16 < 32 * mg.NT) return NTRU_NOT_TAKEN;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_mp");
+  note_kernel(eng, "k_decrypt_mp");
   return launch_resident(eng, k_decrypt_mp, (long)((B + 31) / 32), BLOCK_THREADS, lds, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value,
                          (unsigned long long *)d_packed, out_size);
 }
@@ -391,13 +391,13 @@ int ntru_launch_decrypt_matrix(ntru_engine *eng, int N, int q, int p, int ld, co
     const size_t m3 = ((((size_t)4 * N + 4) & ~(size_t)3) + (size_t)4 * N + 1 + 15) & ~(size_t)15;
     const size_t lds8 = 2 * ((size_t)64 * mg.pitchA + (size_t)256 * mg.NT) + m3 + (size_t)48 * mg.tpitch + (((size_t)q + 15) & ~(size_t)15);
     if (lds8 <= 160 * 1024) {
-      snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m8");
+      note_kernel(eng, "k_decrypt_m8");
       return launch_resident(eng, k_decrypt_m8, (nrb + 1) / 2, 2 * BLOCK_THREADS, lds8, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B,
                              d_value, d_quot1, d_rem1, d_quot2);
     }
   }
   if (lds > 160 * 1024) return NTRU_NOT_TAKEN;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_m");
+  note_kernel(eng, "k_decrypt_m");
   return launch_resident(eng, k_decrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, (u32)p, ntru_lift_addend(eng, q, p), d_f, d_fp, d_e, (long)B, d_value, d_quot1,
                          d_rem1, d_quot2);
 }

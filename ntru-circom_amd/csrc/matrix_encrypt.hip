@@ -39,6 +39,6 @@ int ntru_launch_encrypt_matrix(ntru_engine *eng, int N, int q, int ld, const uin
   const bool rows_dword_aligned = (ld & 3) == 0 && ((uintptr_t)d_r & 3) == 0, img_dword_aligned = (ld & 3) == 0 && ((uintptr_t)d_m & 3) == 0;
   const bool dma_fits = (N + 3 <= 1024 || (rows_dword_aligned && N <= 1024)) && (32 * ld + 3 <= 32768 || (img_dword_aligned && 32 * ld <= 32768));
   const bool md = eng->path != 4 && dma_fits;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, md ? "k_encrypt_md" : "k_encrypt_m");
+  note_kernel(eng, md ? "k_encrypt_md" : "k_encrypt_m");
   return launch_resident(eng, md ? k_encrypt_md : k_encrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, d_h, d_r, d_m, (long)B, d_e, d_quotE);
 }

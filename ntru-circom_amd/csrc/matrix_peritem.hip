@@ -575,7 +575,7 @@ int ntru_launch_polymul_matrix(ntru_engine *eng, int N, int mod, const uint16_t 
   if (!peritem_applies(eng, N, mod)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
   const bool one = mod <= 256;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_polymul_m");
+  note_kernel(eng, "k_polymul_m");
   return launch_peritem(eng, one ? k_polymul_m<true> : k_polymul_m<false>, B, pi_wave_bytes(pg, one ? 1 : 2), pg, (u32)mod, d_a, d_b, (long)B,
                         d_quot, d_rem);
 }
@@ -594,7 +594,7 @@ int ntru_launch_verify_keys_matrix(ntru_engine *eng, int N, int q, int p, const 
                                    uint8_t *d_quot_fp, uint8_t *d_rem_fp, uint16_t *d_quot_h, uint16_t *d_rem_h, uint8_t *d_flags) {
   if (p != 3 || !peritem_applies(eng, N, q)) return NTRU_NOT_TAKEN;
   const PGeom pg = make_pgeom(N);
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_verify_keys_m");
+  note_kernel(eng, "k_verify_keys_m");
   return launch_peritem(eng, k_verify_keys_m, B, pi_wave_bytes(pg, 2), pg, (u32)q, d_f, d_g, d_fq, d_fp, d_h, (long)B, d_quot_fq, d_rem_fq,
                         d_quot_fp, d_rem_fp, d_quot_h, d_rem_h, d_flags);
 }

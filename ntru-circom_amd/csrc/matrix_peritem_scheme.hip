@@ -250,7 +250,7 @@ extern "C" int ntru_encrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   HIP_TRY(hipSetDevice(eng->device));
   if (!peritem_applies(eng, N, q)) return encrypt_composed(eng, N, q, d_h, d_r, d_m, B, d_e, d_quotE);
   const PGeom pg = make_pgeom(N);
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_encrypt_pi_m");
+  note_kernel(eng, "k_encrypt_pi_m");
   return launch_peritem(eng, q <= 256 ? k_encrypt_pi_m<true> : k_encrypt_pi_m<false>, B, pi_wave_bytes(pg, 1), pg, (u32)q, d_h, d_r, d_m,
                         (long)B, d_e, d_quotE);
 }
@@ -265,7 +265,7 @@ extern "C" int ntru_decrypt_peritem_batch_dev(ntru_engine_t *eng, int N, int q, 
   HIP_TRY(hipSetDevice(eng->device));
   if (p != 3 || !peritem_applies(eng, N, q)) return decrypt_composed(eng, N, q, p, d_f, d_fp, d_e, B, d_value, d_quot1, d_rem1, d_quot2);
   const PGeom pg = make_pgeom(N);
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_decrypt_pi_m");
+  note_kernel(eng, "k_decrypt_pi_m");
   return launch_peritem(eng, q <= 256 ? k_decrypt_pi_m<true> : k_decrypt_pi_m<false>, B, pi_wave_bytes(pg, 2), pg, (u32)q, ntru_lift_addend(eng, q, 3), d_f, d_fp, d_e,
                         (long)B, d_value, d_quot1, d_rem1, d_quot2);
 }

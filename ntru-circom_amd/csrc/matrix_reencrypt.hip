@@ -59,7 +59,7 @@ int launch_reencrypt_matrix(ntru_engine *eng, int N, int q, const uint16_t *d_h,
   const long nrb = (long)((B + 31) / 32);
   const bool rows_dword_aligned = (N & 3) == 0 && ((uintptr_t)d_r & 3) == 0;
   const bool md = eng->path != 4 && (N + 3 <= 1024 || (rows_dword_aligned && N <= 1024));
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, md ? "k_reencrypt_md" : "k_reencrypt_m");
+  note_kernel(eng, md ? "k_reencrypt_md" : "k_reencrypt_m");
   return launch_resident(eng, md ? k_reencrypt_md : k_reencrypt_m, nrb, BLOCK_THREADS, lds, mg, (u32)q, d_h, d_r, d_e_in, (long)B_in,
                          (const long *)d_src, (long)B, d_e_out, d_quotE);
 }
@@ -68,20 +68,22 @@ int launch_reencrypt_matrix(ntru_engine *eng, int N, int q, const uint16_t *d_h,
 int launch_reencrypt_valu(ntru_engine *eng, int N, int q, const uint16_t *d_h, const uint8_t *d_r, const uint16_t *d_e_in, int64_t B_in,
                           const int64_t *d_src, int64_t B, uint16_t *d_e_out, uint16_t *d_quotE) {
   const int64_t pass = std::min<int64_t>(B, RE_PASS);
-  const size_t zbytes = ntru_up256((size_t)pass * N);
-  ScratchHold hold(eng, zbytes + (size_t)pass * N * 2);
+  Carve c;
+  const size_t at_zero = c.take((size_t)pass * N), at_enc0 = c.total;
+  ScratchHold hold(eng, at_enc0 + (size_t)pass * N * 2);          // (the last array is not rounded up)
   if (hold.rc) return hold.rc;
-  uint8_t *d_zero = (uint8_t *)hold.p;
-  uint16_t *d_enc0 = (uint16_t *)(hold.p + zbytes);
+  uint8_t *d_zero = (uint8_t *)hold.p + at_zero;
+  uint16_t *d_enc0 = (uint16_t *)(hold.p + at_enc0);
   HIP_TRY(hipMemsetAsync(d_zero, 0, (size_t)pass * N, eng->stream));
-  for (int64_t o = 0; o < B; o += RE_PASS) {
-    const int64_t n = std::min<int64_t>(RE_PASS, B - o);
-    if (int rc = ntru_launch_encrypt_valu(eng, N, q, d_h, d_r + o * N, d_zero, n, d_enc0, d_quotE ? d_quotE + o * N : nullptr)) return rc;
+  const int rc = for_each_pass(B, RE_PASS, [&](int64_t o, int64_t n) -> int {
+    if (int rc = ntru_launch_encrypt_valu(eng, N, q, d_h, d_r + o * N, d_zero, n, d_enc0, rows_at(d_quotE, o * N))) return rc;
     hipLaunchKernelGGL(k_add_gathered_rows, elementwise_grid(eng, (long)n * N), dim3(256), 0, eng->stream, N, (u32)q, d_enc0, d_e_in,
                        (long)B_in, (const long *)d_src, (long)o, (long)n, d_e_out);
     HIP_TRY(hipGetLastError());
-  }
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_add_gathered_rows");
+    return NTRU_OK;
+  });
+  if (rc) return rc;
+  note_kernel(eng, "k_add_gathered_rows");
   return NTRU_OK;
 }
 
@@ -94,8 +96,7 @@ int check_reencrypt(ntru_engine *eng, int N, int q, const void *h, const void *r
   if (!src && B > B_in) return fail(NTRU_ERR_ARG, "ntru_reencrypt_batch: without src, B must not exceed B_in");
   if (B == 0) { *done = true; return NTRU_OK; }
   if (!h || !r || !e_in || !e_out) return fail(NTRU_ERR_ARG, "ntru_reencrypt_batch: NULL buffer");
-  const uintptr_t a0 = (uintptr_t)e_in, a1 = a0 + (size_t)B_in * N * 2, b0 = (uintptr_t)e_out, b1 = b0 + (size_t)B * N * 2;
-  if (a0 < b1 && b0 < a1 && (src || a0 != b0))
+  if (ntru_ranges_overlap(e_in, (size_t)B_in * N * 2, e_out, (size_t)B * N * 2) && (src || e_in != e_out))
     return fail(NTRU_ERR_ARG, "ntru_reencrypt_batch: e_in and e_out overlap (only src == NULL with e_out == e_in works in place)");
   return NTRU_OK;
 }

@@ -215,7 +215,7 @@ int ntru_launch_encrypt_pack_rowimage(ntru_engine *eng, int N, int q, const uint
   if (((uintptr_t)d_packed & 15) != 0 || mg.NT > 4 * RI_WAVES || 32 * os > 64 * RI_WAVES * RP_MAXPI) return NTRU_NOT_TAKEN;
   const size_t lds = (size_t)32 * mg.tpitch + (size_t)32 * mg.pitchA + (size_t)ri_img_bytes(N) + 128;     // + the pad a row's last element reads
   if (lds > 160 * 1024) return NTRU_NOT_TAKEN;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_encrypt_wp");
+  note_kernel(eng, "k_encrypt_wp");
   return launch_resident(eng, q == 2048 ? k_encrypt_wp<11> : q == 4096 ? k_encrypt_wp<12> : k_encrypt_wp<13>, (long)((B + 31) / 32), RI_THREADS,
                          lds, mg, (u32)q, d_h, d_r, d_m, (long)B, os, (unsigned long long *)d_packed);
 }

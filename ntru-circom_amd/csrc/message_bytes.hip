@@ -243,7 +243,7 @@ extern "C" int ntru_bytes_to_rows_dev(ntru_engine_t *eng, int N, int nbytes, con
   hipLaunchKernelGGL(k_bytes_to_rows, grid_of(eng, (total / 16 + MB_THREADS - 1) / MB_THREADS), dim3(MB_THREADS), 0, eng->stream, N, nbytes,
                      d_bytes, total, d_m);
   HIP_TRY(hipGetLastError());
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_bytes_to_rows");
+  note_kernel(eng, "k_bytes_to_rows");
   return NTRU_OK;
 }
 
@@ -257,7 +257,7 @@ extern "C" int ntru_rows_to_bytes_dev(ntru_engine_t *eng, int N, int nbytes, con
   hipLaunchKernelGGL(k_rows_to_bytes, grid_of(eng, ((long)B + R - 1) / R), dim3(MB_THREADS), 0, eng->stream, N, nbytes, d_value, (long)B, R,
                      d_bytes, d_flags);
   HIP_TRY(hipGetLastError());
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_rows_to_bytes");
+  note_kernel(eng, "k_rows_to_bytes");
   return NTRU_OK;
 }
 
@@ -270,12 +270,10 @@ extern "C" int ntru_encrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, in
   ScratchHold hold(eng, (size_t)std::min<int64_t>(B, MB_PASS) * N);
   if (hold.rc) return hold.rc;
   uint8_t *d_m = (uint8_t *)hold.p;
-  for (int64_t o = 0; o < B; o += MB_PASS) {
-    const int64_t n = std::min<int64_t>(MB_PASS, B - o);
+  return for_each_pass(B, MB_PASS, [&](int64_t o, int64_t n) -> int {
     if (int rc = ntru_bytes_to_rows_dev(eng, N, nbytes, d_bytes + o * nbytes, n, d_m)) return rc;
-    if (int rc = ntru_encrypt_batch_dev(eng, N, q, d_h, d_r + o * N, d_m, n, d_e + o * N, d_quotE ? d_quotE + o * N : nullptr)) return rc;
-  }
-  return NTRU_OK;
+    return ntru_encrypt_batch_dev(eng, N, q, d_h, d_r + o * N, d_m, n, d_e + o * N, rows_at(d_quotE, o * N));
+  });
 }
 
 extern "C" int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *d_f, const uint8_t *d_fp,
@@ -287,12 +285,10 @@ extern "C" int ntru_decrypt_bytes_batch_dev(ntru_engine_t *eng, int N, int q, in
   ScratchHold hold(eng, (size_t)std::min<int64_t>(B, MB_PASS) * N);
   if (hold.rc) return hold.rc;
   uint8_t *d_value = (uint8_t *)hold.p;
-  for (int64_t o = 0; o < B; o += MB_PASS) {
-    const int64_t n = std::min<int64_t>(MB_PASS, B - o);
+  return for_each_pass(B, MB_PASS, [&](int64_t o, int64_t n) -> int {
     if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_e + o * N, n, d_value, nullptr, nullptr, nullptr)) return rc;
-    if (int rc = ntru_rows_to_bytes_dev(eng, N, nbytes, d_value, n, d_bytes + o * nbytes, d_flags ? d_flags + o : nullptr)) return rc;
-  }
-  return NTRU_OK;
+    return ntru_rows_to_bytes_dev(eng, N, nbytes, d_value, n, d_bytes + o * nbytes, rows_at(d_flags, o));
+  });
 }
 
 // ---- host-pointer form (the regular ones -- bytes_to_rows, rows_to_bytes, encrypt_bytes, decrypt_bytes -- are in ntru_host.hip) -------

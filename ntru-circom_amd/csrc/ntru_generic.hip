@@ -298,18 +298,18 @@ int run_generic(ntru_engine *eng, int op, int la, int lb, int64_t mod, const int
   long blocks = (long)eng->cus * 2;
   if (blocks > B) blocks = B;
   const size_t in_a = (size_t)B * la * 8, in_b = (size_t)B * lb * 8, rows = (size_t)B * cap * 8, lens = (size_t)B * 4;
-  const size_t o_a = 0, o_b = o_a + ntru_up256(in_a), o_w = o_b + ntru_up256(in_b),
-               o_0 = o_w + ntru_up256((size_t)blocks * NBUF * cap * 8), o_1 = o_0 + ntru_up256(rows), o_l0 = o_1 + ntru_up256(rows),
-               o_l1 = o_l0 + ntru_up256(lens), o_st = o_l1 + ntru_up256(lens), total = o_st + ntru_up256((size_t)B);
+  Carve c;
+  const size_t o_a = c.take(in_a), o_b = c.take(in_b), o_w = c.take((size_t)blocks * NBUF * cap * 8), o_0 = c.take(rows), o_1 = c.take(rows),
+               o_l0 = c.take(lens), o_l1 = c.take(lens), o_st = c.take((size_t)B);
   // the engine's shared scratch buffer, ordered against its last user on another stream (key inversion on stream A, then this
   // call after ntru_engine_set_stream(B): B waits for A's event before the first copy below lands in the buffer)
-  ScratchHold hold(eng, total);
+  ScratchHold hold(eng, c.total);
   if (hold.rc) return hold.rc;
   char *const d = hold.p;
   hipStream_t s = eng->stream;
   if (in_a) HIP_TRY(hipMemcpyAsync(d + o_a, a, in_a, hipMemcpyHostToDevice, s));
   if (in_b) HIP_TRY(hipMemcpyAsync(d + o_b, b, in_b, hipMemcpyHostToDevice, s));
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_generic");
+  note_kernel(eng, "k_generic");
   hipLaunchKernelGGL(k_generic, dim3((unsigned)blocks), dim3(64), 0, s, op, la, lb, (i64)mod, (const i64 *)(d + o_a),
                      (const i64 *)(d + o_b), (long)B, (i64 *)(d + o_w), cap, (i64 *)(d + o_0), (int *)(d + o_l0),
                      out1 ? (i64 *)(d + o_1) : nullptr, out1 ? (int *)(d + o_l1) : nullptr, (unsigned char *)(d + o_st));

@@ -305,13 +305,11 @@ extern "C" int ntru_decrypt_packed_batch_dev(ntru_engine_t *eng, int N, int q, i
   ScratchHold hold(eng, (size_t)std::min<int64_t>(B, PK_PASS) * N * 2);
   if (hold.rc) return hold.rc;
   uint16_t *d_e = (uint16_t *)hold.p;
-  for (int64_t o = 0; o < B; o += PK_PASS) {
-    const int64_t n = std::min<int64_t>(PK_PASS, B - o);
+  return for_each_pass(B, PK_PASS, [&](int64_t o, int64_t n) -> int {
     if (int rc = launch_unpack_rows(eng, N, ps, d_packed + o * ps.os * 4, n, d_e)) return rc;
-    if (int rc = ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_e, n, d_value + o * N, d_quot1 ? d_quot1 + o * N : nullptr,
-                                        d_rem1 ? d_rem1 + o * N : nullptr, d_quot2 ? d_quot2 + o * N : nullptr)) return rc;
-  }
-  return NTRU_OK;
+    return ntru_decrypt_batch_dev(eng, N, q, p, d_f, d_fp, d_e, n, d_value + o * N, rows_at(d_quot1, o * N), rows_at(d_rem1, o * N),
+                                  rows_at(d_quot2, o * N));
+  });
 }
 
 extern "C" int ntru_decrypt_packed_batch(ntru_engine_t *eng, int N, int q, int p, const int8_t *f, const uint8_t *fp, const uint64_t *packed,

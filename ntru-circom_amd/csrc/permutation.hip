@@ -159,22 +159,19 @@ __global__ void __launch_bounds__(PT_THREADS) k_perm_finish(const u32 *__restric
 
 namespace {
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 // Enqueues on eng->stream: the keys (d_keys, or drawn under ck / perm_id when d_keys is NULL), the sort, the finish.  The scratch
 // buffer is held until the last kernel is enqueued and released on return.
 int perm_flow(ntru_engine *eng, const uint64_t *d_keys, const ChaChaKey *ck, uint64_t perm_id, int64_t B, int64_t *d_src, int64_t *d_dst) {
   HIP_TRY(hipSetDevice(eng->device));
   const int tiles = (int)((B + PT_TILE - 1) / PT_TILE);
-  const size_t kbytes = ntru_up256((size_t)B * 8), ibytes = ntru_up256((size_t)B * 4), hbytes = ntru_up256((size_t)tiles * PT_DIGITS * 4);
-  ScratchHold hold(eng, 2 * kbytes + 2 * ibytes + hbytes + ntru_up256(PT_DIGITS * 4));
+  Carve c;
+  const size_t at_k0 = c.take((size_t)B * 8), at_k1 = c.take((size_t)B * 8), at_i0 = c.take((size_t)B * 4), at_i1 = c.take((size_t)B * 4),
+               at_hist = c.take((size_t)tiles * PT_DIGITS * 4), at_total = c.take(PT_DIGITS * 4);
+  ScratchHold hold(eng, c.total);
   if (hold.rc) return hold.rc;
-  u64 *kbuf[2] = {(u64 *)hold.p, (u64 *)(hold.p + kbytes)};
-  u32 *ibuf[2] = {(u32 *)(hold.p + 2 * kbytes), (u32 *)(hold.p + 2 * kbytes + ibytes)};
-  u32 *d_hist = (u32 *)(hold.p + 2 * kbytes + 2 * ibytes), *d_total = (u32 *)(hold.p + 2 * kbytes + 2 * ibytes + hbytes);
+  u64 *kbuf[2] = {(u64 *)(hold.p + at_k0), (u64 *)(hold.p + at_k1)};
+  u32 *ibuf[2] = {(u32 *)(hold.p + at_i0), (u32 *)(hold.p + at_i1)};
+  u32 *d_hist = (u32 *)(hold.p + at_hist), *d_total = (u32 *)(hold.p + at_total);
   const u64 *in_keys = (const u64 *)d_keys;
   if (!in_keys) {                                   // drawn into the pair that pass 0 does not write
     const long blocks = (B + 7) / 8;
@@ -197,7 +194,7 @@ int perm_flow(ntru_engine *eng, const uint64_t *d_keys, const ChaChaKey *ck, uin
   hipLaunchKernelGGL(k_perm_finish, dim3((unsigned)(fblocks < cap ? fblocks : cap)), dim3(PT_THREADS), 0, eng->stream, in_idx, (long)B,
                      (long long *)d_src, (long long *)d_dst);
   HIP_TRY(hipGetLastError());
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_perm_finish");
+  note_kernel(eng, "k_perm_finish");
   return NTRU_OK;
 }
 
@@ -207,7 +204,7 @@ int check_draw(const std::string &name, const uint32_t *key, int64_t B, const vo
   if (B > NTRU_PERM_MAX_B) return fail(NTRU_ERR_ARG, name + ": need B <= NTRU_PERM_MAX_B = " + std::to_string(NTRU_PERM_MAX_B) + ", got " + std::to_string(B));
   if (!key) return fail(NTRU_ERR_ARG, name + ": key is NULL");
   if (B > 0 && !src && !dst) return fail(NTRU_ERR_ARG, name + ": src and dst are both NULL");
-  if (overlap(src, (size_t)B * 8, dst, (size_t)B * 8)) return fail(NTRU_ERR_ARG, name + ": src and dst overlap");
+  if (ntru_ranges_overlap(src, (size_t)B * 8, dst, (size_t)B * 8)) return fail(NTRU_ERR_ARG, name + ": src and dst overlap");
   return NTRU_OK;
 }
 
@@ -222,12 +219,12 @@ int check_mix(ntru_engine *eng, const std::string &name, int N, int q, int p, co
   if (n1 + n2 > N) return fail(NTRU_ERR_ARG, name + ": The total of 1s and -1s cannot exceed the array length.");
   if (B > 0 && (!h || !e_in || !e_out || (need_outputs && (!r || !src)))) return fail(NTRU_ERR_ARG, name + ": NULL buffer");
   const size_t rows = (size_t)B * N * 2;
-  if (overlap(e_in, rows, e_out, rows)) return fail(NTRU_ERR_ARG, name + ": e_in and e_out overlap");
+  if (ntru_ranges_overlap(e_in, rows, e_out, rows)) return fail(NTRU_ERR_ARG, name + ": e_in and e_out overlap");
   const struct { const void *p; size_t n; const char *what; } outs[4] = {
       {e_out, rows, "e_out"}, {quotE, rows, "quotE"}, {r, (size_t)B * N, "r"}, {src, (size_t)B * 8, "src"}};
   for (int a = 0; a < 4; a++)
     for (int b = a + 1; b < 4; b++)
-      if (overlap(outs[a].p, outs[a].n, outs[b].p, outs[b].n))
+      if (ntru_ranges_overlap(outs[a].p, outs[a].n, outs[b].p, outs[b].n))
         return fail(NTRU_ERR_ARG, name + ": " + outs[a].what + " and " + outs[b].what + " overlap");
   if (int rc = ntru_sample_ternary_dev(eng, N, n1, n2, p - 1, key, first_item, 0, nullptr)) return rc;
   return ntru_reencrypt_batch_dev(eng, N, q, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr);
@@ -237,9 +234,12 @@ int check_mix(ntru_engine *eng, const std::string &name, int N, int q, int p, co
 int draw_to_host(ntru_engine *eng, const ChaChaKey &ck, uint64_t perm_id, int64_t B, int64_t *src, int64_t *dst) {
   HIP_TRY(hipSetDevice(eng->device));
   const size_t bytes = (size_t)B * 8;
-  if (int rc = ntru_grow_dev(&eng->shared_dev, 2 * ntru_up256(bytes))) return rc;
-  int64_t *d_src = src ? (int64_t *)eng->shared_dev.p : nullptr;
-  int64_t *d_dst = dst ? (int64_t *)((char *)eng->shared_dev.p + ntru_up256(bytes)) : nullptr;
+  Carve c;
+  const size_t at_src = c.take(bytes), at_dst = c.take(bytes);
+  ResidentHold hold(eng, "ntru_draw_permutation", c.total);
+  if (hold.rc) return hold.rc;
+  int64_t *d_src = src ? (int64_t *)(hold.p + at_src) : nullptr;
+  int64_t *d_dst = dst ? (int64_t *)(hold.p + at_dst) : nullptr;
   if (int rc = perm_flow(eng, nullptr, &ck, perm_id, B, d_src, d_dst)) return rc;
   HIP_TRY(hipStreamSynchronize(eng->stream));
   if (src) HIP_TRY(hipMemcpy(src, d_src, bytes, hipMemcpyDeviceToHost));
@@ -254,7 +254,7 @@ extern "C" int ntru_argsort_keys_dev(ntru_engine_t *eng, const uint64_t *d_keys,
   if (B < 0) return fail(NTRU_ERR_ARG, name + ": negative batch size");
   if (B > NTRU_PERM_MAX_B) return fail(NTRU_ERR_ARG, name + ": need B <= NTRU_PERM_MAX_B = " + std::to_string(NTRU_PERM_MAX_B) + ", got " + std::to_string(B));
   if (B > 0 && (!d_keys || !d_order)) return fail(NTRU_ERR_ARG, name + ": NULL buffer");
-  if (overlap(d_keys, (size_t)B * 8, d_order, (size_t)B * 8)) return fail(NTRU_ERR_ARG, name + ": keys and order overlap");
+  if (ntru_ranges_overlap(d_keys, (size_t)B * 8, d_order, (size_t)B * 8)) return fail(NTRU_ERR_ARG, name + ": keys and order overlap");
   if (!eng) return fail(NTRU_ERR_ARG, "engine is NULL");
   if (B == 0) return NTRU_OK;
   return perm_flow(eng, d_keys, nullptr, 0, B, d_order, nullptr);

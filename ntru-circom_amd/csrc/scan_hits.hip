@@ -166,17 +166,18 @@ int scan_flow(ntru_engine *eng, int N, int q, int p, int nbytes, int K, const in
   HIP_TRY(hipSetDevice(eng->device));
   const int64_t pass = std::min<int64_t>(B, SC_PASS);
   const int max_blocks = (int)((pass + SC_ROWS - 1) / SC_ROWS);
-  const size_t at_value = ntru_up256(os ? (size_t)pass * N * 2 : 0), at_bytes = at_value + ntru_up256((size_t)pass * N),
-               at_flags = at_bytes + ntru_up256((size_t)pass * nbytes), at_counts = at_flags + ntru_up256((size_t)pass),
-               at_offsets = at_counts + ntru_up256((size_t)max_blocks * 4), total = at_offsets + ntru_up256((size_t)max_blocks * 8);
-  ScratchHold hold(eng, total);
+  Carve c;
+  const size_t at_unpacked = c.take(os ? (size_t)pass * N * 2 : 0), at_value = c.take((size_t)pass * N),
+               at_bytes = c.take((size_t)pass * nbytes), at_flags = c.take((size_t)pass), at_counts = c.take((size_t)max_blocks * 4),
+               at_offsets = c.take((size_t)max_blocks * 8);
+  ScratchHold hold(eng, c.total);
   if (hold.rc) return hold.rc;
-  uint16_t *d_unpacked = (uint16_t *)hold.p;
+  uint16_t *d_unpacked = (uint16_t *)(hold.p + at_unpacked);
   uint8_t *d_value = (uint8_t *)hold.p + at_value, *d_bytes = (uint8_t *)hold.p + at_bytes, *d_flags = (uint8_t *)hold.p + at_flags;
   u32 *d_counts = (u32 *)(hold.p + at_counts);
   long long *d_offsets = (long long *)(hold.p + at_offsets);
-  for (int64_t o = 0; o < B; o += SC_PASS) {
-    const int n = (int)std::min<int64_t>(SC_PASS, B - o);
+  const int rc = for_each_pass(B, SC_PASS, [&](int64_t o, int64_t rows) -> int {
+    const int n = (int)rows;
     const dim3 grid((unsigned)((n + SC_ROWS - 1) / SC_ROWS));
     const uint16_t *d_e = (const uint16_t *)d_rows + o * N;
     if (os) {
@@ -197,8 +198,10 @@ int scan_flow(ntru_engine *eng, int N, int q, int p, int nbytes, int K, const in
                            (long long *)d_hit_row + (size_t)k * stride, d_hit_bytes + (size_t)k * stride * nbytes);
       HIP_TRY(hipGetLastError());
     }
-  }
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s", limit > 0 ? "k_scan_emit" : "k_scan_offsets");
+    return NTRU_OK;
+  });
+  if (rc) return rc;
+  note_kernel(eng, limit > 0 ? "k_scan_emit" : "k_scan_offsets");
   return NTRU_OK;
 }
 
@@ -230,11 +233,12 @@ int scan_host(ntru_engine *eng, const char *who, bool packed, int N, int q, int 
   if (!f || !fp || !rows) return fail(NTRU_ERR_ARG, std::string(who) + ": NULL buffer");
   HIP_TRY(hipSetDevice(eng->device));
   const int64_t cap = std::min<int64_t>(max_hits, B);
-  const size_t at_row = ntru_up256((size_t)K * 8), at_bytes = at_row + ntru_up256((size_t)K * cap * 8);
-  if (int rc = ntru_grow_dev(&eng->shared_dev, at_bytes + ntru_up256((size_t)K * cap * nbytes))) return rc;
-  char *dev = (char *)eng->shared_dev.p;
-  int64_t *d_count = (int64_t *)dev, *d_hit_row = (int64_t *)(dev + at_row);
-  uint8_t *d_hit_bytes = (uint8_t *)dev + at_bytes;
+  Carve c;
+  const size_t at_count = c.take((size_t)K * 8), at_row = c.take((size_t)K * cap * 8), at_bytes = c.take((size_t)K * cap * nbytes);
+  ResidentHold hold(eng, who, c.total);
+  if (hold.rc) return hold.rc;
+  int64_t *d_count = (int64_t *)(hold.p + at_count), *d_hit_row = (int64_t *)(hold.p + at_row);
+  uint8_t *d_hit_bytes = (uint8_t *)hold.p + at_bytes;
   HIP_TRY(hipMemset(d_count, 0, (size_t)K * 8));
   HIP_TRY(hipDeviceSynchronize());
   const ScanTag t = tag_of(tag_off, tag_len, tag);

@@ -1,6 +1,7 @@
 // sum_groups_common.h -- what the kernels that sum rows in groups share (ciphertext_sum.hip: dense rows; packed_ciphertexts.hip: rows of
 // packed field elements): the groups of one launch, their cut into row blocks, the layout of the partial rows that
-// k_sum_groups_finish completes, the launcher that sizes and carves the scratch for them, and the body of the tally calls.
+// k_sum_groups_finish completes, the launcher that sizes and carves the scratch for them, and the body of the tally calls; and, for
+// every kernel that reads dense u16 rows eight columns per lane (ciphertext_sum.hip, matrix_combine.hip), the row reads.
 //
 // A launch covers the rows [first offset, last offset), cut into Pb equal ROW BLOCKS.  A group that crosses a block boundary leaves one
 // partial row per block it meets in `part` (u32 [Pb][2][N]): slot 0 of a block for the group that entered through the block's start,
@@ -17,8 +18,37 @@
 
 typedef unsigned long long u64;
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 
 namespace {
+
+// Row blocks of one launch, at most: a finish kernel (k_sum_groups_finish, k_combine_finish) adds one partial per block, each reduced
+// below 65536 when the modulus is no power of two, in a u32.
+constexpr long SUM_MAX_ROW_BLOCKS = 32768;
+
+// ---- eight u16 coefficients at p (2-byte aligned) ------------------------------------------------------------------------------------
+// Rows have a pitch of 2 N bytes with N odd, so every other row starts on half a dword.  A 16-byte load from a 4-byte aligned address
+// runs at the full rate, so a lane reads the ALIGNED 16 bytes at or just below p plus the dword behind them (load8_raw) and shifts by 0
+// or 2 bytes (pairs8: v_alignbyte; the shift is the same for the whole wave).  The caller has checked that p + 10 elements lie inside
+// the array, so a batch of these loads has no branch between them.  Both take sh = half_dword(p) from the caller: worked out once per
+// read, k_combine_m compiles to the stream it had with the two steps in one function; worked out in each, it does not.
+__device__ __forceinline__ u32 half_dword(const u16 *p) { return (u32)((uintptr_t)p >> 1) & 1u; }      // 1: p is the upper half of a dword
+__device__ __forceinline__ void load8_raw(const u16 *p, u32 sh, u32 (&d)[5]) {
+  const u16 *ap = p - sh;                             // 4-byte aligned; at most 2 bytes below p, inside p's own dword
+  const u32x4 v = *(const u32x4_a4 *)ap;
+  d[4] = *(const u32 *)(ap + 8);
+  d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+}
+// the five dwords as four dwords of two coefficients, p[2 k] in the low half of x[k]
+__device__ __forceinline__ void pairs8(u32 sh, const u32 (&d)[5], u32 (&x)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) x[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], 2u * sh);
+}
+// The same pairs element by element, every one checked against `lim`, the end of the array: the last row or two only.
+__device__ __forceinline__ void pairs8_checked(const u16 *p, const u16 *lim, u32 (&x)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) x[k] = (p + 2 * k < lim ? (u32)p[2 * k] : 0u) | (p + 2 * k + 1 < lim ? (u32)p[2 * k + 1] << 16 : 0u);
+}
 
 // The groups of one launch.  off != NULL: group g is rows [off[g], off[g + 1]); else rows [(g0 + g) K, (g0 + g + 1) K).  Both
 // clamped to the window [wlo, whi) (the host form's chunk; everything for the _dev form); row r lies at rows + (r - wlo) N.
@@ -68,7 +98,7 @@ int launch_sum_rows(ntru_engine *eng, int N, int mod, const SumWindow &w, int ti
   HIP_TRY(hipSetDevice(eng->device));
   // row blocks: from the grid (waves_per_cu x CUs), and for uniform groups, whose row count the host knows, no more than there are rows
   long Pb = (long)eng->cus * waves_per_cu / tiles;
-  Pb = Pb < 1 ? 1 : (Pb > 32768 ? 32768 : Pb);
+  Pb = Pb < 1 ? 1 : (Pb > SUM_MAX_ROW_BLOCKS ? SUM_MAX_ROW_BLOCKS : Pb);
   if (!w.off) {
     long T = std::min<long>(w.whi, (w.g0 + w.G) * w.K) - std::max<long>(w.wlo, w.g0 * w.K);
     if (T < 1) T = 1;

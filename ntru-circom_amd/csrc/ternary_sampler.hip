@@ -105,7 +105,7 @@ static int launch_sampler(ntru_engine *eng, int N, int n1, int n2, int other, co
   if (lds > 160 * 1024) return fail(NTRU_ERR_UNSUPPORTED, "N too large for the sampler's LDS rows");
   ChaChaKey ck;
   memcpy(ck.k, key, 32);
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "k_sample_ternary");
+  note_kernel(eng, "k_sample_ternary");
   return launch_resident(eng, k_sample_ternary<BIGN, WAVES, DR, Items>, (B + WAVES * 64 - 1) / (WAVES * 64), WAVES * 64, lds, N, n1, n2,
                          (u32)other, ck, items, (long)B, d_out, (N + 15) / 16);
 }

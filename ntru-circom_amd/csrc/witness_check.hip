@@ -308,7 +308,7 @@ int launch_check(ntru_engine *eng, Kern kern, const char *name, const Geom &g, i
   HIP_TRY(hipSetDevice(eng->device));
   const size_t lds = (size_t)WC_WAVES * (2 * g.alen + 2 * g.vlen);
   if (int rc = launch_resident(eng, kern, (long)((B + WC_WAVES - 1) / WC_WAVES), WC_THREADS, lds, g, args...)) return rc;
-  snprintf(eng->last_kernel, sizeof eng->last_kernel, "%s", name);
+  note_kernel(eng, name);
   return NTRU_OK;
 }
 

@@ -2,9 +2,11 @@
 // device (fake_hip.cpp, fake_device.cpp), run under AddressSanitizer + UBSan and under ThreadSanitizer.  What is exercised: engine
 // life cycle, the three-stage chunk pipeline (pinned and pageable buffers, single chunk / many chunks / ragged last chunk / empty batch),
 // optional outputs, every regular host form, the shared scratch buffer across two user streams, ntru_multi_* (one host thread per
-// shard, unequal and empty shards), two engines driven from two threads, error paths.  Expected values come from the same formulas applied to the whole batch.
+// shard, unequal and empty shards), two engines driven from two threads, error paths, and the small host helpers of engine_internal.h
+// that the kernel files' host forms carve and hold buffers with.  Expected values come from the same formulas applied to the whole batch.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,7 +18,8 @@
 #include "engine_internal.h"
 
 static int g_fail = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { g_fail++; fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
+static std::atomic<int> g_checks{0};          // (CHECK runs on two threads at once in one case)
+#define CHECK(cond, ...) do { g_checks++; if (!(cond)) { g_fail++; fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } while (0)
 #define OK(call) do { int rc_ = (call); CHECK(rc_ == 0, "%s -> %d (%s)", #call, rc_, ntru_last_error()); } while (0)
 
 static thread_local uint32_t rng_state = 12345;
@@ -226,6 +229,55 @@ static void two_streams_share_the_scratch(ntru_engine_t *eng, int N, int q) {
   hipStreamDestroy(sa); hipStreamDestroy(sb);
 }
 
+// eng->shared_dev through ResidentHold: one holder at a time; a second hold fails without growing (growing frees what the first
+// holder still points at, which AddressSanitizer would see at the reads below).
+static void resident_hold(ntru_engine_t *eng) {
+  const size_t small = 1000, large = (size_t)3 << 20;
+  {
+    ResidentHold first(eng, "first_form", small);
+    CHECK(first.rc == NTRU_OK && first.p != nullptr && first.p == (char *)eng->shared_dev.p, "a hold hands out the engine's buffer");
+    if (first.rc != NTRU_OK) return;
+    memset(first.p, 0x5A, small);
+    const size_t cap = eng->shared_dev.cap;
+    {
+      ResidentHold second(eng, "second_form", large);
+      CHECK(second.rc == NTRU_ERR_ARG && second.p == nullptr, "a second hold while one is live must be refused");
+      CHECK(strstr(ntru_last_error(), "first_form") && strstr(ntru_last_error(), "second_form"), "the refusal names both holders: %s", ntru_last_error());
+    }
+    CHECK(eng->shared_dev.p == first.p && eng->shared_dev.cap == cap, "the refused hold did not grow the buffer");
+    CHECK(eng->shared_holder && !strcmp(eng->shared_holder, "first_form"), "the refused hold left the first holder's mark");
+    bool intact = true;
+    for (size_t i = 0; i < small && intact; i++) intact = first.p[i] == 0x5A;
+    CHECK(intact, "the first holder's bytes after the refused hold");
+  }
+  CHECK(eng->shared_holder == nullptr, "leaving scope releases the hold");
+  ResidentHold third(eng, "third_form", large);
+  CHECK(third.rc == NTRU_OK && third.p != nullptr && eng->shared_dev.cap >= large, "a larger hold after the first has left scope");
+  if (third.rc == NTRU_OK) memset(third.p, 0, large);
+}
+
+// Carve against the offset chain scan_flow wrote by hand (one pass of 1000 packed rows, N = 61, 7 message bytes, 4 blocks), and
+// ntru_ranges_overlap.
+static void carve_and_overlap() {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t pass = 1000, N = 61, nbytes = 7, max_blocks = 4;
+  const size_t at_value = up(pass * N * 2), at_bytes = at_value + up(pass * N), at_flags = at_bytes + up(pass * nbytes), at_counts = at_flags + up(pass),
+               at_offsets = at_counts + up(max_blocks * 4), total = at_offsets + up(max_blocks * 8);
+  Carve c;
+  const size_t got[6] = {c.take(pass * N * 2), c.take(pass * N), c.take(pass * nbytes), c.take(pass), c.take(max_blocks * 4), c.take(max_blocks * 8)};
+  const size_t want[6] = {0, at_value, at_bytes, at_flags, at_counts, at_offsets};
+  for (int i = 0; i < 6; i++) CHECK(got[i] == want[i] && got[i] % 256 == 0, "Carve offset %d: %zu, by hand %zu", i, got[i], want[i]);
+  CHECK(c.total == total && total % 256 == 0, "Carve total %zu, by hand %zu", c.total, total);
+  Carve e;
+  CHECK(e.take(0) == 0 && e.take(1) == 0 && e.take(256) == 256 && e.take(257) == 512 && e.total == 1024, "empty arrays take no room, every other one whole granules");
+  char buf[64];
+  CHECK(!ntru_ranges_overlap(buf, 16, buf + 16, 16) && !ntru_ranges_overlap(buf + 16, 16, buf, 16), "touching ranges do not overlap");
+  CHECK(ntru_ranges_overlap(buf, 17, buf + 16, 16) && ntru_ranges_overlap(buf + 16, 16, buf, 17), "one shared byte overlaps");
+  CHECK(ntru_ranges_overlap(buf, 64, buf + 8, 4) && ntru_ranges_overlap(buf + 8, 4, buf, 64) && ntru_ranges_overlap(buf, 8, buf, 8), "a range inside another, and a range and itself");
+  CHECK(!ntru_ranges_overlap(buf + 8, 0, buf, 64) && !ntru_ranges_overlap(buf, 64, buf + 8, 0) && !ntru_ranges_overlap(buf, 0, buf, 0), "an empty range overlaps nothing");
+  CHECK(!ntru_ranges_overlap(nullptr, 64, buf, 64) && !ntru_ranges_overlap(buf, 64, nullptr, 64) && !ntru_ranges_overlap(nullptr, 8, nullptr, 8), "NULL overlaps nothing");
+}
+
 static void multi(int N, int q) {
   const int ids[3] = {0, 1, 2};
   ntru_multi_t *mu = nullptr;
@@ -330,6 +382,8 @@ int main() {
     OK(ntru_dev_free(eng, d));
   }
   two_streams_share_the_scratch(eng, N, q);
+  resident_hold(eng);
+  carve_and_overlap();
   {   // two engines from two host threads at once (thread-local error strings, nothing shared between engines)
     std::thread t1([&] { round_trip(eng, N, q, (1 << 15) + 11, false, true); });
     std::thread t2([&] { round_trip(e2, N, q, (1 << 15) + 13, true, true); });
@@ -340,6 +394,6 @@ int main() {
   ntru_engine_destroy(e2);
   ntru_engine_destroy(eng);
   if (g_fail) { fprintf(stderr, "hostcheck: %d failure(s)\n", g_fail); return 1; }
-  printf("hostcheck ok\n");
+  printf("hostcheck ok (%d checks)\n", g_checks.load());
   return 0;
 }

@@ -3,7 +3,10 @@
 Error parity: the return code and the ntru_last_error() text of every bad-argument case equal tests/golden/host_form_errors.json,
 recorded by tests/golden/record_host_form_errors.py from the commit before the forms were derived from one description each.
 Data parity: a host form's outputs equal, byte for byte, what its own _dev form writes for the same inputs held in device buffers:
-B = 1 and B = 8197 (four chunks of 2050, the last one ragged), pageable and pinned arrays, optional outputs asked for and not."""
+B = 1 and B = 8197 (four chunks of 2050, the last one ragged), pageable and pinned arrays, optional outputs asked for and not.
+
+The host forms that keep results on the device for a whole call (sum_groups, combine_batch, draw_permutation: the engine's resident
+buffer, one holder at a time) one after the other on one engine, each against numpy."""
 import ctypes as C
 
 import numpy as np
@@ -156,3 +159,37 @@ def test_multi_form_equals_host_form(eng, multi, f):
             got = run_host(multi._lib, f.name, multi._h, f, inputs, count, wanted, False)
             diff = [k for k in want if got[k] != want[k]]
             assert not diff, (f.name, count, wanted, diff)
+
+
+def test_resident_buffer_passes_from_one_host_form_to_the_next():
+    """sum_groups (offsets with an empty group), combine_batch, draw_permutation, then sums of four times the groups and the
+    combination again, on ONE engine: every holder of the resident buffer takes it after every other kind and computes what numpy
+    does.  The buffer grows in steps of 1 MiB, which none of these sizes crosses, so a draw of 200000 items (3.2 MB) follows and the sums
+    and the combination run once more behind that regrow."""
+    N, mod, rows_n = 17, 4096, 40
+    rng = np.random.default_rng(20)
+    rows = rng.integers(0, mod, (rows_n, N), dtype=np.uint16)
+    w = rng.integers(0, mod, (rows_n, 3), dtype=np.uint16)
+    key = np.arange(1, 9, dtype=np.uint32)
+    wide = rows.astype(np.int64)
+    want_combo = ((w.T.astype(np.int64) @ wide) % mod).astype(np.uint16)
+
+    def sums(offsets):
+        return np.stack([wide[a:b].sum(axis=0) % mod for a, b in zip(offsets[:-1], offsets[1:])]).astype(np.uint16)
+
+    def check_draw(B):
+        src = pkg.draw_permutation(eng, key, 7, B)
+        assert np.array_equal(np.sort(src), np.arange(B)), "not a permutation of range(B)"
+        assert np.array_equal(pkg.draw_permutation(eng, key, 7, B), src), "a second draw under the same key and id differs"
+
+    few = np.array([0, 7, 7, 19, 40], np.int64)                                  # group 1 is empty
+    many = np.array([0, 2, 5, 5, 7, 10, 12, 15, 19, 20, 24, 27, 30, 33, 36, 38, 40], np.int64)   # 16 groups, group 2 is empty
+    eng = pkg.Engine(0)
+    assert np.array_equal(eng.sum_groups(N, mod, rows, offsets=few), sums(few))
+    assert np.array_equal(pkg.combine_batch(eng, N, mod, rows, w), want_combo)
+    check_draw(1000)
+    assert np.array_equal(eng.sum_groups(N, mod, rows, offsets=many), sums(many))
+    assert np.array_equal(pkg.combine_batch(eng, N, mod, rows, w), want_combo)
+    check_draw(200000)
+    assert np.array_equal(eng.sum_groups(N, mod, rows, offsets=few), sums(few))
+    assert np.array_equal(pkg.combine_batch(eng, N, mod, rows, w), want_combo)
