@@ -131,6 +131,28 @@ int ntru_polymul_split(ntru_engine_t *eng, int N, int mod, const uint16_t *a, co
 int ntru_polymul_split_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_a, const uint16_t *d_b,
                            int64_t B, uint16_t *d_quot, uint16_t *d_rem);
 
+/* ---- product of a batch with ONE shared polynomial + split: multiplyPolynomials(row, s, mod) followed by dividePolynomials(., I, mod)
+ *      (index.js:319-355, 358-401) with s fixed over the batch -- e * c mod (x^N - 1) for a public polynomial c (the homomorphic
+ *      plaintext-polynomial product; c = x^k rotates), or s * e for a key that is not ternary.  s: [N]; rows: [B][N] dense; quot, rem:
+ *      [B][N]; quot may be NULL, like quotE.  Row b of quot / rem is byte for byte what ntru_polymul_split(a = rows, b = s repeated B
+ *      times) returns: quot[b][k] = (mod - c[N+k]) % mod, rem[b][k] = (c[k] + c[N+k]) % mod, c = the linear product rows[b] * s.
+ *      Domain: that of ntru_polymul_split, ntru_engine_supports(N, mod); operands are any uint16, reduced or not, when mod is a power of
+ *      two, and below mod otherwise; pointers of any 2-byte alignment; B == 0 launches nothing.  Refused, each with a message of its
+ *      own, before the engine is looked at and before anything is launched: B < 0; an unsupported (N, mod) (NTRU_ERR_UNSUPPORTED); a
+ *      NULL s, rows or rem with B > 0; an output range that overlaps an input range or the other output; a NULL engine with valid
+ *      arguments is then the usual "engine is NULL".
+ *      A power-of-two mod <= 8192 with N <= 1024 on kernel paths 0 (N >= 64), 4 and 5 runs as batch x Toeplitz matrix of s on the int8
+ *      matrix cores (k_mul_shared_m: rows and s both split at 128, three plane products per contraction step, exact).  Everything else
+ *      -- mod > 8192, a modulus that is no power of two, N > 1024, kernel paths 1-3 -- replicates s into the engine-owned scratch and
+ *      runs the per-item kernels of ntru_polymul_split_dev, in passes of at most 65536 rows: correct, not fast.
+ *   _dev: enqueues on the engine's stream, does not synchronise, allocates nothing per call.
+ *   host form: the rows run through the chunked pipeline; s goes up with every chunk, as h does for ntru_encrypt_batch.
+ *   On ciphertexts the product multiplies the noise by the 1-norm of c ("Multiplying by a shared polynomial"). */
+int ntru_mul_shared_batch(ntru_engine_t *eng, int N, int mod, const uint16_t *s, const uint16_t *rows, int64_t B, uint16_t *quot,
+                          uint16_t *rem);
+int ntru_mul_shared_batch_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_s, const uint16_t *d_rows, int64_t B,
+                              uint16_t *d_quot, uint16_t *d_rem);
+
 /* ---- stand-alone split: dividePolynomials(a, I, mod) (index.js:358-401 with b = I = 1 - x^N) for dividends that
  *      are already reduced into [0,mod).  a: [B][2N] (row b = the dividend's coefficients 0..2N-1, zero padded).
  *      quot[b][k] = (mod - a[N+k]) % mod, rem[b][k] = (a[k] + a[N+k]) % mod   (SURVEY.md 0.3). */

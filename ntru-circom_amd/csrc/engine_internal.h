@@ -31,6 +31,9 @@
 //   matrix_combine.hip       G linear combinations of the same rows by a weight matrix, out = W^T rows: the contraction over the batch axis on
 //                            the int8 matrix cores (k_combine_m), the vector-ALU twin (k_combine_v), the finish over row blocks (kernels, *_dev
 //                            and host-pointer entry points)
+//   matrix_mulshared.hip     a batch of full-range rows times ONE full-range polynomial, with the split: batch x Toeplitz matrix on the int8
+//                            matrix cores with both operands in two digit planes (k_mul_shared_m), the replicated per-item route for
+//                            everything outside its range (kernel, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

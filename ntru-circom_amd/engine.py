@@ -91,6 +91,8 @@ _SIGS = {
     **_both("ntru_tally_decrypt_batch", "p iii ppppp ll ppppp"),
     # combining ciphertexts by a weight matrix: the functions are in combine.py
     **_both("ntru_combine_batch", "p ii pp l i p"),
+    # a batch times one shared polynomial, with the split: the functions are in shared_product.py
+    **_both("ntru_mul_shared_batch", "p ii pp l pp"),
     # ciphertexts as packOutput(q - 1, N, e) rows: the methods are in packed.py
     **_both("ntru_sum_groups_packed", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_packed_batch", "p iii ppppp ll ppppp"),

@@ -304,6 +304,23 @@ export function combineCiphertexts(rows, q, weights, G = null) {
   return Array.from({ length: m.G }, (_, g) => trimPolynomial(Array.from(out.subarray(g * N, (g + 1) * N))));
 }
 
+// B rows, rows: Uint16Array[B * N], times the ONE polynomial poly (numbers of any sign, at most N of them) modulo (x^N - 1, q): row b is
+// dividePolynomials(multiplyPolynomials(row b, poly, q), I, q).  -> the remainders Uint16Array[B * N], or { quotient, remainder } with
+// wantQuot.  Composed from polymulSplit with poly repeated per row: the same bytes as the engine's ntru_mul_shared_batch, which keeps poly
+// as one Toeplitz matrix on the matrix cores, but not that call (INTEGRATION.md, "Multiplying by a shared polynomial"): from Node this is
+// correct, not fast.  On ciphertexts the product multiplies the noise by the 1-norm of poly.
+export function multiplyByPolynomialBatch(rows, N, q, B, poly, wantQuot = false) {
+  if (poly.length > N) throw new RangeError('Invalid array length');
+  if (!(rows instanceof Uint16Array) || rows.length !== B * N) throw new TypeError(`multiplyByPolynomialBatch: rows must be a Uint16Array of B * N = ${B * N} values`);
+  const s = new Uint16Array(B * N), quot = new Uint16Array(B * N), rem = new Uint16Array(B * N);
+  if (B > 0) {
+    for (let i = 0; i < poly.length; i++) s[i] = mod(poly[i], q);
+    for (let b = 1; b < B; b++) s.copyWithin(b * N, 0, N);
+    engine().polymulSplit(N, q, rows, s, B, quot, rem);
+  }
+  return wantQuot ? { quotient: quot, remainder: rem } : rem;
+}
+
 // Rows of packOutput(q - 1, N, e) field elements, BigUint64Array[B * outputSize * 4] -> the dense rows Uint16Array[B * N]: unpackInput of
 // every row with the pad dropped, whatever the pad and the bits above an element's fields hold.
 function unpackRows(N, q, packed, B) {
@@ -647,6 +664,9 @@ export default class NTRU {
     const sum = combineRows(this.N, this.q, rows, B, m.w, m.G);
     return { sum, ...this.decryptBatch(sum, m.G, wantWitness) };
   }
+
+  // rows: Uint16Array[B*N] times the one polynomial poly modulo (x^N - 1, q) (multiplyByPolynomialBatch above).
+  multiplyByPolynomialBatch(rows, B, poly, wantQuot = false) { return multiplyByPolynomialBatch(rows, this.N, this.q, B, poly, wantQuot); }
 
   // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed
   // from unpackBatch and tallyDecryptBatch (same results as ntru_tally_decrypt_packed_batch, not that call).

@@ -23,6 +23,7 @@ from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
 from . import scan as scan_calls
+from . import shared_product as shared_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
 
@@ -498,6 +499,15 @@ class NTRU:
             value, q1, r1, q2 = self.engine.decrypt_batch(N, q, p, expandArray(self.f, N), expandArray(self.fp, N), total,
                                                           want_witness=want_witness)
         return {"sum": total, "value": value, "quotient1": q1, "remainder1": r1, "quotient2": q2}
+
+    def multiplyByPolynomialBatch(self, rows, poly, want_quot=False):
+        """rows [B][N] (ciphertexts, or any rows modulo q) times the one polynomial `poly` (coefficients of any sign, at most N of them)
+        modulo (x^N - 1, q): row b is dividePolynomials(multiplyPolynomials(rows[b], poly, q), I, q).  Returns the remainders [B][N],
+        or (quotients, remainders) with want_quot.  A ciphertext's noise grows by the 1-norm of poly."""
+        N, q = self.N, self.q
+        s = np.asarray(expandArray(list(poly), N), dtype=np.int64) % q
+        quot, rem = shared_calls.mul_shared_batch(self.engine, N, q, s, np.asarray(rows).reshape(-1, N), want_quot=want_quot)
+        return (quot, rem) if want_quot else rem
 
     # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
     def tallyPacked(self, packed, offsets=None, weights=None, wantWitness=True):

@@ -157,6 +157,30 @@ def decrypt_model(N, q, p, f, fp, e):
     return value, quot1, rem1, quot2
 
 
+def mul_shared_planes(s, q):
+    """k_mul_shared_m's digits of the shared operand: s mod q = s0 + 128 s1 with s0 in [-64, 63]; s1 is kept modulo 64 and doubled."""
+    s = np.asarray(s, np.int64) & (q - 1)
+    s0 = ((s + 64) & 127) - 64
+    s1x2 = 2 * (((s - s0) >> 7) & 0x3F)
+    assert s0.min() >= -64 and s0.max() <= 63 and s1x2.max() <= 126 and np.all((s0 + 64 * s1x2 - s) % q == 0)
+    return s0, s1x2
+
+
+def mul_shared_model(N, q, s, rows):
+    """k_mul_shared_m (csrc/matrix_mulshared.hip): rows = e_lo + 128 e_hi against s = s0 + 128 s1 as three plane products.  Pass B,
+    e_lo (2 s1) + (2 e_hi) s0, counts 64-fold: its int32 sums are shifted left by 6 (wrapping) and pass A, e_lo s0, adds on top."""
+    e = np.asarray(rows, np.int64) & (q - 1)
+    E_lo, E_hi2 = stage(e & 127, N), stage((e >> 6) & 0xFE, N)
+    s0, s1x2 = mul_shared_planes(s, q)
+    T0, T1 = rev_array(s0, N), rev_array(s1x2, N)
+    lowB, highB = toeplitz_product([E_lo, E_hi2], [T1, T0], N)
+    lowA, highA = toeplitz_product([E_lo], [T0], N)
+    wrap = lambda x: ((x + 2 ** 31) % 2 ** 32) - 2 ** 31                     # an int32 accumulator
+    assert max(np.abs(x).max() for x in (lowA, highA, lowB, highB)) < 2 ** 31
+    low, high = wrap(wrap(lowB << 6) + lowA), wrap(wrap(highB << 6) + highA)
+    return (low[:, :N] + high[:, :N]) % q, (-high[:, :N]) % q               # rem, quot
+
+
 def direct_split(X, s, N, mod):
     lin = np.zeros((X.shape[0], 2 * N), np.int64)
     for i in range(N):
@@ -182,6 +206,12 @@ def main():
         assert np.array_equal(rem1, r1) and np.array_equal(quot1, q1), (N, q, "decrypt product 1")
         v2, q2 = direct_split(lift(r1, q, p), fp, N, p)
         assert np.array_equal(value, v2) and np.array_equal(quot2, q2), (N, q, "decrypt product 2")
+        s = rng.integers(0, q, N)
+        s[:8] = np.array([0, 63, 64, 65, 127, 128, q - 64, q - 1]) % q      # every edge of both digits
+        e[0], e[1] = q - 1, 127
+        rem, quot = mul_shared_model(N, q, s, e)
+        rs, qs = direct_split(e, s, N, q)
+        assert np.array_equal(rem, rs) and np.array_equal(quot, qs), (N, q, "shared full-range product")
         print("N=%d q=%d: tiles %d, strips %s  OK" % (N, q, tiles(N)[0], strips(tiles(N)[0])))
 
 
