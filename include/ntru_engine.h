@@ -265,6 +265,41 @@ int ntru_decrypt_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, const
                                   const uint64_t *d_packed, int64_t B, uint8_t *d_value, uint16_t *d_quot1, uint16_t *d_rem1,
                                   uint8_t *d_quot2);
 
+/* ---- measuring noise: how much room a ciphertext row has left under a private key.  For a row e ([N], reduced modulo q, q a power of
+ *      two) and a key f ([N], symbols in {-1, 0, 1}: the precondition of ntru_decrypt_batch),
+ *        a_k      = (f * e mod x^N - 1)_k mod q       byte for byte the rem1 that ntru_decrypt_batch returns for that row and key
+ *        c_k      = a_k > q/2 ? a_k - q : a_k         the threshold of both lift modes; it is strict: a_k = q/2 stays +q/2
+ *        peak     = max_k |c_k|                       in [0, q/2]: a uint16_t (32768 at most, at q = 65536)
+ *        energy   = sum_k c_k^2                       a uint64_t (below 2^41 for every N and q of the domain)
+ *      Neither depends on p, on fp or on the lift mode (ntru_engine_set_lift changes nothing here).
+ *      What the numbers mean: with A = p r*g + f*m taken over the integers, decryption under the centred lift is right exactly when
+ *      every A_k lies in (-q/2, q/2].  Then c = A, peak is the true infinity norm of A and q/2 - peak is the room left.  Once some A_k
+ *      has left that interval a has wrapped and peak is only the norm of the wrapped value: a wrapped row cannot be told from a merely
+ *      noisy one with certainty, which is why callers keep a guard band.  Growth: sums add A (ntru_sum_groups, the tallies), weights
+ *      and a polynomial c scale it (ntru_combine_batch: by the weight; ntru_mul_shared_batch: by at most the 1-norm of c), and every
+ *      mix round adds a fresh p r*g (ntru_reencrypt_batch, ntru_mix_batch).  INTEGRATION.md, "Measuring noise".
+ *      f: [N]; e: [B][N] dense; packed: [B][output_size][4] in the wire format of "packed ciphertexts" above (ignored fields and bits
+ *      as there); peak: [B]; energy: [B].  Either output may be NULL, but not both.  energy needs 8-byte alignment; e and peak take any
+ *      2-byte alignment, packed any 8-byte alignment.  Domain: 2 <= N <= NTRU_MAX_N, q a power of two with 2 <= q <= 65536, B >= 0;
+ *      B == 0 launches nothing.  Refused, each with a message of its own, before the engine is looked at and before anything is
+ *      launched (NTRU_ERR_UNSUPPORTED for the domain, NTRU_ERR_ARG otherwise): B < 0; (N, q) outside the domain; a NULL f or NULL rows
+ *      with B > 0; both outputs NULL; a misaligned energy; an output range that overlaps an input range or the other output.  A NULL
+ *      engine with valid arguments is then the usual "engine is NULL".
+ *      Wherever the shared-key decrypt runs on the matrix cores (q <= 8192, N <= 1024, kernel paths 0 with N >= 64, 4 and 5) one
+ *      kernel, k_noise_m, runs decrypt's first product and reduces it in its epilogue: one of decrypt's two products, 10 bytes stored
+ *      per row.  Everything else runs the vector-ALU decrypt for its rem1 into the engine-owned scratch, in passes of at most 65536
+ *      rows, and reduces the pass (k_noise_rows); ntru_engine_last_kernel then reports noise_rows(<the product's kernel>).  The packed
+ *      forms unpack a pass into scratch first.  Scratch is bounded in B.
+ *   _dev: enqueues on the engine's stream, does not synchronise, allocates nothing per call.
+ *   host forms: the rows run through the chunked pipeline, f goes up with every chunk; 2 and 8 bytes per row come down. */
+int ntru_noise_batch(ntru_engine_t *eng, int N, int q, const int8_t *f, const uint16_t *e, int64_t B, uint16_t *peak, uint64_t *energy);
+int ntru_noise_batch_dev(ntru_engine_t *eng, int N, int q, const int8_t *d_f, const uint16_t *d_e, int64_t B, uint16_t *d_peak,
+                         uint64_t *d_energy);
+int ntru_noise_packed_batch(ntru_engine_t *eng, int N, int q, const int8_t *f, const uint64_t *packed, int64_t B, uint16_t *peak,
+                            uint64_t *energy);
+int ntru_noise_packed_batch_dev(ntru_engine_t *eng, int N, int q, const int8_t *d_f, const uint64_t *d_packed, int64_t B,
+                                uint16_t *d_peak, uint64_t *d_energy);
+
 /* ---- on-device ternary sampler: generateCustomArray(N, n1, n2) (index.js:461-488) for B items, so that encryptBits'
  *      randomness r never crosses PCIe.  Row b (item index first_item + b) gets n1 ones, n2 entries equal to `other`
  *      (2 = p-1 for r after the index.js:89 map) and zeros, shuffled exactly like the reference: for i = N-1 .. 1:

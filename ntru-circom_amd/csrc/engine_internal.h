@@ -34,6 +34,10 @@
 //   matrix_mulshared.hip     a batch of full-range rows times ONE full-range polynomial, with the split: batch x Toeplitz matrix on the int8
 //                            matrix cores with both operands in two digit planes (k_mul_shared_m), the replicated per-item route for
 //                            everything outside its range (kernel, *_dev and host-pointer entry points)
+//   matrix_noise.hip         the decryption noise of rows under one key: decrypt's first product on the int8 matrix cores reduced to
+//                            peak and energy in the epilogue (k_noise_m), the vector-ALU decrypt's rem1 reduced pass by pass for
+//                            everything outside its range (k_noise_rows), dense and packed rows (kernels, *_dev and host-pointer entry
+//                            points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

@@ -93,6 +93,9 @@ _SIGS = {
     **_both("ntru_combine_batch", "p ii pp l i p"),
     # a batch times one shared polynomial, with the split: the functions are in shared_product.py
     **_both("ntru_mul_shared_batch", "p ii pp l pp"),
+    # the decryption noise of rows under a key, dense and packed: the functions are in noise.py
+    **_both("ntru_noise_batch", "p ii pp l pp"),
+    **_both("ntru_noise_packed_batch", "p ii pp l pp"),
     # ciphertexts as packOutput(q - 1, N, e) rows: the methods are in packed.py
     **_both("ntru_sum_groups_packed", "p ii ppp ll p"),
     **_both("ntru_tally_decrypt_packed_batch", "p iii ppppp ll ppppp"),

@@ -668,6 +668,28 @@ export default class NTRU {
   // rows: Uint16Array[B*N] times the one polynomial poly modulo (x^N - 1, q) (multiplyByPolynomialBatch above).
   multiplyByPolynomialBatch(rows, B, poly, wantQuot = false) { return multiplyByPolynomialBatch(rows, this.N, this.q, B, poly, wantQuot); }
 
+  // The decryption noise of the ciphertexts e: Uint16Array[B*N] under this key -> { peak: Uint16Array[B], energy: Array of B Numbers
+  // (exact: below 2^53), margin: Int32Array[B] }.  With a = remainder1 of decryptBits(row) and c_k = a_k > q/2 ? a_k - q : a_k:
+  // peak = max |c_k|, energy = sum c_k^2, margin = q/2 - peak.  Composed from decryptBatch with its witnesses and a reduction of
+  // remainder1 in JavaScript: the same numbers as the engine's ntru_noise_batch, which runs one product and stores 10 bytes per row, but
+  // not that call (INTEGRATION.md, "Measuring noise").  A row whose noise has wrapped past q/2 shows the norm of the wrapped value only.
+  noiseBatch(e, B) {
+    const { N, q } = this;
+    if (!(e instanceof Uint16Array) || e.length !== B * N) throw new TypeError(`noiseBatch: e must be a Uint16Array of B * N = ${B * N} values`);
+    const r1 = B > 0 ? this.decryptBatch(e, B, true).remainder1 : new Uint16Array(0);      // remainder1 does not depend on the lift
+    const peak = new Uint16Array(B), energy = new Array(B).fill(0), margin = new Int32Array(B);
+    for (let b = 0; b < B; b++) {
+      let m = 0, s = 0;
+      for (let k = 0; k < N; k++) {
+        const a = r1[b * N + k], c = a > q / 2 ? q - a : a;
+        if (c > m) m = c;
+        s += c * c;
+      }
+      peak[b] = m; energy[b] = s; margin[b] = q / 2 - m;
+    }
+    return { peak, energy, margin };
+  }
+
   // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed
   // from unpackBatch and tallyDecryptBatch (same results as ntru_tally_decrypt_packed_batch, not that call).
   tallyPackedBatch(packed, B, offsets = null, weights = null, wantWitness = true) {

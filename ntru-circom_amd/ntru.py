@@ -23,6 +23,7 @@ from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
 from . import scan as scan_calls
+from . import noise as noise_calls
 from . import shared_product as shared_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
                      GENERIC_ERRORS, Engine, EngineError)
@@ -508,6 +509,21 @@ class NTRU:
         s = np.asarray(expandArray(list(poly), N), dtype=np.int64) % q
         quot, rem = shared_calls.mul_shared_batch(self.engine, N, q, s, np.asarray(rows).reshape(-1, N), want_quot=want_quot)
         return (quot, rem) if want_quot else rem
+
+    def noiseBatch(self, rows, packed=False):
+        """The decryption noise of the ciphertexts `rows` ([B][N], or packed rows [B][outputSize][4] with packed=True) under this key:
+        {"peak", "energy", "margin"} as [B] arrays, peak = max |a centred at q/2| and energy = the sum of its squares for
+        a = remainder1 of decryptBits(row), margin = q // 2 - peak.  A row whose noise has wrapped past q/2 shows the norm of the
+        wrapped value only: keep a guard band."""
+        N, q = self.N, self.q
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")
+        f = expandArray(self.f, N)
+        if packed:
+            peak, energy = noise_calls.noise_packed_batch(self.engine, N, q, f, rows)
+        else:
+            peak, energy = noise_calls.noise_batch(self.engine, N, q, f, np.asarray(rows).reshape(-1, N))
+        return {"peak": peak, "energy": energy, "margin": (q // 2 - peak.astype(np.int64))}
 
     # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
     def tallyPacked(self, packed, offsets=None, weights=None, wantWitness=True):

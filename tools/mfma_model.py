@@ -181,6 +181,68 @@ def mul_shared_model(N, q, s, rows):
     return (low[:, :N] + high[:, :N]) % q, (-high[:, :N]) % q               # rem, quot
 
 
+def noise_strip_slots(NT, waves=4):
+    """k_noise_m's slots: strip j = 4 rho + w of for_each_strip's cut owns slot j; (kb0, nt) per slot, in slot order, for the strips that
+    exist (a wave without a strip, NT < 4, has no slot below the count the fold runs to)."""
+    per_wave = strips(NT, waves)
+    rounds = max(len(w) for w in per_wave)
+    slots = [per_wave[w][rho] for rho in range(rounds) for w in range(waves) if rho < len(per_wave[w])]
+    assert len(slots) == min(NT, rounds * waves) <= 8 and [kb0 for kb0, _ in slots] == sorted(kb0 for kb0, _ in slots)
+    return slots
+
+
+def noise_lane_fold(mx, sq):
+    """The halving exchange over the 32 lanes of each half-wave: mx, sq [64 lanes][16 registers] -> per lane the (max, sum) of register
+    (lane & 31) >> 1 over its half-wave.  In step H the lanes l and l ^ 2H split the 2H live registers between them."""
+    mx, sq = mx.copy(), sq.copy()
+    lane = np.arange(64)
+    for H in (8, 4, 2, 1):
+        up, partner = (lane & (2 * H)) != 0, lane ^ (2 * H)
+        for k in range(H):
+            keep_m, give_m = np.where(up, mx[:, k + H], mx[:, k]), np.where(up, mx[:, k], mx[:, k + H])
+            keep_s, give_s = np.where(up, sq[:, k + H], sq[:, k]), np.where(up, sq[:, k], sq[:, k + H])
+            mx[:, k], sq[:, k] = np.maximum(keep_m, give_m[partner]), keep_s + give_s[partner]
+    m, s = np.maximum(mx[:, 0], mx[lane ^ 1, 0]), sq[:, 0] + sq[lane ^ 1, 0]
+    assert s.max() < 2 ** 32                                  # a u32 in the kernel
+    return m, s
+
+
+def noise_epilogue(N, q, low, high):
+    """k_noise_m's epilogue on one row block: low, high [32][32 NT] accumulators (columns >= N hold junk).  Register i of lane (r, h)
+    and tile t is row (i & 3) + 8 (i >> 2) + 4 h, column 32 (kb0 + t) + r.  Per register x = (low + high) & (q - 1), 0 for a column
+    >= N, c = min(x, q - x); max c and the 32-bit sum of c^2 over the strip's tiles, the lane fold, one (max, sum) per row and slot,
+    then the fold over the slots: (peak [32], energy [32])."""
+    NT, NP = tiles(N)
+    lane = np.arange(64)
+    r, h = lane & 31, lane >> 5
+    reg = np.arange(16)
+    row = (reg[None, :] & 3) + 8 * (reg[None, :] >> 2) + 4 * h[:, None]          # [lane][register]
+    slots = noise_strip_slots(NT)
+    smax, ssum = np.zeros((8, 32), np.int64), np.zeros((8, 32), np.int64)
+    for j, (kb0, nt) in enumerate(slots):
+        mx, sq = np.zeros((64, 16), np.int64), np.zeros((64, 16), np.int64)
+        for t in range(nt):
+            col = 32 * (kb0 + t) + r
+            x = (low[row, col[:, None]] + high[row, col[:, None]]) & np.where(col < N, q - 1, 0)[:, None]
+            c = np.minimum(x, q - x)
+            mx, sq = np.maximum(mx, c), sq + c * c
+        assert sq.max() <= 4 * (q // 2) ** 2
+        m, s = noise_lane_fold(mx, sq)
+        i = (lane & 31) >> 1
+        even = (lane & 1) == 0
+        at = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)
+        smax[j, at[even]], ssum[j, at[even]] = m[even], s[even]
+    return smax[:len(slots)].max(axis=0), ssum[:len(slots)].sum(axis=0)
+
+
+def noise_model(N, q, f, e):
+    """k_noise_m on one row block: decrypt's product 1 followed by noise_epilogue."""
+    e = np.asarray(e, np.int64) & (q - 1)
+    fs = np.asarray(f, np.int64)
+    low, high = toeplitz_product([stage(e & 127, N), stage((e >> 6) & 0xFE, N)], [rev_array(fs, N), rev_array(64 * fs, N)], N)
+    return noise_epilogue(N, q, low, high)
+
+
 def direct_split(X, s, N, mod):
     lin = np.zeros((X.shape[0], 2 * N), np.int64)
     for i in range(N):
@@ -212,6 +274,10 @@ def main():
         rem, quot = mul_shared_model(N, q, s, e)
         rs, qs = direct_split(e, s, N, q)
         assert np.array_equal(rem, rs) and np.array_equal(quot, qs), (N, q, "shared full-range product")
+        r1 = direct_split(e, f % q, N, q)[0]               # (e has changed since)
+        a = np.where(2 * r1 > q, r1 - q, r1)
+        peak, energy = noise_model(N, q, f, e)
+        assert np.array_equal(peak, np.abs(a).max(axis=1)) and np.array_equal(energy, (a * a).sum(axis=1)), (N, q, "noise")
         print("N=%d q=%d: tiles %d, strips %s  OK" % (N, q, tiles(N)[0], strips(tiles(N)[0])))
 
 
