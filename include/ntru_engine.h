@@ -738,6 +738,47 @@ int ntru_mix_batch_dev(ntru_engine_t *eng, int N, int q, int p, const uint16_t *
 int ntru_mix_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const uint32_t *key, uint64_t first_item, int n1, int n2,
                    uint64_t perm_id, const uint16_t *e_in, int64_t B, uint8_t *r_out, int64_t *src_out, uint16_t *e_out, uint16_t *quotE);
 
+/* ---- removing duplicates: which rows of a batch repeat an earlier row, of the batch or of a set accepted before (dedup_rows.hip).  A
+ *      replayed ciphertext counts twice in a tally and comes out of a mix as a recognisable pair, so intake rejects it first.
+ *      Two rows are EQUAL MODULO mod when row_a[k] % mod == row_b[k] % mod for every k < N; 2 <= N <= NTRU_MAX_N, 2 <= mod <= 65536,
+ *      a power of two or not (mod == 65536: raw equality).  A row with mod added to a coefficient is therefore a duplicate.  Packed
+ *      rows ([rows][output_size][4] uint64_t, geometry from ntru_pack_params(mod - 1, N, ...), "packed ciphertexts" above) compare by
+ *      their N fields, each reduced modulo mod: fields with index >= N and the bits of an element above per * bits are ignored, and a
+ *      raw field >= mod counts as its remainder.  A homomorphically re-randomised copy is a different row: out of scope here.
+ *      The S rows of `prior` (accepted in earlier batches; S may be 0 with prior NULL) take the indices 0 .. S - 1, the B new rows
+ *      S .. S + B - 1; both sets in the same format; S + B <= NTRU_DEDUP_MAX_ROWS.  Outputs, for the B new rows only:
+ *        first  [B] int64_t  first[b] = the smallest combined index of a row equal to new row b; row b is a first occurrence exactly
+ *                            when first[b] == S + b (prior rows may repeat one another: the smallest index is named);
+ *        unique [B] int64_t  the batch-local indices b of the first occurrences, ascending; only the first count[0] entries are
+ *                            written, nothing behind them;
+ *        count  [1] int64_t  SET to the number of first occurrences.
+ *      first may be NULL, unique may be NULL, count is required.  Positions come from prefix sums only, never from the arrival order
+ *      of an atomic: the bytes are the same for any launch shape, salt and fingerprint width.
+ *      salt keys the 64-bit row fingerprint that is sorted (ntru_argsort_keys_dev): a submitter who does not know it cannot craft
+ *      fingerprint collisions; results do not depend on it.  fingerprint_bits (0 .. 64; 64 in production) keeps only that many low
+ *      bits: fewer cost time (rows with equal fingerprints are compared in full, a first occurrence against every earlier distinct
+ *      row of its fingerprint) and never change a byte of the result; 0 makes every row collide.  Equality is always decided on
+ *      the full reduced rows, never on the fingerprint, whose function is internal.
+ *      _dev: enqueued on the engine's stream without synchronising, nothing is allocated; d_work is a caller-owned device workspace of
+ *      ntru_dedup_workspace_bytes(N, S + B) bytes (fingerprints, sorted order, flags; monotone in the row count, 256-byte granular),
+ *      as ntru_keygen_workspace_bytes.  The sort takes the engine's scratch buffer for itself.
+ *      Host forms: the S + B rows, the workspace and the outputs live in the engine's resident buffer for the call; the rows go up
+ *      through the staging pipeline; count, first and the count[0]-entry prefix of unique come down.
+ *      NTRU_ERR_ARG with a message of its own, before the engine is looked at: B < 0 or S < 0, S + B > NTRU_DEDUP_MAX_ROWS,
+ *      fingerprint_bits outside 0 .. 64, N or mod out of range, a NULL count, a NULL required buffer with B > 0, S > 0 with a NULL
+ *      prior, overlapping outputs (with one another, the inputs or the workspace); then a NULL engine.  B == 0 sets count[0] = 0 and
+ *      launches nothing else. */
+#define NTRU_DEDUP_MAX_ROWS NTRU_PERM_MAX_B                      /* S + B */
+int ntru_dedup_workspace_bytes(int N, int64_t total_rows, size_t *bytes);
+int ntru_dedup_rows_dev(ntru_engine_t *eng, int N, int mod, const uint16_t *d_prior, int64_t S, const uint16_t *d_rows, int64_t B,
+                        uint64_t salt, int fingerprint_bits, void *d_work, int64_t *d_first, int64_t *d_unique, int64_t *d_count);
+int ntru_dedup_packed_dev(ntru_engine_t *eng, int N, int mod, const uint64_t *d_prior, int64_t S, const uint64_t *d_packed, int64_t B,
+                          uint64_t salt, int fingerprint_bits, void *d_work, int64_t *d_first, int64_t *d_unique, int64_t *d_count);
+int ntru_dedup_rows(ntru_engine_t *eng, int N, int mod, const uint16_t *prior, int64_t S, const uint16_t *rows, int64_t B, uint64_t salt,
+                    int fingerprint_bits, int64_t *first, int64_t *unique, int64_t *count);
+int ntru_dedup_packed(ntru_engine_t *eng, int N, int mod, const uint64_t *prior, int64_t S, const uint64_t *packed, int64_t B,
+                      uint64_t salt, int fingerprint_bits, int64_t *first, int64_t *unique, int64_t *count);
+
 #ifdef __cplusplus
 }
 #endif

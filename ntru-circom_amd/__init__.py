@@ -19,6 +19,9 @@ Layout
   shared_product.py      multiplying a batch by one shared polynomial, with the split by 1 - x^N (functions on an Engine)
   csrc/matrix_noise.hip  the decryption noise of rows under a key: decrypt's first product reduced to peak and energy (k_noise_m)
   noise.py               measuring noise: peak = max |a centred|, energy = sum of squares, per row, dense or packed (functions on an Engine)
+  csrc/dedup_rows.hip    the duplicate rows of a batch: keyed fingerprints, the stable argsort, one exact neighbour comparison, compaction
+  dedup.py               removing duplicates: first occurrence and unique list of a batch against a prior set, dense or packed (functions on an
+                         Engine)
   scan.py                scanning a batch for the rows a key decrypts to a tagged message; only the hits come back (functions on an Engine)
   ntru.py                `NTRU` class + pure functions with the reference's names and semantics (index.js)
   js/                    N-API addon + ES-module shim exposing the same surface to Node.js
@@ -28,10 +31,11 @@ raises `EngineError` when it (or a GPU) is missing.
 """
 from .engine import (FLAG_NOT_BITS, FLAG_PAD_NONZERO, Engine, EngineError, MultiEngine, library_path,  # noqa: F401
                      load_library)
-from . import combine, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
+from . import combine, dedup, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
 from .combine import combine_batch, combine_batch_dev  # noqa: F401
 from .shared_product import mul_shared_batch, mul_shared_batch_dev  # noqa: F401
 from .noise import noise_batch, noise_batch_dev, noise_packed_batch, noise_packed_batch_dev  # noqa: F401
+from .dedup import dedup_packed, dedup_packed_dev, dedup_rows, dedup_rows_dev, dedup_workspace_bytes  # noqa: F401
 from .mix import reencrypt_batch, reencrypt_batch_dev  # noqa: F401
 from .mix import (argsort_keys_dev, draw_permutation, draw_permutation_dev, mix_batch, mix_batch_dev)  # noqa: F401
 from .scan import (scan_bytes_batch, scan_bytes_batch_dev, scan_bytes_packed_batch,  # noqa: F401

@@ -38,6 +38,10 @@
 //                            peak and energy in the epilogue (k_noise_m), the vector-ALU decrypt's rem1 reduced pass by pass for
 //                            everything outside its range (k_noise_rows), dense and packed rows (kernels, *_dev and host-pointer entry
 //                            points)
+//   dedup_rows.hip           the duplicate rows of a batch, dense or packed, against an optional prior set: keyed 64-bit fingerprints
+//                            (k_dedup_fingerprint), permutation.hip's stable argsort, one exact comparison with the sorted
+//                            predecessor (k_dedup_neighbours), a walk for true collisions only (k_dedup_walk), prefix-sum compaction
+//                            (kernels, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

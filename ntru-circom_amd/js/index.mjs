@@ -690,6 +690,32 @@ export default class NTRU {
     return { peak, energy, margin };
   }
 
+  // Which of the ciphertexts e: Uint16Array[B*N] repeat an earlier row of the batch or of prior: Uint16Array[S*N] (rows accepted before)
+  // -> { first: Array of B Numbers, unique: Array of Numbers }.  Rows are equal when every coefficient agrees modulo q.  The prior rows
+  // take the indices 0 .. S - 1, the new rows S .. S + B - 1; first[b] is the smallest index of a row equal to row b, unique the
+  // batch-local b with first[b] === S + b, ascending.  Composed in JavaScript, a map from the reduced row to the index that saw it first:
+  // the same numbers as the engine's ntru_dedup_rows, which fingerprints, sorts and compares on the device, but not that call
+  // (INTEGRATION.md, "Removing duplicates").
+  dedupCiphertexts(e, B, { prior = null } = {}) {
+    const { N, q } = this;
+    if (!(e instanceof Uint16Array) || e.length !== B * N) throw new TypeError(`dedupCiphertexts: e must be a Uint16Array of B * N = ${B * N} values`);
+    if (prior !== null && (!(prior instanceof Uint16Array) || prior.length % N !== 0)) throw new TypeError('dedupCiphertexts: prior must be a Uint16Array of whole rows');
+    const S = prior === null ? 0 : prior.length / N;
+    const seen = new Map(), first = new Array(B), unique = [], row = new Uint16Array(N);
+    const keyOf = (a, at) => {
+      for (let k = 0; k < N; k++) row[k] = a[at + k] % q;
+      return String.fromCharCode.apply(null, row);
+    };
+    for (let i = 0; i < S; i++) { const key = keyOf(prior, i * N); if (!seen.has(key)) seen.set(key, i); }
+    for (let b = 0; b < B; b++) {
+      const key = keyOf(e, b * N);
+      if (!seen.has(key)) seen.set(key, S + b);
+      first[b] = seen.get(key);
+      if (first[b] === S + b) unique.push(b);
+    }
+    return { first, unique };
+  }
+
   // tallyBatch on ciphertexts in the wire format: packed is BigUint64Array[B * outputSize * 4], rows of packOutput(q - 1, N, e).  Composed
   // from unpackBatch and tallyDecryptBatch (same results as ntru_tally_decrypt_packed_batch, not that call).
   tallyPackedBatch(packed, B, offsets = null, weights = null, wantWitness = true) {

@@ -19,6 +19,7 @@ import secrets
 import numpy as np
 
 from . import combine as combine_calls
+from . import dedup as dedup_calls
 from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
@@ -524,6 +525,22 @@ class NTRU:
         else:
             peak, energy = noise_calls.noise_batch(self.engine, N, q, f, np.asarray(rows).reshape(-1, N))
         return {"peak": peak, "energy": energy, "margin": (q // 2 - peak.astype(np.int64))}
+
+    def dedupBatch(self, rows, packed=False, prior=None, salt=None):
+        """Which of the ciphertexts `rows` ([B][N], or packed rows [B][outputSize][4] with packed=True) repeat an earlier row of the
+        batch or of `prior` (rows accepted before, same format): {"first", "unique"}.  Rows are equal when every coefficient agrees
+        modulo q.  The S prior rows take the indices 0 .. S - 1 and the new rows S .. S + B - 1; first[b] is the smallest index of a
+        row equal to row b, unique the batch-local indices of the rows with first[b] == S + b, ascending.  salt keys the fingerprint
+        that is sorted and never changes the result; None draws one from `secrets`."""
+        N, q = self.N, self.q
+        if salt is None:
+            salt = secrets.randbits(64)
+        if packed:
+            first, unique = dedup_calls.dedup_packed(self.engine, N, q, rows, prior=prior, salt=salt)
+        else:
+            first, unique = dedup_calls.dedup_rows(self.engine, N, q, np.asarray(rows).reshape(-1, N),
+                                                   prior=None if prior is None else np.asarray(prior).reshape(-1, N), salt=salt)
+        return {"first": first, "unique": unique}
 
     # -- the same on ciphertexts in the wire format: rows of packOutput(q - 1, N, e), uint64 [B][outputSize][4] ----------------------------
     def tallyPacked(self, packed, offsets=None, weights=None, wantWitness=True):
