@@ -350,7 +350,8 @@ int ntru_decrypt_batch_dev(ntru_engine_t *eng, int N, int q, int p, const int8_t
  * kernel argument.  Honoured by everything that runs decryptBits: ntru_decrypt_batch[_dev], ntru_decrypt_batch_pitched_dev,
  * ntru_decrypt_pack_batch_dev, ntru_decrypt_peritem_batch[_dev], ntru_decrypt_bytes_batch[_dev], ntru_tally_decrypt_batch[_dev],
  * ntru_tally_decrypt_packed_batch[_dev], ntru_decrypt_packed_batch[_dev], the decrypt stage of ntru_pipeline_batch and
- * ntru_pipeline_bytes_batch, ntru_scan_bytes_batch[_dev], ntru_scan_bytes_packed_batch[_dev], ntru_multi_decrypt_batch (ntru_multi_set_lift). ntru_check_decrypt_batch checks the circuit and
+ * ntru_pipeline_bytes_batch, ntru_scan_bytes_batch[_dev], ntru_scan_bytes_packed_batch[_dev], ntru_count_bytes_batch[_dev],
+ * ntru_count_bytes_packed_batch[_dev], ntru_multi_decrypt_batch (ntru_multi_set_lift). ntru_check_decrypt_batch checks the circuit and
  * ntru_verify_keys_batch has no lift: neither changes.
  * The mode is read when a call enqueues and reaches the kernel by value: a _dev call enqueued before a later ntru_engine_set_lift
  * keeps the mode it was enqueued with.  As with ntru_engine_set_stream and ntru_engine_set_kernel_path, do not change it while a
@@ -444,6 +445,64 @@ int ntru_scan_bytes_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, in
                                      const uint8_t *d_fp, const uint64_t *d_packed, int64_t B, int tag_off, int tag_len,
                                      const uint8_t *tag, int64_t max_hits, int64_t *d_hit_row, uint8_t *d_hit_bytes,
                                      int64_t *d_count);
+
+/* ---- counting: how many rows of a batch decrypt to each choice, per group?  The end of a ballot pipeline: a homomorphic tally counts
+ *      at most p - 1 votes per coefficient, so after the last mix step every row is decrypted (decryptStr, index.js:84-86, on
+ *      decryptBits, index.js:111-140), the choice is read out of the message and counted.  One decrypt of the batch classifies every
+ *      row on the device; only the table, and optionally one class id per row, cross the bus.
+ *      For value = decryptBits(e[b]).value under (f, fp) and (bytes, flag) = ntru_rows_to_bytes(value), cls(b) is the FIRST of these
+ *      that applies, with n_bins = n_choices + 3:
+ *        1. flag != 0                                                          NTRU_COUNT_MALFORMED(n_choices) = n_choices + 2
+ *        2. bytes [tag_off, tag_off + tag_len) differ from tag[0 .. tag_len)   NTRU_COUNT_BAD_TAG(n_choices)   = n_choices + 1
+ *        3. v = the big-endian integer of bytes [field_off, field_off + field_len); v < first_choice or
+ *           v - first_choice >= n_choices (compared in 64 bits: first_choice + n_choices may pass 2^32)
+ *                                                                              NTRU_COUNT_OTHER(n_choices)     = n_choices
+ *        4. otherwise                                                          v - first_choice
+ *      tag is a HOST pointer in every form, as in "scanning": 0 <= tag_len <= NTRU_SCAN_MAX_TAG, tag_off >= 0, tag_off + tag_len <=
+ *      nbytes; tag_len == 0 skips step 2 (tag may then be NULL).  1 <= field_len <= 4, field_off >= 0, field_off + field_len <= nbytes;
+ *      the field may overlap the tag.  first_choice is a 32-bit value, 0 <= first_choice < 2^32 (the parameter is a uint64_t as
+ *      every unsigned scalar of this header).  1 <= n_choices <= NTRU_COUNT_MAX_CHOICES, G >= 1, G * n_bins <= NTRU_COUNT_MAX_BINS.
+ *      f [N] int8_t, fp [N] uint8_t: one private key.  e [B][N] uint16_t, or packed [B][output_size][4] uint64_t, the wire format of
+ *      "packed ciphertexts" above (ignored fields and bits as there).  group [B] int32_t: the group of every row, or NULL -- then G
+ *      must be 1 and every row is in group 0.
+ *      count [G][n_bins] int64_t is SET: count[g][c] is the number of rows with group == g and cls == c.  Every row with a valid group
+ *      lands in exactly one bin, so count[g] sums to the size of group g.  cls [B] int32_t (may be NULL) receives cls(b).  count
+ *      needs 8-byte alignment, group and cls 4-byte alignment.
+ *      A group id outside [0, G): the _dev forms count such a row nowhere and give it cls[b] = -1; the host forms reject it as
+ *      NTRU_ERR_ARG before any launch and name the index (as ntru_reencrypt_batch treats src).
+ *      Integer counts do not depend on the order of the adds: the bytes of count and cls are the same whatever the launch shape, the
+ *      pass size, the kernel path, the route the bins are accumulated by and the chunking of the host form.
+ *      Domain: that of ntru_decrypt_bytes_batch; the packed forms as ntru_decrypt_packed_batch.  Each of these is NTRU_ERR_ARG with a
+ *      message of its own, before the engine is looked at: a NULL buffer, a tag or a field outside the message, first_choice, n_choices, G
+ *      or G * n_bins out of range, a NULL group with G > 1, count and cls that overlap.  B == 0 sets the counts to 0 and launches nothing
+ *      else.  The lift is the engine's mode (ntru_engine_set_lift), read at enqueue.
+ *   _dev forms: enqueue on the engine's stream, do not synchronise and allocate nothing per call beyond the engine-owned scratch
+ *      buffer: d_count is cleared on the stream, then rows go in passes of at most 65536; per pass (packed: k_unpack_rows first)
+ *      ntru_decrypt_batch_dev and ntru_rows_to_bytes_dev run as they are into scratch, then k_count_classify (count_bytes.hip), one lane
+ *      per row: up to 8192 bins are counted in a workgroup-private LDS histogram and flushed with one 64-bit atomic add per non-zero
+ *      bin, larger tables take one 64-bit atomic add per row.
+ *   host forms: the rows (and group) stream through the chunked pipeline with the key as shared inputs and cls as a per-row output;
+ *      the table stays on the device until the last chunk and comes down once.  count is a host array. */
+#define NTRU_COUNT_MAX_CHOICES 65536
+#define NTRU_COUNT_MAX_BINS (1 << 24)
+#define NTRU_COUNT_OTHER(n_choices) (n_choices)
+#define NTRU_COUNT_BAD_TAG(n_choices) ((n_choices) + 1)
+#define NTRU_COUNT_MALFORMED(n_choices) ((n_choices) + 2)
+int ntru_count_bytes_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp, const uint16_t *e,
+                           int64_t B, int tag_off, int tag_len, const uint8_t *tag, int field_off, int field_len,
+                           uint64_t first_choice, int n_choices, int G, const int32_t *group, int64_t *count, int32_t *cls);
+int ntru_count_bytes_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *d_f, const uint8_t *d_fp,
+                               const uint16_t *d_e, int64_t B, int tag_off, int tag_len, const uint8_t *tag, int field_off,
+                               int field_len, uint64_t first_choice, int n_choices, int G, const int32_t *d_group, int64_t *d_count,
+                               int32_t *d_cls);
+int ntru_count_bytes_packed_batch(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *f, const uint8_t *fp,
+                                  const uint64_t *packed, int64_t B, int tag_off, int tag_len, const uint8_t *tag, int field_off,
+                                  int field_len, uint64_t first_choice, int n_choices, int G, const int32_t *group, int64_t *count,
+                                  int32_t *cls);
+int ntru_count_bytes_packed_batch_dev(ntru_engine_t *eng, int N, int q, int p, int nbytes, const int8_t *d_f, const uint8_t *d_fp,
+                                      const uint64_t *d_packed, int64_t B, int tag_off, int tag_len, const uint8_t *tag,
+                                      int field_off, int field_len, uint64_t first_choice, int n_choices, int G,
+                                      const int32_t *d_group, int64_t *d_count, int32_t *d_cls);
 
 /* ---- encryptBits and decryptBits with a SEPARATE key pair for every item (one ciphertext per recipient, one decryption per key
  *      holder): h, f and fp are [B][N] batch arrays with the types and layout of ntru_keygen_batch's outputs, so its device arrays

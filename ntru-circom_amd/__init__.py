@@ -23,6 +23,9 @@ Layout
   dedup.py               removing duplicates: first occurrence and unique list of a batch against a prior set, dense or packed (functions on an
                          Engine)
   scan.py                scanning a batch for the rows a key decrypts to a tagged message; only the hits come back (functions on an Engine)
+  csrc/count_bytes.hip   the decrypted byte messages of a batch classified on the device and counted by choice and group (k_count_classify)
+  count.py               counting decrypted messages: count [G][n_choices + 3] and optional per-row classes, dense or packed (functions on
+                         an Engine)
   ntru.py                `NTRU` class + pure functions with the reference's names and semantics (index.js)
   js/                    N-API addon + ES-module shim exposing the same surface to Node.js
 
@@ -31,7 +34,7 @@ raises `EngineError` when it (or a GPU) is missing.
 """
 from .engine import (FLAG_NOT_BITS, FLAG_PAD_NONZERO, Engine, EngineError, MultiEngine, library_path,  # noqa: F401
                      load_library)
-from . import combine, dedup, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
+from . import combine, count, dedup, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
 from .combine import combine_batch, combine_batch_dev  # noqa: F401
 from .shared_product import mul_shared_batch, mul_shared_batch_dev  # noqa: F401
 from .noise import noise_batch, noise_batch_dev, noise_packed_batch, noise_packed_batch_dev  # noqa: F401
@@ -40,6 +43,8 @@ from .mix import reencrypt_batch, reencrypt_batch_dev  # noqa: F401
 from .mix import (argsort_keys_dev, draw_permutation, draw_permutation_dev, mix_batch, mix_batch_dev)  # noqa: F401
 from .scan import (scan_bytes_batch, scan_bytes_batch_dev, scan_bytes_packed_batch,  # noqa: F401
                    scan_bytes_packed_batch_dev)
+from .count import (count_bytes_batch, count_bytes_batch_dev, count_bytes_packed_batch,  # noqa: F401
+                    count_bytes_packed_batch_dev)
 from .packed import (decrypt_packed_batch, decrypt_packed_batch_dev, pack_rows, sum_groups_packed,  # noqa: F401
                      sum_groups_packed_dev, tally_decrypt_packed_batch, tally_decrypt_packed_batch_dev, unpack_rows)
 from .ntru import (NTRU, addCiphertexts, addPolynomials, bigintToBits, bitsToBigInt, bitsToString, degree,  # noqa: F401

@@ -42,6 +42,9 @@
 //                            (k_dedup_fingerprint), permutation.hip's stable argsort, one exact comparison with the sorted
 //                            predecessor (k_dedup_neighbours), a walk for true collisions only (k_dedup_walk), prefix-sum compaction
 //                            (kernels, *_dev and host-pointer entry points)
+//   count_bytes.hip          the decrypted byte messages of a batch counted by choice and group: decrypt and rows_to_bytes as they
+//                            are, then one classifying kernel (k_count_classify) that counts in an LDS histogram or, for large
+//                            tables, with one global atomic per row (kernel, *_dev and host-pointer entry points)
 // Every kernel family exports the host function that launches it (ntru_launch_*, hidden visibility); a launcher returns
 // NTRU_NOT_TAKEN when the parameters are outside its family's range and the dispatcher in abi.hip tries the next one.
 #ifndef NTRU_ENGINE_INTERNAL_H

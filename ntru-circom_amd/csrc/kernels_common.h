@@ -54,6 +54,32 @@ static __device__ __forceinline__ void wg_inclusive_scan(u32 *s, int tid) {
   }
 }
 
+// ---- the tag of the scanning and counting calls (scan_hits.hip, count_bytes.hip) ---------------------------------------------------
+// At most NTRU_SCAN_MAX_TAG bytes, read on the host when the call enqueues; it reaches the kernels by value.
+static_assert(NTRU_SCAN_MAX_TAG == 32, "ScanTag holds eight words");
+struct ScanTag {
+  u32 w[NTRU_SCAN_MAX_TAG / 4];                // byte j of the tag in bits 8 (j % 4) .. of word j / 4
+  int off, len;
+};
+static inline ScanTag tag_of(int tag_off, int tag_len, const uint8_t *tag) {
+  ScanTag t;
+  memset(&t, 0, sizeof t);
+  for (int j = 0; j < tag_len; j++) t.w[j >> 2] |= (u32)tag[j] << (8 * (j & 3));
+  t.off = tag_off;
+  t.len = tag_len;
+  return t;
+}
+// Do the bytes [tag.off, tag.off + tag.len) of the message m equal the tag?  (tag.len is uniform: the loop is scalar control flow
+// around byte loads.)
+static __device__ __forceinline__ bool tag_matches(const uint8_t *__restrict__ m, const ScanTag &tag) {
+  m += tag.off;
+  u32 diff = 0;
+#pragma unroll
+  for (int j = 0; j < NTRU_SCAN_MAX_TAG; j++)
+    if (j < tag.len) diff |= (u32)m[j] ^ ((tag.w[j >> 2] >> (8 * (j & 3))) & 0xffu);
+  return diff == 0;
+}
+
 // ---- bit spreads between packed small values and bytes ---------------------------------------------------------------------------
 // bit j of a nibble -> bit 0 of byte j, and back
 static __host__ __device__ __forceinline__ constexpr u32 nibble_to_bytes(u32 nib) { return (nib * 0x00204081u) & 0x01010101u; }

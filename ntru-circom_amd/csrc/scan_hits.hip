@@ -33,23 +33,12 @@ namespace {
 constexpr int SC_ROWS = 256;                   // rows = lanes per workgroup of the select kernels
 constexpr int64_t SC_PASS = 1 << 16;           // rows per pass, as the byte and packed calls
 static_assert(SC_PASS / SC_ROWS <= SC_ROWS, "k_scan_offsets scans the block counts of a pass in one workgroup");
-static_assert(NTRU_SCAN_MAX_TAG == 32, "ScanTag holds eight words");
 
-struct ScanTag {
-  u32 w[NTRU_SCAN_MAX_TAG / 4];                // byte j of the tag in bits 8 (j % 4) .. of word j / 4
-  int off, len;
-};
-
-// Is row r of the pass a hit?  (tag.len is uniform: the loop is scalar control flow around byte loads.)
+// Is row r of the pass a hit?  (ScanTag and the tag test are in kernels_common.h: count_bytes.hip classifies rows with them too.)
 __device__ __forceinline__ bool row_hits(const uint8_t *__restrict__ bytes, const uint8_t *__restrict__ flags, int r, int nbytes,
                                          const ScanTag &tag) {
   if (flags[r] != 0) return false;
-  const uint8_t *m = bytes + (long)r * nbytes + tag.off;
-  u32 diff = 0;
-#pragma unroll
-  for (int j = 0; j < NTRU_SCAN_MAX_TAG; j++)
-    if (j < tag.len) diff |= (u32)m[j] ^ ((tag.w[j >> 2] >> (8 * (j & 3))) & 0xffu);
-  return diff == 0;
+  return tag_matches(bytes + (long)r * nbytes, tag);
 }
 
 __global__ void __launch_bounds__(SC_ROWS) k_scan_mark(int nbytes, ScanTag tag, const uint8_t *__restrict__ bytes,
@@ -146,15 +135,6 @@ int check_scan_args(const ntru_engine *eng, const char *who, bool packed, int N,
     if (int rc = ntru_pack_params(q - 1, N, &bits, &per, &al, os)) return rc;
   }
   return NTRU_OK;
-}
-
-ScanTag tag_of(int tag_off, int tag_len, const uint8_t *tag) {
-  ScanTag t;
-  memset(&t, 0, sizeof t);
-  for (int j = 0; j < tag_len; j++) t.w[j >> 2] |= (u32)tag[j] << (8 * (j & 3));
-  t.off = tag_off;
-  t.len = tag_len;
-  return t;
 }
 
 // Enqueues the scan of B rows -- dense (os == 0: d_rows is uint16_t [B][N]) or packed (uint64_t [B][os][4]) -- under K keys on

@@ -109,6 +109,9 @@ _SIGS = {
     # scanning a batch for the rows a key decrypts to a tagged message: the functions are in scan.py
     **_both("ntru_scan_bytes_batch", "p iiiii ppp l ii p l ppp"),
     **_both("ntru_scan_bytes_packed_batch", "p iiiii ppp l ii p l ppp"),
+    # counting the decrypted byte messages of a batch by choice and group: the functions are in count.py
+    **_both("ntru_count_bytes_batch", "p iiii ppp l ii p ii u ii ppp"),
+    **_both("ntru_count_bytes_packed_batch", "p iiii ppp l ii p ii u ii ppp"),
     # removing duplicates, dense and packed: the functions are in dedup.py
     "ntru_dedup_workspace_bytes": _sig("i l Z"),
     "ntru_dedup_rows": _sig("p ii p l p l u i ppp"), "ntru_dedup_rows_dev": _sig("p ii p l p l u i pppp"),

@@ -24,6 +24,7 @@ from . import lift as lift_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
 from . import scan as scan_calls
+from . import count as count_calls
 from . import noise as noise_calls
 from . import shared_product as shared_calls
 from .engine import (FLAG_INVALID_FP, FLAG_INVALID_FQ, FLAG_INVALID_H, FLAG_NOT_UNIT_MOD2, FLAG_NOT_UNIT_MODP,
@@ -292,7 +293,7 @@ class NTRU:
 
     lift="reference" (the default) decrypts with index.js:117 verbatim and never touches the engine's mode; lift="centred" runs every
     decrypt-family method (decryptBits, decryptStr, decryptBytes, tallyBatch, tallyPacked, decryptPackedBatch, decryptBatchPerKey, scanBytes,
-    scanPacked, the decrypt stage of pipeline) with the engine in the centred mode and puts the engine back into the mode it had (lift.py), so
+    scanPacked, countBytes, countPacked, the decrypt stage of pipeline) with the engine in the centred mode and puts the engine back into the mode it had (lift.py), so
     an engine shared by two instances is never left in the other's mode.  The centred mode returns the plaintext where the reference's
     `+ 1` does not (q = 4096 with p = 3, p = 5 or 7 at almost every q).  The `params` of a witness do not depend on the mode;
     VerifyDecrypt (checkWitnesses) accepts a centred witness only when the addend (p - q % p) % p is 1."""
@@ -737,6 +738,32 @@ class NTRU:
     def scanPacked(self, packed, keys=None, tag=b"", tagOffset=0, maxHits=None):
         """scanBytes on blocks in the wire format: rows of packOutput(q - 1, N, e), uint64 [blocks][outputSize][4]."""
         return self._scan(scan_calls.scan_bytes_packed_batch, packed, keys, tag, tagOffset, maxHits)
+
+    # -- counting: how many blocks decrypt to each choice, per group? -----------------------------------------------------------------
+    def _count(self, call, rows, firstChoice, nChoices, fieldOffset, fieldLength, tag, tagOffset, groups, G, classes):
+        N = self.N
+        if self.f is None:
+            raise TypeError("Cannot read property 'map' of null")                  # what index.js:112 does
+        with self._lifted():
+            count, cls = call(self.engine, N, self.q, self.p, self.bytesPerBlock, expandArray(self.f, N), expandArray(self.fp, N), rows,
+                              firstChoice, nChoices, fieldOffset, fieldLength, tag=tag, tag_off=tagOffset, groups=groups, G=G,
+                              classes=classes)
+        return {"count": count, "classes": cls}
+
+    def countBytes(self, e, firstChoice, nChoices, fieldOffset, fieldLength, tag=b"", tagOffset=0, groups=None, G=1, classes=False):
+        """Decrypts every block of e [blocks][N] once under this instance's key and counts the blocks by choice and group on the device.
+        The class of a block is the first that applies of: decryptBytes gives it a flag -> nChoices + 2 (malformed); its bytes
+        [tagOffset, tagOffset + len(tag)) differ from `tag` (at most 32 bytes) -> nChoices + 1 (wrong tag); v, the big-endian integer
+        of its bytes [fieldOffset, fieldOffset + fieldLength) (1 to 4 bytes), lies outside [firstChoice, firstChoice + nChoices) ->
+        nChoices (other); else v - firstChoice.  groups: [blocks] ids in [0, G), or None for one group.  Returns {"count": int64
+        [G][nChoices + 3], "classes": int32 [blocks] or None (classes=False)}; only these cross the bus."""
+        return self._count(count_calls.count_bytes_batch, np.asarray(e, dtype=np.uint16).reshape(-1, self.N), firstChoice, nChoices,
+                           fieldOffset, fieldLength, tag, tagOffset, groups, G, classes)
+
+    def countPacked(self, packed, firstChoice, nChoices, fieldOffset, fieldLength, tag=b"", tagOffset=0, groups=None, G=1, classes=False):
+        """countBytes on blocks in the wire format: rows of packOutput(q - 1, N, e), uint64 [blocks][outputSize][4]."""
+        return self._count(count_calls.count_bytes_packed_batch, packed, firstChoice, nChoices, fieldOffset, fieldLength, tag, tagOffset,
+                           groups, G, classes)
 
     def encryptStr(self, inputPlain):
         return self.encryptBits(stringToBits(inputPlain))["value"]
