@@ -797,6 +797,43 @@ int ntru_mix_batch_dev(ntru_engine_t *eng, int N, int q, int p, const uint16_t *
 int ntru_mix_batch(ntru_engine_t *eng, int N, int q, int p, const uint16_t *h, const uint32_t *key, uint64_t first_item, int n1, int n2,
                    uint64_t perm_id, const uint16_t *e_in, int64_t B, uint8_t *r_out, int64_t *src_out, uint16_t *e_out, uint16_t *quotE);
 
+/* ---- auditing a mix: checking revealed re-encryption links (mix_audit.hip).  A mixer that opens a link names (index in, index out,
+ *      r); link l of L holds when, coefficient by coefficient,
+ *        e_out[o] == r[l] * h + e_in[i]   modulo (x^N - 1, q),   i = in_idx ? in_idx[l] : l,   o = out_idx ? out_idx[l] : l,
+ *      both sides reduced mod q (a coefficient with q added still matches; q == 65536: raw equality).  This is what
+ *      ntru_reencrypt_batch computes, compared against a row instead of stored: no quotient, 5 N bytes read per link, one written.
+ *      r [L][N] uint8_t; in_idx, out_idx [L] int64_t (DEVICE memory in the _dev form; either may be NULL); e_in [B_in][N] and e_out
+ *      [B_out][N] uint16_t, any value, may be the same array or overlap (both are only read); flags [L] uint8_t; n_bad one int64_t,
+ *      SET to the number of links whose flag is not 0 (a device scalar in the _dev form; may be NULL).  Nothing is written to r, e_in
+ *      or e_out.  flags[l] is 0 when the link holds, else
+ *        NTRU_LINK_BAD_INDEX  i outside [0, B_in) or o outside [0, B_out): no row of that link is read.  A finding in BOTH forms, not
+ *                             an argument error (here the host form differs from ntru_reencrypt_batch);
+ *        NTRU_LINK_BAD_R      a byte of r[l] outside {0, 1, other}; or n1 >= 0 and the ones do not number n1; or n2 >= 0 and the
+ *                             bytes equal to other do not number n2.  With other == 1 the two counts are of the same bytes: the ones
+ *                             must number n1 + n2 when both are given, and are not counted when either is negative;
+ *        NTRU_LINK_MISMATCH   some coefficient differs.  Reported only when neither other bit is set: a link with a bad index or a
+ *                             bad r carries exactly those bits, and its product is never relied on.
+ *      other is 1, 2 or 3 (p - 1; 2 for p = 3): the matrix planes carry 32 r without carries only for r <= 3.
+ *      Where the matrix-core encrypt applies (64 <= N <= 1024, a power-of-two q <= 8192, kernel paths 0, 4 and 5) this is ONE kernel,
+ *      k_linkcheck_md / k_linkcheck_m by the rule of k_reencrypt_md / _m: the encrypt body with the gathered e_in row as addend and
+ *      a compare against the columns of e_out[o] in the place of the stores.  Elsewhere the vector-ALU encrypt of a zero message
+ *      into the engine's scratch, at most 65536 links per pass (with the bytes of r outside the domain cleared first, so that it
+ *      only ever sees its documented operands), then k_compare_links.
+ *      NTRU_ERR_ARG before anything is launched: a NULL required buffer with L > 0, a negative size, other outside 1 .. 3,
+ *      n1 + n2 > N, flags (or n_bad) overlapping an input, and what every batch call refuses (a NULL engine, an unsupported (N, q)).
+ *      L == 0 launches nothing and sets n_bad to 0 when it is given.
+ *      _dev: enqueued on the engine's stream, no synchronisation, nothing allocated per call.  Host form: the links run through the
+ *      chunked pipeline, both rows of a link gathered on the host while a chunk's staging buffer is filled. */
+#define NTRU_LINK_BAD_INDEX 1
+#define NTRU_LINK_BAD_R 2
+#define NTRU_LINK_MISMATCH 4
+int ntru_check_links_batch_dev(ntru_engine_t *eng, int N, int q, int other, int n1, int n2, const uint16_t *d_h, const uint8_t *d_r,
+                               const uint16_t *d_e_in, int64_t B_in, const int64_t *d_in_idx, const uint16_t *d_e_out, int64_t B_out,
+                               const int64_t *d_out_idx, int64_t L, uint8_t *d_flags, int64_t *d_n_bad);
+int ntru_check_links_batch(ntru_engine_t *eng, int N, int q, int other, int n1, int n2, const uint16_t *h, const uint8_t *r,
+                           const uint16_t *e_in, int64_t B_in, const int64_t *in_idx, const uint16_t *e_out, int64_t B_out,
+                           const int64_t *out_idx, int64_t L, uint8_t *flags, int64_t *n_bad);
+
 /* ---- removing duplicates: which rows of a batch repeat an earlier row, of the batch or of a set accepted before (dedup_rows.hip).  A
  *      replayed ciphertext counts twice in a tally and comes out of a mix as a recognisable pair, so intake rejects it first.
  *      Two rows are EQUAL MODULO mod when row_a[k] % mod == row_b[k] % mod for every k < N; 2 <= N <= NTRU_MAX_N, 2 <= mod <= 65536,

@@ -22,6 +22,8 @@ Layout
   csrc/dedup_rows.hip    the duplicate rows of a batch: keyed fingerprints, the stable argsort, one exact neighbour comparison, compaction
   dedup.py               removing duplicates: first occurrence and unique list of a batch against a prior set, dense or packed (functions on an
                          Engine)
+  csrc/mix_audit.hip     checking revealed re-encryption links: the encrypt body with a compare in the place of the stores (k_linkcheck_m)
+  audit.py               auditing a mix: check_links, and randomized partial checking of a pair of mix steps (functions on an Engine)
   scan.py                scanning a batch for the rows a key decrypts to a tagged message; only the hits come back (functions on an Engine)
   csrc/count_bytes.hip   the decrypted byte messages of a batch classified on the device and counted by choice and group (k_count_classify)
   count.py               counting decrypted messages: count [G][n_choices + 3] and optional per-row classes, dense or packed (functions on
@@ -34,12 +36,13 @@ raises `EngineError` when it (or a GPU) is missing.
 """
 from .engine import (FLAG_NOT_BITS, FLAG_PAD_NONZERO, Engine, EngineError, MultiEngine, library_path,  # noqa: F401
                      load_library)
-from . import combine, count, dedup, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
+from . import audit, combine, count, dedup, lift, mix, noise, packed, scan, shared_product, sharding  # noqa: F401
 from .combine import combine_batch, combine_batch_dev  # noqa: F401
 from .shared_product import mul_shared_batch, mul_shared_batch_dev  # noqa: F401
 from .noise import noise_batch, noise_batch_dev, noise_packed_batch, noise_packed_batch_dev  # noqa: F401
 from .dedup import dedup_packed, dedup_packed_dev, dedup_rows, dedup_rows_dev, dedup_workspace_bytes  # noqa: F401
 from .mix import reencrypt_batch, reencrypt_batch_dev  # noqa: F401
+from .audit import check_links, check_links_dev, open_links, verify_rpc  # noqa: F401
 from .mix import (argsort_keys_dev, draw_permutation, draw_permutation_dev, mix_batch, mix_batch_dev)  # noqa: F401
 from .scan import (scan_bytes_batch, scan_bytes_batch_dev, scan_bytes_packed_batch,  # noqa: F401
                    scan_bytes_packed_batch_dev)

@@ -29,10 +29,50 @@
 // to 2 bytes next to an e_in that is not dword-aligned share an access with it; nothing further away is touched.  An element is
 // staged before the wave that staged it stores to it, so e_out may be e_in when src is NULL (in place).  Offsets are 64-bit:
 // B_in x N x 2 bytes can pass 4 GB.
-struct AddByteImage { static constexpr bool ROWS16 = false; };
+// AddCheckLinks (mix_audit.hip: k_linkcheck_m, k_linkcheck_md; e and quotE are NULL): AddGatherRows16 with a compare in the place of the
+// stores.  Row l claims e_out[dst[l]] == r[l] * h + e_in[src[l]]: the epilogue forms the sum as the re-encrypt kernels do and XORs it
+// with the expected columns, read from global memory where they are used -- this epilogue stores nothing, so the loads do not queue
+// behind stores as the addend's did, and a second stage per wave would cost the second workgroup per CU for 1 % at best
+// (EXPERIMENTS.md "Auditing a mix" has both timings, and what the direct read costs in latency).  The differences of a
+// strip are OR-ed per row by wave ballots into a 32-entry LDS flag table; the row's owner in the r stage tests its bytes and counts
+// into a second table; after the last strip one barrier, and lanes 0-31 store the row block's 32 flag bytes at once.  A link with an
+// index outside its array reads no row (both offsets -1).  Out-of-domain bytes of r: load_a forms the 32 r plane by shifting the
+// dwords of ONE row's fragment, so a carry lands in bytes of the same row of the A operand, and a row of the product depends on that
+// row of A alone: the other links of the row block are not disturbed, and the bad row's own product is ignored (NTRU_LINK_BAD_R).
+struct AddByteImage { static constexpr bool ROWS16 = false, CHECK = false; };
 constexpr int ADD_ROW_PITCH = 272;                        // bytes per staged row segment: 4 tiles x 32 columns x 2 bytes + its dword phase, in 16-byte pieces
+constexpr int CHECK_TABLE_BYTES = 512;                   // AddCheckLinks, behind the addend stages: 32 expected-row offsets, 32 flag words, 32 r verdicts
+struct AddCheckLinks {
+  static constexpr bool ROWS16 = true, CHECK = true;
+  const u16 *e_in;
+  long B_in;
+  const long *src;
+  const u16 *e_out;
+  long B_out;
+  const long *dst;
+  int other, n1, n2;                                      // the domain of r: bytes in {0, 1, other}; counts, each -1 = not tested
+  uint8_t *flags;
+  unsigned long long *n_bad;                              // NULL, or zeroed by the launcher: one atomic per workgroup adds to it
+  // element offsets of a link's two rows into in_ofs / out_ofs, both -1 unless both indices are inside their arrays; true: a link of
+  // the batch with an index outside
+  __device__ __forceinline__ bool link_offsets(long row, long B, int LD, long &in_ofs, long &out_ofs) const {
+    in_ofs = out_ofs = -1;
+    if (row >= B) return false;
+    const long s = src ? src[row] : row, d = dst ? dst[row] : row;
+    if ((unsigned long)s >= (unsigned long)B_in || (unsigned long)d >= (unsigned long)B_out) return true;
+    in_ofs = s * LD;
+    out_ofs = d * LD;
+    return false;
+  }
+  // NTRU_LINK_BAD_R or 0 from a row's totals: bytes outside the domain, ones, bytes equal to `other` (other == 1: the same bytes)
+  __device__ __forceinline__ u32 r_verdict(bool outside, int ones, int others) const {
+    if (outside) return 2u;
+    if (other == 1) return n1 >= 0 && n2 >= 0 && ones != n1 + n2 ? 2u : 0u;
+    return (n1 >= 0 && ones != n1) || (n2 >= 0 && others != n2) ? 2u : 0u;
+  }
+};
 struct AddGatherRows16 {
-  static constexpr bool ROWS16 = true;
+  static constexpr bool ROWS16 = true, CHECK = false;
   const u16 *e_in;
   long B_in;
   const long *src;
@@ -48,7 +88,7 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
                                                       const uint8_t *__restrict__ r,
                                                       const uint8_t *__restrict__ m, long B,
                                                       u16 *__restrict__ e, u16 *__restrict__ quotE, Add add = Add()) {
-  constexpr bool ROWS16 = Add::ROWS16;
+  constexpr bool ROWS16 = Add::ROWS16, CHECK = Add::CHECK;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   // DMA: a barrier that orders LDS traffic only.  With direct-to-LDS loads in flight the compiler puts s_waitcnt vmcnt(0) in front of
   // every __syncthreads() -- which also waits for every outstanding STORE, the very queue the early loads are meant to get ahead of.
@@ -77,6 +117,7 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
   const bool want_q = quotE != nullptr;
   const long nrb = (B + 31) >> 5;
   int sidx = 0, stamp_iter = -1;
+  u32 n_bad_mine = 0;                                    // CHECK: links of this workgroup's row blocks with a flag set (lanes 0-31 of wave 0)
   const long stride = (long)gridDim.x, iters = (nrb + stride - 1) / stride;
   const int rounds = (((g.NT + MAXT - 1) / MAXT) + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
   // DMA: pieces start at absolutely dword-aligned addresses (descriptor based at the dword at or below the row block, size in
@@ -113,6 +154,10 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
   // from the dword at or below the row's first column of the strip (as dma_r); the descriptor ends with the dword that holds the
   // row's last element, and has no bytes at all for a row without an addend.
   unsigned char *stg = mimg + 256 + wave * (32 * ADD_ROW_PITCH);
+  // CHECK: behind the four stages, the element offsets of the 32 expected rows, the flag table the epilogues OR into, the verdicts
+  // on the rows of r
+  long *rowtab2 = (long *)(mimg + 256 + WAVES_PER_BLOCK * (32 * ADD_ROW_PITCH));
+  u32 *flagtab = (u32 *)(rowtab2 + 32), *rtab = flagtab + 32;
   auto stage_addend = [&](int kb0, int lane) {
     if constexpr (ROWS16) {
       const long mine = rowtab[lane & 31];
@@ -127,6 +172,28 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
         if (lane < ADD_ROW_PITCH / 16)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(stg + row * ADD_ROW_PITCH), 16, 16 * lane, 0, 0, 0);
       }
+    }
+  };
+  // CHECK: the row of r a wave has just brought into operand form (16 bytes per lane, columns >= N zero): its bytes outside
+  // {0, 1, other} and its counts, summed over the wave; lane 0 files the verdict.  Bytes are classed four at a time: zero_bytes(x)
+  // has bit 7 of a byte set exactly where that byte of x is zero.
+  auto judge_r = [&](int row, v4i w, int lane) {
+    if constexpr (CHECK) {
+      auto zero_bytes = [](u32 x) { return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; };
+      const u32 oth = 0x01010101u * (u32)add.other;
+      int zeros = 0, ones = 0, others = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        zeros += __builtin_popcount(zero_bytes((u32)w[k]));
+        ones += __builtin_popcount(zero_bytes((u32)w[k] ^ 0x01010101u));
+        others += __builtin_popcount(zero_bytes((u32)w[k] ^ oth));
+      }
+      const bool outside = zeros + ones + (add.other == 1 ? 0 : others) != 16;
+      u32 pair = (u32)ones | ((u32)others << 16);            // each total <= 1024
+#pragma unroll
+      for (int s = 32; s > 0; s >>= 1) pair += (u32)__shfl_xor((int)pair, s, 64);
+      const bool any_outside = __ballot(outside) != 0;
+      if (lane == 0) rtab[row] = add.r_verdict(any_outside, (int)(pair & 0xFFFFu), (int)(pair >> 16));
     }
   };
   if (DMA) {
@@ -171,11 +238,18 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
       }
     }
     long row_ofs = -1;                               // ROWS16: thread t < 32 looks up source row t of the row block
-    if constexpr (ROWS16) if (tid < 32) row_ofs = add.row_offset(b0 + tid, B, LD);
+    long row_ofs2 = -1;                              // CHECK: and the expected row; idx_flag: NTRU_LINK_BAD_INDEX of that link
+    u32 idx_flag = 0;
+    if constexpr (CHECK) {
+      if (tid < 32) idx_flag = add.link_offsets(b0 + tid, B, LD, row_ofs, row_ofs2) ? 1u : 0u;
+    } else if constexpr (ROWS16) {
+      if (tid < 32) row_ofs = add.row_offset(b0 + tid, B, LD);
+    }
     wg_barrier();                                    // the previous row block's readers are done (first pass: key arrays built)
     STAMP(1);
     const int a0m = DMA ? __builtin_amdgcn_readfirstlane((int)((unsigned long long)(m + b0 * LD) & 3)) : 0;   // DMA: the m image starts a0m bytes in
     if constexpr (ROWS16) if (tid < 32) rowtab[tid] = row_ofs;
+    if constexpr (CHECK) if (tid < 32) { rowtab2[tid] = row_ofs2; flagtab[tid] = 0; }
     if (DMA) {                                       // every wave's r rows have landed (each waited for its own in its last epilogue)
       if constexpr (!ROWS16) dma_m(rb, tid);
       const int a0r = (int)((unsigned long long)(r + b0 * LD) & 3);
@@ -195,6 +269,7 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
         v4i v[1];
         shift_raw<1>(in_r[j], s4[j], v);
         if (lane < 2 * g.NT) *(v4i *)(stA + row * g.pitchA + 16 * lane) = v[0] & mk;
+        judge_r(row, v[0] & mk, lane);
       }
     } else {
       const v4i mk = col_mask16(16 * lane, N);
@@ -204,6 +279,7 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
         v4i v[1];
         shift_raw<1>(in_r[j], src_r.a0 + row * LD, v);
         if (lane < 2 * g.NT) *(v4i *)(stA + row * g.pitchA + 16 * lane) = v[0] & mk;
+        judge_r(row, v[0] & mk, lane);
       }
       STAMP(16);
       if constexpr (!ROWS16) {
@@ -260,6 +336,7 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
         // the instruction count: 8-byte stores of four rows per lane group were 14 % SLOWER (profiles/archive/r02_ablation_*).
         const int pv0 = 32 * kb0 + lane;                 // column of this lane in a tile pair starting at tile kb0
         auto out = [&](auto wq) {
+          u32 bad_rows = 0;                              // CHECK: bit R = row R of the row block differs somewhere in this strip (wave-uniform)
 #pragma unroll
           for (int j = 0; j < 4; j++) {                  // 4 rows per half-wave at a time, across the strip's tiles
             u32 mv[NTS][4];
@@ -289,32 +366,53 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
                 ev[t][ii] = (u32)(lo[t][4 * j + ii] + hi[t][4 * j + ii] + (int)mv[t][ii]) & (q - 1);
                 qv[t][ii] = (u32)(0 - hi[t][4 * j + ii]) & (q - 1);
               }
-#pragma unroll
-            for (int t = 0; t + 1 < NTS; t += 2) {       // tile pairs: one row of 64 columns per store
-              const int pvoff = pv0 + 32 * t < N ? 2 * lane : (int)0x80000000;
+            if constexpr (CHECK) {
+              // the expected columns against the sum; a lane without a link or a column keeps its zero.  One bit per row of
+              // the row block: a half-wave holds 32 columns of one row, so a ballot's halves are rows 8 j + ii and 8 j + ii + 4
 #pragma unroll
               for (int ii = 0; ii < 4; ii++) {
-                const auto se = __builtin_amdgcn_permlane32_swap(ev[t][ii], ev[t + 1][ii], false, false);
-                const int so = 2 * ((8 * j + ii) * LD + 32 * (kb0 + t));
-                {
-                  __builtin_amdgcn_raw_buffer_store_b16((u16)se[0], rs_e, pvoff, so, ST_AUX);
-                  __builtin_amdgcn_raw_buffer_store_b16((u16)se[1], rs_e, pvoff, so + 8 * LD, ST_AUX);
-                  if (decltype(wq)::value) {
-                    const auto sq = __builtin_amdgcn_permlane32_swap(qv[t][ii], qv[t + 1][ii], false, false);
-                    __builtin_amdgcn_raw_buffer_store_b16((u16)sq[0], rs_q, pvoff, so, ST_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b16((u16)sq[1], rs_q, pvoff, so + 8 * LD, ST_AUX);
+                const int rw = 8 * j + ii + 4 * (lane >> 5);
+                const long ro = rowtab2[rw];
+                u32 dd = 0;
+#pragma unroll
+                for (int t = 0; t < NTS; t++) {
+                  const int col = 32 * (kb0 + t) + (lane & 31);
+                  const bool ok = ro >= 0 && col < N;
+                  // (unconditional, as the staged read above: a lane without a link or a column reads h[0], which is always there)
+                  const u32 xv = *(ok ? add.e_out + ro + col : h);
+                  dd |= ok ? (ev[t][ii] ^ xv) & (q - 1) : 0u;
+                }
+                const unsigned long long differ = __ballot(dd != 0);
+                bad_rows |= ((u32)differ ? 1u : 0u) << (8 * j + ii) | ((u32)(differ >> 32) ? 1u : 0u) << (8 * j + ii + 4);
+              }
+            } else {
+#pragma unroll
+              for (int t = 0; t + 1 < NTS; t += 2) {       // tile pairs: one row of 64 columns per store
+                const int pvoff = pv0 + 32 * t < N ? 2 * lane : (int)0x80000000;
+#pragma unroll
+                for (int ii = 0; ii < 4; ii++) {
+                  const auto se = __builtin_amdgcn_permlane32_swap(ev[t][ii], ev[t + 1][ii], false, false);
+                  const int so = 2 * ((8 * j + ii) * LD + 32 * (kb0 + t));
+                  {
+                    __builtin_amdgcn_raw_buffer_store_b16((u16)se[0], rs_e, pvoff, so, ST_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b16((u16)se[1], rs_e, pvoff, so + 8 * LD, ST_AUX);
+                    if (decltype(wq)::value) {
+                      const auto sq = __builtin_amdgcn_permlane32_swap(qv[t][ii], qv[t + 1][ii], false, false);
+                      __builtin_amdgcn_raw_buffer_store_b16((u16)sq[0], rs_q, pvoff, so, ST_AUX);
+                      __builtin_amdgcn_raw_buffer_store_b16((u16)sq[1], rs_q, pvoff, so + 8 * LD, ST_AUX);
+                    }
                   }
                 }
               }
-            }
-            if (NTS & 1) {                               // the odd tile out: two rows of 32 columns per store
-              constexpr int t = NTS - 1;
-              const int so = 2 * (8 * j * LD + 32 * (kb0 + t));
-              {
+              if (NTS & 1) {                               // the odd tile out: two rows of 32 columns per store
+                constexpr int t = NTS - 1;
+                const int so = 2 * (8 * j * LD + 32 * (kb0 + t));
+                {
 #pragma unroll
-                for (int ii = 0; ii < 4; ii++) {
-                  __builtin_amdgcn_raw_buffer_store_b16((u16)ev[t][ii], rs_e, voff[t], so + 2 * ii * LD, ST_AUX);
-                  if (decltype(wq)::value) __builtin_amdgcn_raw_buffer_store_b16((u16)qv[t][ii], rs_q, voff[t], so + 2 * ii * LD, ST_AUX);
+                  for (int ii = 0; ii < 4; ii++) {
+                    __builtin_amdgcn_raw_buffer_store_b16((u16)ev[t][ii], rs_e, voff[t], so + 2 * ii * LD, ST_AUX);
+                    if (decltype(wq)::value) __builtin_amdgcn_raw_buffer_store_b16((u16)qv[t][ii], rs_q, voff[t], so + 2 * ii * LD, ST_AUX);
+                  }
                 }
               }
             }
@@ -322,7 +420,11 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
           // DMA: the row loads are older than the S stores issued since and vector memory operations complete in order: at most
           // min(S, 63) outstanding = the rows have landed (and the S - 63 oldest stores with them).  At the END of the epilogue:
           // the loads have had its whole length (phase stamps: waiting after the second group of rows cost ~3 k cycles).
-          constexpr int S = 16 * NTS * (decltype(wq)::value ? 2 : 1), K = S < 63 ? S : 63;
+          // CHECK: no stores follow the row loads, so the wait is for all of them; the strip's verdicts go into the flag table
+          if constexpr (CHECK)
+            if (bad_rows != 0 && lane < 32 && ((bad_rows >> lane) & 1u))
+              __hip_atomic_fetch_or(&flagtab[lane], 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          constexpr int S = CHECK ? 0 : 16 * NTS * (decltype(wq)::value ? 2 : 1), K = S < 63 ? S : 63;
           if (DMA && dma_now && sidx == rounds - 1) __builtin_amdgcn_s_waitcnt((K & 15) | (7 << 4) | (15 << 8) | ((K >> 4) << 14));
         };
         if (want_q) out(std::true_type{}); else out(std::false_type{});
@@ -340,7 +442,19 @@ static __device__ __forceinline__ void encrypt_m_body(MGeom g, u32 q, const u16 
       }
       sidx++;
     }, DMA);
+    if constexpr (CHECK) {
+      wg_barrier();                                  // every wave's strips have filed their verdicts
+      if (tid < 32) {
+        // a bad index or a bad r stands alone: that link's product and rows mean nothing
+        const u32 fl = idx_flag | rtab[tid] ? idx_flag | rtab[tid] : flagtab[tid];
+        const bool mine = b0 + tid < B;
+        if (mine) add.flags[b0 + tid] = (uint8_t)fl;     // 32 bytes side by side: one store per row block
+        n_bad_mine += (u32)__builtin_popcountll(__ballot(mine && fl != 0));
+      }
+    }
   }
+  if constexpr (CHECK)                               // one atomic per workgroup
+    if (threadIdx.x == 0 && add.n_bad && n_bad_mine) atomicAdd(add.n_bad, (unsigned long long)n_bad_mine);
 }
 
 #endif

@@ -102,6 +102,8 @@ _SIGS = {
     **_both("ntru_decrypt_packed_batch", "p iii ppp l pppp"),
     # re-randomising and shuffling under the shared public key: the functions are in mix.py
     **_both("ntru_reencrypt_batch", "p ii ppp l p l pp"),
+    # auditing a mix, checking revealed re-encryption links: the functions are in audit.py
+    **_both("ntru_check_links_batch", "p iiiii pp p l p p l p l pp"),
     # the order of a mix step drawn on the device, and a whole mix step from a key: also in mix.py
     "ntru_argsort_keys_dev": _sig("p p l p"),
     **_both("ntru_draw_permutation", "p p u l pp"),

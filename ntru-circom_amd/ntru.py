@@ -21,6 +21,7 @@ import numpy as np
 from . import combine as combine_calls
 from . import dedup as dedup_calls
 from . import lift as lift_calls
+from . import audit as audit_calls
 from . import mix as mix_calls
 from . import packed as packed_calls
 from . import scan as scan_calls
@@ -599,6 +600,18 @@ class NTRU:
         value, quot, r, src = mix_calls.mix_batch(self.engine, N, q, p, expandArray(self.h, N), key, firstItem, self.dr, self.dr, permId, e,
                                                   want_quot=wantWitness)
         return {"value": value, "r": r, "m": e[src], "src": src, "quotientE": quot}
+
+    def auditLinks(self, e_in, e_out, r, in_idx=None, out_idx=None):
+        """Checks revealed re-encryption links under h: link l holds when e_out[out_idx[l]] == r[l] * h + e_in[in_idx[l]] modulo
+        (x^N - 1, q) (an index list of None: row l).  r: [L][N] signed ternary or already mapped to {0, 1, p - 1}, which must hold dr
+        ones and dr entries p - 1.  Returns {"flags", "bad"}: one byte per link (0, or audit.LINK_*) and the number that are not 0."""
+        N, q, p = self.N, self.q, self.p
+        r = np.asarray(r).reshape(-1, N)
+        r = np.where(r == -1, p - 1, r).astype(np.uint8)
+        flags, bad = audit_calls.check_links(self.engine, N, q, expandArray(self.h, N), r, np.asarray(e_in).reshape(-1, N) % 65536,
+                                             np.asarray(e_out).reshape(-1, N) % 65536, in_idx=in_idx, out_idx=out_idx, other=p - 1,
+                                             n1=self.dr, n2=self.dr)
+        return {"flags": flags, "bad": bad}
 
     # -- generatePublicKeyH, index.js:72-79 ----------------------------------------------------------------
     def generatePublicKeyH(self):
